@@ -238,6 +238,25 @@ def timed_steps(step, args, torch, dist, world, dev):
     return elapsed
 
 
+DUMP_MAX_ROWS = 1 << 22      # rows of y written whole by --dump-outputs (32 MiB of float64); above that, a fixed sample of them
+DUMP_SAMPLE_ROWS = 1 << 21   # the sample: 16 MiB of values and 16 MiB of row numbers
+
+
+def dump_outputs(out_dir, y, np, log):
+    """--dump-outputs: y of the last timed step as a caller of the plan path receives it (original row order, float64).
+    The matrix, x and the sample below are fixed by the arguments, so two builds can be compared entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.size <= DUMP_MAX_ROWS:
+        np.save(os.path.join(out_dir, "y.npy"), y)
+        log(f"[bench] wrote y ({y.nbytes / 1e6:.1f} MB) to {out_dir}/y.npy")
+        return
+    rows = np.sort(np.random.default_rng(0).choice(y.size, DUMP_SAMPLE_ROWS, replace=False))
+    np.save(os.path.join(out_dir, "y_sample.npy"), y[rows])
+    np.save(os.path.join(out_dir, "y_sample_rows.npy"), rows.astype(np.float64))
+    log(f"[bench] wrote {DUMP_SAMPLE_ROWS} of the {y.size} rows of y (seeded sample) to {out_dir}/y_sample.npy, their row numbers to y_sample_rows.npy")
+
+
 def all_ranks_agree_or_exit(bad, worst, torch, dist, world, dev, what):
     """Every rank learns the parity verdict of every other and all leave together."""
     if world > 1:
@@ -754,7 +773,14 @@ def main():
                     help="N>1 strong: skip the run of the same matrix on rank 0's GPU alone (the N = 1 point inside the N > 1 line)")
     ap.add_argument("--no-tune", action="store_true", help="N=1: skip ehyb_plan_tune (the item -> workgroup map stays the built-in one)")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="N=1: after the timed steps, write what the last timed step computed (y in the caller's row order, float64) as DIR/y.npy "
+                         "(above 2^22 rows: a fixed seeded sample of 2^21 rows, DIR/y_sample.npy with its row numbers in DIR/y_sample_rows.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs is an N = 1 option")
     args.host_us_per_step = 0.0
 
     world_env = os.environ.get("WORLD_SIZE")
@@ -911,6 +937,8 @@ def main():
 
     # ---- parity of what was just timed against the CPU oracle
     y = E.vector_recover(y_d.cpu().numpy(), perm)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, np, log)
     bad, worst = O.check_tolerance(y, y_cpu, scale)
     parity = {"rows_over_1e-12": bad, "worst_rel": worst}
     log(f"[bench] parity vs CPU oracle: {bad} rows over 1e-12, worst {worst:.3e}")

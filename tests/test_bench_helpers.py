@@ -179,3 +179,28 @@ def test_frac_follows_from_the_loop_and_carries_the_cold_cache_figure():
     assert r["frac_first_to_last"] == pytest.approx(454.66e6 / 83.15e-6 / 8e12, abs=2e-4)                 # 0.683
     assert r["alg_frac"] > 1.5                                                                              # pairs are read once: SURVEY 8d cannot price them
     assert r["l2_share"] == 0.0
+
+
+def test_dump_outputs_writes_y_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: y as float64 .npy; above DUMP_MAX_ROWS a seeded sample with its row numbers, the same from run
+    to run, and never more than 64 MB in all."""
+    import numpy as np
+
+    y = np.linspace(-1.0, 1.0, 1000)
+    B.dump_outputs(str(tmp_path / "whole"), y, np, lambda *a: None)
+    got = np.load(tmp_path / "whole" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y)
+    monkeypatch.setattr(B, "DUMP_MAX_ROWS", 100)
+    monkeypatch.setattr(B, "DUMP_SAMPLE_ROWS", 50)
+    for d in ("a", "b"):
+        B.dump_outputs(str(tmp_path / d), y, np, lambda *a: None)
+    rows = np.load(tmp_path / "a" / "y_sample_rows.npy")
+    vals = np.load(tmp_path / "a" / "y_sample.npy")
+    assert rows.dtype == vals.dtype == np.float64 and len(rows) == 50 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(vals, y[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "y_sample_rows.npy"))
+    assert not (tmp_path / "a" / "y.npy").exists()
+
+
+def test_dump_outputs_stays_under_64_mb():
+    assert 8 * B.DUMP_MAX_ROWS <= 64e6 and 2 * 8 * B.DUMP_SAMPLE_ROWS <= 64e6

@@ -1,8 +1,12 @@
 """Matrix Market reader of the harness (ehyb_mm_read: the role of matrixRead_sym/_unsym,
-solver_test.c:31-265) against scipy.io and against the reference's own mmio.c, which is
-compiled from where it lies into oracle/_ref/libmmio_ref.so (test infrastructure only)."""
+solver_test.c:31-265) against scipy.io and against the reference's own mmio.c.  What mmio.c
+reads from the golden files is stored in tests/golden/ref_mmio.json; where oracle/Makefile has
+compiled mmio.c into oracle/_ref/libmmio_ref.so (test infrastructure only), the live library
+must give the same answers (`python tests/test_mmio.py` rewrites the file from it)."""
 import ctypes as C
+import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +16,8 @@ import scipy.sparse as sp
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
 REF_MMIO = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libmmio_ref.so")
+REF_MMIO_GOLD = os.path.join(GOLD, "ref_mmio.json")
+GOLD_MTX = ["sym_grid", "gen_band", "pat_graph"]
 
 
 def ref_banner_and_size(path):
@@ -33,7 +39,11 @@ def ref_banner_and_size(path):
     return rc, code.raw.decode(), rc2, m.value, n.value, nz.value
 
 
-@pytest.mark.parametrize("name", ["sym_grid", "gen_band", "pat_graph"])
+def _as_record(rc, code, rc2, M, N, nz):
+    return dict(banner_rc=rc, typecode=code, size_rc=rc2, rows=M, cols=N, stored=nz)
+
+
+@pytest.mark.parametrize("name", GOLD_MTX)
 def test_reader_matches_scipy_and_reference_mmio(E, name):
     path = os.path.join(GOLD, name + ".mtx")
     m = E.Matrix.read_mtx(path)
@@ -42,9 +52,11 @@ def test_reader_matches_scipy_and_reference_mmio(E, name):
     assert abs(m.to_scipy() - S).max() == 0
     assert np.array_equal(np.repeat(np.arange(m.n), np.diff(m.row_idx)), m.I)
     assert m.c.maxCol == np.diff(S.indptr).max()
-    if not os.path.exists(REF_MMIO):
-        pytest.skip("oracle/_ref/libmmio_ref.so not built (needs /root/reference at build time)")
-    rc, code, rc2, M, N, nz = ref_banner_and_size(path)
+    with open(REF_MMIO_GOLD) as f:
+        ref = json.load(f)[name]
+    if os.path.exists(REF_MMIO):
+        assert _as_record(*ref_banner_and_size(path)) == ref
+    rc, code, rc2, M, N, nz = (ref[k] for k in ("banner_rc", "typecode", "size_rc", "rows", "cols", "stored"))
     assert rc == 0 and rc2 == 0 and M == N == m.n
     assert (code[3] == "S") == m.symmetric                      # mm_is_symmetric, solver_test.c:348
     stored = sum(1 for line in open(path) if not line.startswith("%")) - 1
@@ -227,3 +239,12 @@ def test_comment_and_blank_lines_inside_the_body(E, tmp_path):
     np.add.at(d, m.I[m.I == m.J], m.V[m.I == m.J])
     assert np.array_equal(d, 2.0 + np.arange(rows))
     assert np.all(m.V[m.I != m.J] == -1.5) and (m.I != m.J).sum() == 2 * (rows - 1)
+
+
+if __name__ == "__main__":
+    # rewrite tests/golden/ref_mmio.json from oracle/_ref/libmmio_ref.so (built by oracle/Makefile)
+    if not os.path.exists(REF_MMIO):
+        sys.exit("oracle/_ref/libmmio_ref.so is not built")
+    out = {n: _as_record(*ref_banner_and_size(os.path.join(GOLD, n + ".mtx"))) for n in GOLD_MTX}
+    with open(REF_MMIO_GOLD, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")

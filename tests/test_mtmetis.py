@@ -3,7 +3,7 @@
 vendored libmtmetis.a statically -- as the reference's own Makefile does -- and libehyb.so finds the
 partitioner in the process image.  Reorder -> layout -> oracle walk -> reference product, and the
 partition quality next to the built-in partitioner's (the table in DESIGN.md comes from the same tool).
-Skipped where neither the reference tree nor a prebuilt driver exists."""
+Skipped where oracle/Makefile found no reference partitioner to link (the driver is then not built)."""
 import json
 import os
 import subprocess
@@ -23,10 +23,8 @@ CASES = [
 
 @pytest.mark.parametrize("kind,args,lds", CASES, ids=[c[0] for c in CASES])
 def test_mtmetis_backend_end_to_end(E, O, tmp_path, kind, args, lds):
-    if os.path.isdir("/root/reference"):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"], check=True)
     if not os.path.exists(DRIVER):
-        pytest.skip("oracle/_ref/mtmetis_driver not built (needs /root/reference/libmtmetis.a at build time)")
+        pytest.skip("oracle/_ref/mtmetis_driver was not built (oracle/Makefile builds it only where the reference's libmtmetis.a is present)")
     prefix = str(tmp_path / "mt")
     p = subprocess.run([DRIVER, kind] + [str(a) for a in args] + ["--", prefix, str(lds)], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
