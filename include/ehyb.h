@@ -434,6 +434,14 @@ int ehyb_plan_host_array(const ehyb_plan* plan, int which, const void** ptr, int
  * A plan multiplies ONE vector at a time: with the residual in panel form (stats.er_partials > 0) the
  * partial sums of a multiply live in a buffer of the plan, so two multiplies of the same plan must not
  * overlap on different streams (the reference is not re-entrant either: global device counters).
+ * Non-finite values.  A NaN or an infinity in the MATRIX reaches exactly the rows that store it: a row comes out NaN, +inf,
+ * -inf or finite as the exact sum of its entries' products would (that class does not depend on the order of summation), and
+ * no other row changes.  A NaN or an infinity in x makes every row that stores its column non-finite (a NaN is never lost;
+ * an infinity may come out as NaN).  Rows that do NOT store that column may come out NaN as well: padding slots hold the
+ * value 0.0 and still read a column -- ELL lanes without an entry read column 0 of their window, as the reference's ELL
+ * padding does (convert.c), and the padding of an inline residual (stats.er_inline) reads x[0] -- and 0 * inf, 0 * NaN are
+ * NaN.  (A NaN in x[0] alone turns most rows of an inline-residual plan NaN.)  The padding of the panel form and the direct
+ * shape reads nothing.  With every x finite no padding slot changes a result.
  */
 int ehyb_spmv(ehyb_plan* plan, const double* x_dev, double* y_dev, void* stream);
 /*
@@ -618,7 +626,9 @@ int spmvGPuEHYB_cfg(matrixCOO* localMatrix, const double* vectorIn, double* vect
  *                (ehyb_entry_order computes it).
  *   on_device    0: values / entry_order are host arrays (uploaded for the call);  1: both are device pointers.
  * With symmetric pair storage a slot stands for a_ij AND a_ji: the new values must be equal there (a_ij == a_ji, the test the builder paired them with); they
- * are checked on the device first and the plan is left untouched (EHYB_ERR_ARG) if any pair differs.
+ * are checked on the device first and the plan is left untouched (EHYB_ERR_ARG) if any pair differs.  The builder pairs by
+ * VALUE, so on a matrix that is not symmetric entries that merely happened to be equal are pairs too, and new values must
+ * keep them equal; a NaN never equals itself, so a NaN in a pair is refused as well.
  * After a successful call the HOST copy of the value arrays (ehyb_plan_host_array, ehyb_plan_save) is stale:
  * ehyb_plan_save refuses such a plan.  Synchronous with respect to `stream` when on_device = 0.
  */

@@ -136,7 +136,9 @@ int64_t oracle_compare(const double* yResult, const double* y, double threshold,
     return bad;
 }
 
-/* Strict check used by the parity tests: rows with |a-b| > tol * scale[i]; *worst = max |a-b|/scale. */
+/* Check kept for bench.py and smoke(): rows with |a-b| > tol * scale[i]; *worst = max |a-b|/scale.
+ * It does NOT catch NaN: for a NaN row both comparisons are false, so a y full of NaN returns 0 bad rows and
+ * *worst == 0.  The tests use oracle_check_strict below. */
 int64_t oracle_check_tolerance(const double* a, const double* b, const double* scale, int n, double tol,
                                double* worst)
 {
@@ -146,6 +148,30 @@ int64_t oracle_check_tolerance(const double* a, const double* b, const double* s
         double d = fabs(a[i] - b[i]);
         if (d > tol * scale[i]) bad++;
         double r = scale[i] > 0 ? d / scale[i] : (d > 0 ? INFINITY : 0);
+        if (r > w) w = r;
+    }
+    if (worst) *worst = w;
+    return bad;
+}
+
+/* NaN-strict form of oracle_check_tolerance, same signature and return: row i passes if a == b (equal infinities
+ * included), or both are NaN, or both are finite and |a-b| <= tol * scale[i] -- written so that NaN fails the last
+ * test.  (A row of the reference that holds an infinity has an infinite scale; without "both finite" -inf, or any
+ * finite value, would pass against it.)  Every other row is bad; *worst is the largest |a-b|/scale[i] over all rows,
+ * and infinite as soon as a bad row has a NaN or an infinity on either side (or a zero scale). */
+int64_t oracle_check_strict(const double* a, const double* b, const double* scale, int n, double tol, double* worst)
+{
+    int64_t bad = 0;
+    double w = 0;
+    for (int i = 0; i < n; i++) {
+        if (a[i] == b[i] || (isnan(a[i]) && isnan(b[i]))) continue;
+        double d = fabs(a[i] - b[i]);
+        int ok = isfinite(a[i]) && isfinite(b[i]) && d <= tol * scale[i];
+        double r = !isfinite(d) ? INFINITY : scale[i] > 0 ? d / scale[i] : (d > 0 ? INFINITY : 0);
+        if (!ok) {
+            bad++;
+            if (!isfinite(a[i]) || !isfinite(b[i]) || isnan(r)) r = INFINITY;
+        }
         if (r > w) w = r;
     }
     if (worst) *worst = w;

@@ -36,6 +36,8 @@ def lib():
         L.oracle_compare.restype = C.c_int64
         L.oracle_check_tolerance.argtypes = [dp, dp, dp, C.c_int, C.c_double, dp]
         L.oracle_check_tolerance.restype = C.c_int64
+        L.oracle_check_strict.argtypes = [dp, dp, dp, C.c_int, C.c_double, dp]
+        L.oracle_check_strict.restype = C.c_int64
         L.oracle_time_spmv.argtypes = [C.c_int, C.c_int, C.c_int64, i64p, ip, ip, dp, dp, dp, C.c_int]
         L.oracle_time_spmv.restype = C.c_double
         _lib = L
@@ -116,12 +118,25 @@ TOLERANCE = 1e-12  # |y_gpu - y_cpu| <= 1e-12 * sum_j |a_ij x_j|  (SURVEY.md 8c,
 
 
 def check_tolerance(a, b, scale, tol=TOLERANCE):
-    """-> (rows violating |a-b| <= tol*scale, worst |a-b|/scale)."""
+    """-> (rows violating |a-b| <= tol*scale, worst |a-b|/scale).  Does NOT catch NaN: a NaN row violates nothing
+    (a y full of NaN gives (0, 0.0)).  Kept as it is for bench.py and smoke(); the tests use check_strict."""
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
     s = np.ascontiguousarray(scale, dtype=np.float64)
     w = C.c_double()
     bad = lib().oracle_check_tolerance(_d(a), _d(b), _d(s), len(a), tol, C.byref(w))
+    return int(bad), w.value
+
+
+def check_strict(a, b, scale, tol=TOLERANCE):
+    """check_tolerance that NaN cannot pass -> (bad rows, worst |a-b|/scale).  A row passes if a == b (equal infinities
+    included), both are NaN, or both are finite and |a-b| <= tol*scale; worst is inf once a failing row is non-finite on either side."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    s = np.ascontiguousarray(scale, dtype=np.float64)
+    assert a.shape == b.shape == s.shape, (a.shape, b.shape, s.shape)
+    w = C.c_double()
+    bad = lib().oracle_check_strict(_d(a), _d(b), _d(s), len(a), tol, C.byref(w))
     return int(bad), w.value
 
 

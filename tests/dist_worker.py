@@ -45,7 +45,7 @@ def run_case(kind, args, cfg_kw, rank, world):
     y_full[r0:r1] = torch.from_numpy(y_loc[r0:r1])
     D.exchange_segments(y_full, cuts, rank)  # iterating x <- y is the same exchange
     y = E.vector_recover(y_full.numpy(), perm)
-    bad, worst = O.check_tolerance(y, y_ref, scale)
+    bad, worst = O.check_strict(y, y_ref, scale)
     st = plan.stats
     # entry balance of the blocks (one GPU each)
     tot = torch.tensor([float(st["nnz"])], dtype=torch.float64)

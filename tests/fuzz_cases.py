@@ -51,16 +51,32 @@ def random_config_kwargs(rng):
                 ell_alternate=int(rng.choice([0, 1, 1, 2])))
 
 
-def build(E, O, seed):
-    """-> (matrix, plan config, x in original order, oracle y, tolerance scale); the matrix is reordered."""
+def build(E, O, seed, exact=False, **overrides):
+    """-> (matrix, plan config, x in original order, oracle y, tolerance scale); the matrix is reordered.
+    exact=True: the same pattern and configuration with integer values and x (exact_cases.py), and y the exact
+    product; a matrix that is symmetric in value stays so, the others get accidentally equal mirror pairs.
+    overrides: configuration fields set after the random draw (the draw itself is unchanged)."""
     rng = np.random.default_rng(seed)
     A = random_matrix(rng)
     kw = random_config_kwargs(rng)
+    kw.update(overrides)
     cfg = E.make_config(**kw)
+    if exact:
+        from exact_cases import integer_values, integer_x
+
+        I = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+        A.data = integer_values(I, A.indices, symmetric=abs(A - A.T).nnz == 0)
+        x = integer_x(A.shape[0], seed)
     m = E.Matrix.from_csr(A.indptr, A.indices, A.data, cfg)
-    x = O.x_glibc(m.n)
+    if not exact:
+        x = O.x_glibc(m.n)
     if m.nnz:
-        y_ref = O.spmv_coo(m.n, m.I, m.J, m.V, x)
+        if exact:
+            from exact_cases import exact_reference
+
+            y_ref = exact_reference(m.n, m.I, m.J, m.V, x, O)
+        else:
+            y_ref = O.spmv_coo(m.n, m.I, m.J, m.V, x)
         scale = O.abs_rowsum(m.n, m.I, m.J, m.V, x)
         m.reorder(cfg, symmetric=bool(rng.integers(0, 2)) and abs(A - A.T).nnz == 0)
     else:

@@ -76,7 +76,7 @@ def check_rank(tag, I, J, V, cuts, rank, world, cfg, symmetric, chunks=1, shares
     y_plan, written = O.walk_plan(plan, x_ext.numpy())
     assert written[:L.n_loc].min() == 1 and written.sum() == L.n_loc
     y = L.y_from_plan(y_plan[:L.n_loc])
-    bad, worst = O.check_tolerance(y, y_ref, scale)
+    bad, worst = O.check_strict(y, y_ref, scale)
     # the same rows with the all-gather layout: ghost columns = places inside the gathered segments
     G = D.RankLocalMatrix(I, J, V, cuts, rank, cfg, symmetric=symmetric, exchange="allgather")
     seg = G.seg_len
@@ -91,7 +91,7 @@ def check_rank(tag, I, J, V, cuts, rank, world, cfg, symmetric, chunks=1, shares
         assert len(ghc) == 0 or ghc.max() < G.n_loc
         yg, wg = O.walk_plan(gplan, xg.numpy())
         assert wg[:G.n_loc].min() == 1 and wg.sum() == G.n_loc
-        bad_g, _ = O.check_tolerance(G.y_from_plan(yg[:G.n_loc]), y_ref, scale)
+        bad_g, _ = O.check_strict(G.y_from_plan(yg[:G.n_loc]), y_ref, scale)
         bad += bad_g
     tot = torch.tensor([float(L.n_ghost), float(len(V)), float(bad)], dtype=torch.float64)
     dist.all_reduce(tot)
@@ -137,7 +137,7 @@ def check_cover(tag, I, J, V, cuts, rank, world, cfg, chunks=1, shares=None, loo
     hx.transfer_partials()
     y_own = y_t[:L.n_loc].numpy().copy()
     np.add.at(y_own, L.yrecv_idx, hx.ybuf.numpy()[:len(L.yrecv_idx)])
-    bad, worst = O.check_tolerance(L.y_from_plan(y_own), y_ref, scale)
+    bad, worst = O.check_strict(L.y_from_plan(y_own), y_ref, scale)
     tot = torch.tensor([float(R.n_ghost), float(L.n_ghost + int(L.yrecv_counts.sum())), float(L.nnz_exported), float(bad)], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tot)

@@ -37,7 +37,7 @@ def case(tag, I, J, V, cuts, rank, world, cfg, chunks, shares, symmetric, dev, m
         ys.append(sh.y_local())
     bad = 0
     for y in ys:
-        b, worst = O.check_tolerance(y, y_ref, scale)
+        b, worst = O.check_strict(y, y_ref, scale)
         bad += b
     same = bool(np.array_equal(ys[0], ys[1]) and np.array_equal(ys[0], ys[2]))
     gap = float(np.max(np.abs(ys[0] - ys[1]) / np.maximum(scale, 1e-300))) if len(scale) else 0.0

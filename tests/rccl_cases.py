@@ -33,7 +33,8 @@ def comm(gpu):
     c.destroy()
 
 
-def _case(E, O, comm, gen, gargs, cfg_gen, cfg_plan, chunks, shares, loopback, symmetric=False, exchange="halo"):
+def _case(E, O, comm, gen, gargs, cfg_gen, cfg_plan, chunks, shares, loopback, symmetric=False, exchange="halo", exact=False):
+    """exact: integer values and x (exact_cases.py), y_ref the exact product"""
     import torch
 
     from ehyb_spmv_gpu_amd import dist as D
@@ -43,8 +44,15 @@ def _case(E, O, comm, gen, gargs, cfg_gen, cfg_plan, chunks, shares, loopback, s
     n = m.n
     I, J, V = m.I.copy(), m.J.copy(), m.V.copy()
     m.free()
-    x = O.x_glibc(n)
-    y_ref = O.spmv_coo(n, I, J, V, x)
+    if exact:
+        from exact_cases import exact_reference, integer_values, integer_x
+
+        V = integer_values(I, J, symmetric)
+        x = integer_x(n, 5)
+        y_ref = exact_reference(n, I, J, V, x, O)
+    else:
+        x = O.x_glibc(n)
+        y_ref = O.spmv_coo(n, I, J, V, x)
     scale = O.abs_rowsum(n, I, J, V, x)
     L = D.RankLocalMatrix(I, J, V, [0, n], 0, cfg_plan, symmetric=symmetric, chunks=chunks, chunk_shares=shares, loopback=loopback, exchange=exchange)
     assert L.exchanges and L.n_ghost > 0 and int(L.send_counts.sum()) == int(L.recv_counts.sum()) == L.n_ghost
@@ -80,7 +88,7 @@ def test_loopback_step_fem_windows_bit_for_bit(E, O, comm):
     cfg = E.make_config(lds_doubles=4096)
     L, plain, rccl, x, y_ref, scale = _case(E, O, comm, "fem3d", (30000, 3, 22, 22, 13500, 0, 7), cfg, cfg, 2, None, 0.3)
     y0, y1 = _run(plain, x), _run(rccl, x, steps=3)
-    assert O.check_tolerance(y1, y_ref, scale)[0] == 0
+    assert O.check_strict(y1, y_ref, scale)[0] == 0
     assert np.array_equal(y0, y1)
 
 
@@ -92,9 +100,20 @@ def test_loopback_step_rmat_panel_form(E, O, comm, chunks, shares):
     L, plain, rccl, x, y_ref, scale = _case(E, O, comm, "rmat", (17, 1 << 20, 1), cfg, cfgp, chunks, shares, 0.6)
     assert rccl.plan.stats["er_partials"] > 0 and rccl.plan.col_segs == chunks + 1
     y0, y1 = _run(plain, x), _run(rccl, x, steps=2)
-    assert O.check_tolerance(y0, y_ref, scale)[0] == 0 and O.check_tolerance(y1, y_ref, scale)[0] == 0
+    assert O.check_strict(y0, y_ref, scale)[0] == 0 and O.check_strict(y1, y_ref, scale)[0] == 0
     # same launches on the same data: only the order of pass 2's LDS adds may differ
     assert float(np.max(np.abs(y0 - y1) / np.maximum(scale, 1e-300))) < 1e-14
+
+
+def test_loopback_step_rmat_panel_form_exact(E, O, comm):
+    """The panel-form step with three chunks on integer values and x: the plain and the RCCL step both give the exact product
+    bit for bit (the LDS adds of pass 2 and the multiply in parts cannot hide behind a tolerance)."""
+    cfg = E.make_config(partitioner=E.EHYB_PART_DEGREE)
+    cfgp = E.make_config(partitioner=E.EHYB_PART_DEGREE, er_mode=2, er_panel_cols=4096)
+    L, plain, rccl, x, y_ref, scale = _case(E, O, comm, "rmat", (17, 1 << 20, 1), cfg, cfgp, 3, [0.2, 0.3, 0.5], 0.6, exact=True)
+    assert rccl.plan.stats["er_partials"] > 0 and rccl.plan.col_segs == 4
+    y0, y1 = _run(plain, x), _run(rccl, x, steps=2)
+    assert np.array_equal(y0, y_ref) and np.array_equal(y1, y_ref)
 
 
 def test_loopback_step_follows_a_changing_x(E, O, comm):
@@ -112,7 +131,7 @@ def test_loopback_step_follows_a_changing_x(E, O, comm):
     torch.cuda.synchronize()
     for k, y in enumerate(ys):
         got = L.y_from_plan(y.cpu().numpy())
-        assert O.check_tolerance(got, y_ref * (-0.5) ** k, scale * 0.5 ** k)[0] == 0, k
+        assert O.check_strict(got, y_ref * (-0.5) ** k, scale * 0.5 ** k)[0] == 0, k
 
 
 def test_comm_collectives_single_rank(E, comm):
@@ -190,7 +209,7 @@ def test_cover_exchange_over_rccl(E, O, comm):
     assert L.cover and L.n_foreign > 0 and rccl.plan.stats["nnz_ell"] == 0
     print(f"cover: {L.n_ghost} ghost columns + {int(L.yrecv_counts.sum())} partial sums per step, {L.nnz_exported} entries handed over")
     y0 = _run(plain, x)
-    assert O.check_tolerance(y0, y_ref, scale)[0] == 0
+    assert O.check_strict(y0, y_ref, scale)[0] == 0
     rccl.set_x_local(x)
     ys = []
     for k in range(5):
@@ -200,7 +219,7 @@ def test_cover_exchange_over_rccl(E, O, comm):
         rccl.x[:L.n_loc].mul_(-0.5)
     torch.cuda.synchronize()
     for k, y in enumerate(ys):
-        assert O.check_tolerance(L.y_from_plan(y.cpu().numpy()), y_ref * (-0.5) ** k, scale * 0.5 ** k)[0] == 0, k
+        assert O.check_strict(L.y_from_plan(y.cpu().numpy()), y_ref * (-0.5) ** k, scale * 0.5 ** k)[0] == 0, k
 
 
 def test_gather_spmv_single_rank(E, O, comm):
@@ -239,4 +258,4 @@ def test_gather_spmv_single_rank(E, O, comm):
     for _ in range(3):
         assert lib.ehyb_gather_spmv(comm.h, plan.h, xd.data_ptr(), yd.data_ptr(), seg, torch.cuda.current_stream().cuda_stream) == 0, lib.ehyb_last_error()
     torch.cuda.synchronize()
-    assert O.check_tolerance(E.vector_recover(yd.cpu().numpy(), perm), y_ref, scale)[0] == 0
+    assert O.check_strict(E.vector_recover(yd.cpu().numpy(), perm), y_ref, scale)[0] == 0

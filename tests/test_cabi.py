@@ -211,5 +211,5 @@ def test_multiply_ignores_the_environment(E, O, gpu, monkeypatch):
     plan = E.Plan(m, cfg)
     assert plan.stats["er_partials"] > 0
     y = E.vector_recover(plan.spmv_host(E.vector_reorder(x, m.reorder_list)), m.reorder_list)
-    bad, worst = O.check_tolerance(y, y_ref, scale)
+    bad, worst = O.check_strict(y, y_ref, scale)
     assert bad == 0, worst

@@ -8,13 +8,29 @@ import pytest
 
 @pytest.mark.parametrize("world,chunks,cost_model", [(2, 1, 0), (3, 2, 1), (5, 3, 1)])
 def test_cover_step_with_the_ranks_as_threads(E, O, world, chunks, cost_model):
+    _cover_step(E, O, world, chunks, cost_model)
+
+
+def test_cover_step_exact(E, O):
+    """The same step on integer values and x (exact_cases.py): every rank's share, the exchanged partial sums included,
+    adds up to the exact product bit for bit."""
+    _cover_step(E, O, 3, 2, 1, exact=True)
+
+
+def _cover_step(E, O, world, chunks, cost_model, exact=False):
     from ehyb_spmv_gpu_amd import dist as D
+    from exact_cases import exact_reference, integer_values, integer_x
 
     cfg = E.make_config(partitioner=E.EHYB_PART_DEGREE, er_panel_cols=512, er_block_rows=300, lds_doubles=256, host_threads=2)
     full = E.Matrix.generate("rmat", 13, 1 << 16, 2, cfg=cfg)
     n = full.n
-    x = O.x_glibc(n)
-    y_ref = O.spmv_coo(n, full.I, full.J, full.V, x)
+    if exact:
+        full.V[:] = integer_values(full.I, full.J, False)
+        x = integer_x(n, 3)
+        y_ref = exact_reference(n, full.I, full.J, full.V, x, O)
+    else:
+        x = O.x_glibc(n)
+        y_ref = O.spmv_coo(n, full.I, full.J, full.V, x)
     scale = O.abs_rowsum(n, full.I, full.J, full.V, x)
     tr = D.ThreadRanks(world)
     Ls, errs = [None] * world, []
@@ -25,7 +41,8 @@ def test_cover_step_with_the_ranks_as_threads(E, O, world, chunks, cost_model):
             cuts = m.block_cuts
             rp = m.row_idx.astype(np.int64)
             a, b = int(rp[cuts[r]]), int(rp[cuts[r + 1]])
-            Ls[r] = D.RankLocalMatrix(m.I[a:b].copy(), m.J[a:b].copy(), m.V[a:b].copy(), cuts, r, cfg, group=tr.group(r), exchange="cover", chunks=chunks)
+            V = integer_values(m.I[a:b], m.J[a:b], False) if exact else m.V[a:b].copy()
+            Ls[r] = D.RankLocalMatrix(m.I[a:b].copy(), m.J[a:b].copy(), V, cuts, r, cfg, group=tr.group(r), exchange="cover", chunks=chunks)
         except Exception as e:  # noqa: BLE001
             errs.append(repr(e))
             tr.barrier.abort()
@@ -66,5 +83,7 @@ def test_cover_step_with_the_ranks_as_threads(E, O, world, chunks, cost_model):
             off, cnt = S.n_loc + int(S.ysend_counts[:L.rank].sum()), int(S.ysend_counts[L.rank])
             np.add.at(yo, L.yrecv_idx[at:at + cnt], ys[s][off:off + cnt])
             at += cnt
-        bad, worst = O.check_tolerance(L.y_from_plan(yo), y_ref[L.r0:L.r1], scale[L.r0:L.r1])
+        bad, worst = O.check_strict(L.y_from_plan(yo), y_ref[L.r0:L.r1], scale[L.r0:L.r1])
         assert bad == 0, (L.rank, worst)
+        if exact:
+            assert np.array_equal(L.y_from_plan(yo), y_ref[L.r0:L.r1]), L.rank

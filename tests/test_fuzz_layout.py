@@ -14,7 +14,7 @@ def test_random_layout_walk(E, O, seed):
     plan = E.Plan(m, cfg, upload=False)
     yp, written = O.walk_plan(plan, E.vector_reorder(x, m.reorder_list))
     assert (written == 1).all(), kw
-    bad, worst = O.check_tolerance(E.vector_recover(yp, m.reorder_list), y_ref, scale)
+    bad, worst = O.check_strict(E.vector_recover(yp, m.reorder_list), y_ref, scale)
     assert bad == 0, (kw, worst)
     st = plan.stats
     assert st["nnz_ell"] + st["nnz_er"] == m.nnz, kw
@@ -37,4 +37,4 @@ def test_random_plan_cache_round_trip(E, O, seed, tmp_path):
             assert np.array_equal(plan.array(name), back.array(name)), (name, kw)
     assert back.stats == plan.stats, kw
     yp, written = O.walk_plan(back, E.vector_reorder(x, perm))
-    assert (written == 1).all() and O.check_tolerance(E.vector_recover(yp, perm), y_ref, scale)[0] == 0, kw
+    assert (written == 1).all() and O.check_strict(E.vector_recover(yp, perm), y_ref, scale)[0] == 0, kw

@@ -21,7 +21,7 @@ def test_oracle_reproduces_fixture(E, O, name):
     m, y_gold, scale = _load(E, O, name)
     x = O.x_glibc(m.n)
     y = O.spmv_coo(m.n, m.I, m.J, m.V, x)
-    assert O.check_tolerance(y, y_gold, scale)[0] == 0
+    assert O.check_strict(y, y_gold, scale)[0] == 0
     assert np.allclose(O.abs_rowsum(m.n, m.I, m.J, m.V, x), scale, rtol=1e-13, atol=1e-300)
     assert m.symmetric == (name == "sym_grid")
 
@@ -37,7 +37,7 @@ def test_layout_walk_reproduces_fixture(E, O, name, mode):
     yp, written = O.walk_plan(plan, E.vector_reorder(x, m.reorder_list))
     assert (written == 1).all()
     y = E.vector_recover(yp, m.reorder_list)
-    assert O.check_tolerance(y, y_gold, scale)[0] == 0
+    assert O.check_strict(y, y_gold, scale)[0] == 0
 
 
 @pytest.mark.gpu
@@ -49,7 +49,7 @@ def test_gpu_reproduces_fixture(E, O, gpu, name):
     m.reorder(cfg)
     yp, _ = E.spmv_gpu_ehyb(m, E.vector_reorder(x, m.reorder_list), 2)
     y = E.vector_recover(yp, m.reorder_list)
-    bad, worst = O.check_tolerance(y, y_gold, scale)
+    bad, worst = O.check_strict(y, y_gold, scale)
     assert bad == 0, f"{name}: worst {worst:.3e}"
 
 

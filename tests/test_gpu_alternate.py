@@ -40,7 +40,7 @@ def test_both_directions_give_the_product(E, O, gpu, name, kind, args, kw, deter
         plan.spmv(dx.ptr, dy.ptr)
         E.host._lib.load().ehyb_dev_sync()
         ys.append(dy.download())
-        bad, worst = O.check_tolerance(E.vector_recover(ys[-1], perm), y_ref, scale)
+        bad, worst = O.check_strict(E.vector_recover(ys[-1], perm), y_ref, scale)
         assert bad == 0, (name, len(ys), worst)
     if deterministic:                                    # a row's sum does not depend on the order its slab is taken in
         assert np.array_equal(ys[0], ys[1]) and np.array_equal(ys[0], ys[2])
@@ -68,7 +68,7 @@ def test_two_host_threads_share_one_plan(E, O, gpu):
     plan.spmv(dx.ptr, single.ptr)
     E.host._lib.load().ehyb_dev_sync()
     y_one = single.download()
-    assert O.check_tolerance(E.vector_recover(y_one, perm), y_ref, scale)[0] == 0
+    assert O.check_strict(E.vector_recover(y_one, perm), y_ref, scale)[0] == 0
     results, errors = {}, []
 
     def worker(tid):
@@ -114,7 +114,7 @@ def test_explicit_walk_and_captured_graphs_keep_the_product(E, O, gpu, kw, deter
         plan.spmv(dx.ptr, dy.ptr, walk=walk)
         sync()
         ys.append(dy.download())
-        assert O.check_tolerance(E.vector_recover(ys[-1], perm), y_ref, scale)[0] == 0, walk
+        assert O.check_strict(E.vector_recover(ys[-1], perm), y_ref, scale)[0] == 0, walk
     if deterministic:
         assert np.array_equal(ys[0], ys[1]) and np.array_equal(ys[0], ys[2])
     st = E.Stream()
@@ -125,7 +125,7 @@ def test_explicit_walk_and_captured_graphs_keep_the_product(E, O, gpu, kw, deter
             g.launch(st.ptr)
             st.sync()
             y = dy.download()
-            assert O.check_tolerance(E.vector_recover(y, perm), y_ref, scale)[0] == 0, (count, launch)
+            assert O.check_strict(E.vector_recover(y, perm), y_ref, scale)[0] == 0, (count, launch)
             if deterministic:
                 assert np.array_equal(y, ys[0])
         g.destroy()

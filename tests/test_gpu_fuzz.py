@@ -15,7 +15,7 @@ def test_random_plan_on_gpu(E, O, gpu, seed):
     plan = E.Plan(m, cfg)
     xp = E.vector_reorder(x, m.reorder_list)
     y = E.vector_recover(plan.spmv_host(xp, iters=2), m.reorder_list)
-    bad, worst = O.check_tolerance(y, y_ref, scale)
+    bad, worst = O.check_strict(y, y_ref, scale)
     assert bad == 0, (kw, worst)
     # the two-phase call composes to the same result (a plan in the direct shape has no phases)
     dx, dy = E.DeviceBuffer(m.n).upload(xp), E.DeviceBuffer(m.n)
@@ -25,4 +25,4 @@ def test_random_plan_on_gpu(E, O, gpu, seed):
         return
     plan.spmv(dx.ptr, dy.ptr, phase=1)
     plan.spmv(dx.ptr, dy.ptr, phase=2)
-    assert O.check_tolerance(E.vector_recover(dy.download(), m.reorder_list), y_ref, scale)[0] == 0, kw
+    assert O.check_strict(E.vector_recover(dy.download(), m.reorder_list), y_ref, scale)[0] == 0, kw

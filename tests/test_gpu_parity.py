@@ -64,7 +64,7 @@ def test_residual_recomputed_every_iteration(E, O, gpu):
     plan.spmv(dx.ptr, dy.ptr)
     y2 = dy.download()
     scale = O.abs_rowsum(c.n, c.m.I, c.m.J, c.m.V, E.vector_reorder(x2, c.perm))
-    bad, worst = O.check_tolerance(y2, y_ref2, scale)
+    bad, worst = O.check_strict(y2, y_ref2, scale)
     assert bad == 0, f"second multiply with a new x is wrong: worst {worst:.3e}"
 
 
@@ -151,7 +151,7 @@ def test_panel_form_of_the_residual(E, O, gpu, name, kind, args, kw):
     y2 = dy.download()
     ref2 = O.spmv_coo(c.n, c.m.I, c.m.J, c.m.V, x2)
     sc2 = O.abs_rowsum(c.n, c.m.I, c.m.J, c.m.V, x2)
-    assert O.check_tolerance(y2, ref2, sc2)[0] == 0
+    assert O.check_strict(y2, ref2, sc2)[0] == 0
     # deterministic: no global atomics in either pass; LDS adds of one row block may reorder
     y_b = plan.spmv_host(c.xp)
     assert c.check(y_b)[0] == 0

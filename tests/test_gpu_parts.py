@@ -53,13 +53,13 @@ def test_parts_add_up_to_the_whole_multiply(E, O, gpu, name, kind, args, kw):
     E.host._lib.load().ehyb_dev_sync()
     y_parts, y_whole = E.vector_recover(dy.download(), perm), E.vector_recover(dw.download(), perm)
     for y in (y_parts, y_whole):
-        bad, worst = O.check_tolerance(y, y_ref, scale)
+        bad, worst = O.check_strict(y, y_ref, scale)
         assert bad == 0, (name, worst)
     # one call with every segment and both flags is the whole multiply
     dy.upload(np.full(n, np.nan))
     plan.spmv_part(dx.ptr, dy.ptr, 0, 0, 4, 3)
     E.host._lib.load().ehyb_dev_sync()
-    assert O.check_tolerance(E.vector_recover(dy.download(), perm), y_ref, scale)[0] == 0
+    assert O.check_strict(E.vector_recover(dy.download(), perm), y_ref, scale)[0] == 0
 
 
 def test_part_and_segment_arguments_are_checked(E, O, gpu):

@@ -52,7 +52,7 @@ def test_refilled_plan_multiplies_like_a_fresh_one(E, O, gpu, name, kind, args, 
         assert lib.ehyb_dev_sync() == 0
         lib.ehyb_dev_free(dv), lib.ehyb_dev_free(do)
     y2p = plan.spmv_host(c.xp)
-    bad, worst = O.check_tolerance(c.recover(y2p), y2_ref, scale2)
+    bad, worst = O.check_strict(c.recover(y2p), y2_ref, scale2)
     assert bad == 0, f"{name}/{how}: {bad} rows over tolerance after the refill, worst {worst:.3e}"
     # a plan built from scratch from the new matrix: same pattern, same layout
     c.m.V[:] = V2_orig[order]
@@ -69,7 +69,7 @@ def test_refilled_plan_multiplies_like_a_fresh_one(E, O, gpu, name, kind, args, 
         plan.spmv(dx.ptr, dy.ptr, phase=1)
         plan.spmv(dx.ptr, dy.ptr, phase=2)
         assert plan.lib.ehyb_dev_sync() == 0
-        bad, worst = O.check_tolerance(c.recover(dy.download()), y2_ref, scale2)
+        bad, worst = O.check_strict(c.recover(dy.download()), y2_ref, scale2)
         assert bad == 0
     plan.destroy(), fresh.destroy()
 
@@ -105,7 +105,7 @@ def test_bad_arguments(E, O, gpu, tmp_path):
     with pytest.raises(E.EhybError) as ei:      # host copy stale
         plan.save(tmp_path / "stale.plan")
     assert ei.value.code == 8
-    bad, worst = O.check_tolerance(c.recover(plan.spmv_host(c.xp)), 2.0 * c.y_ref, 2.0 * c.scale)
+    bad, worst = O.check_strict(c.recover(plan.spmv_host(c.xp)), 2.0 * c.y_ref, 2.0 * c.scale)
     assert bad == 0
     # a plan without maps, and one that is not on the device
     plain = E.Plan(c.m, E.make_config(lds_doubles=4096, direct=2))

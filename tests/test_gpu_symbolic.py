@@ -62,7 +62,7 @@ def test_device_built_panel_form_equals_the_host_builders(E, O, gpu, name, kind,
     perm = m.reorder_list
     for plan in (host, dev):
         y = E.vector_recover(plan.spmv_host(E.vector_reorder(x, perm)), perm)
-        bad, worst = O.check_tolerance(y, y_ref, scale)
+        bad, worst = O.check_strict(y, y_ref, scale)
         assert bad == 0, (name, worst)
 
 
@@ -82,7 +82,7 @@ def test_device_built_plan_in_column_segments(E, O, gpu):
     dev.spmv_part(dx.ptr, dy.ptr, 0, 1, 3, 0)
     dev.spmv_part(dx.ptr, dy.ptr, 0, 3, 4, 2)
     E.host._lib.load().ehyb_dev_sync()
-    bad, worst = O.check_tolerance(E.vector_recover(dy.download(), perm), y_ref, scale)
+    bad, worst = O.check_strict(E.vector_recover(dy.download(), perm), y_ref, scale)
     assert bad == 0, worst
 
 
@@ -100,14 +100,14 @@ def test_refill_and_cache_of_a_device_built_plan(E, O, gpu, tmp_path):
     loaded, lperm = E.Plan.load(path)
     assert np.array_equal(lperm, perm)
     y = E.vector_recover(loaded.spmv_host(xp), perm)
-    bad, worst = O.check_tolerance(y, y_ref, scale)
+    bad, worst = O.check_strict(y, y_ref, scale)
     assert bad == 0, worst
     # new values on the same pattern
     rng = np.random.default_rng(5)
     v2 = rng.uniform(-1.0, 1.0, m.nnz)
     dev.set_values(v2)
     y2 = dev.spmv_host(xp)                       # (compared in the plan's own numbering: m is the permuted matrix)
-    bad, worst = O.check_tolerance(y2, O.spmv_coo(m.n, m.I, m.J, v2, xp), O.abs_rowsum(m.n, m.I, m.J, v2, xp) + 1e-300)
+    bad, worst = O.check_strict(y2, O.spmv_coo(m.n, m.I, m.J, v2, xp), O.abs_rowsum(m.n, m.I, m.J, v2, xp) + 1e-300)
     assert bad == 0, worst
 
 
@@ -138,7 +138,7 @@ def test_rows_that_are_not_in_column_order(E, O, gpu):
     host, dev = _both(E, m, kw)
     _same_form(host, dev)
     for plan in (host, dev):
-        bad, worst = O.check_tolerance(plan.spmv_host(x), y_ref, scale)
+        bad, worst = O.check_strict(plan.spmv_host(x), y_ref, scale)
         assert bad == 0, worst
 
 

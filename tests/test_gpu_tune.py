@@ -32,5 +32,5 @@ def test_tuned_plan_multiplies_right(E, O, gpu, kw, gen):
         dy.upload(np.full(n, np.nan))
         plan.spmv(dx.ptr, dy.ptr)
         y = E.vector_recover(dy.download(), perm)
-        bad, worst = O.check_tolerance(y, y_ref, scale)
+        bad, worst = O.check_strict(y, y_ref, scale)
         assert bad == 0, (rnd, worst)

@@ -36,7 +36,7 @@ def test_mesh3d_is_symmetric_unstructured_and_walks_to_the_reference_product(E, 
         plan = E.Plan(g, cfg, upload=False)
         yp, written = O.walk_plan(plan, E.vector_reorder(x, g.reorder_list))
         assert (written == 1).all()
-        assert O.check_tolerance(E.vector_recover(yp, g.reorder_list), y_ref, scale)[0] == 0
+        assert O.check_strict(E.vector_recover(yp, g.reorder_list), y_ref, scale)[0] == 0
         if kw.get("sym_pairs"):
             assert plan.stats["sym_pairs"] > 0.25 * plan.stats["nnz"] / 2
 

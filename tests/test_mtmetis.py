@@ -43,7 +43,7 @@ def test_mtmetis_backend_end_to_end(E, O, tmp_path, kind, args, lds):
     assert sorted(perm.tolist()) == list(range(m.n))
     y, written = O.walk_plan(plan, E.vector_reorder(x, perm))
     assert written.min() == 1
-    bad, worst = O.check_tolerance(E.vector_recover(y, perm), y_ref, scale)
+    bad, worst = O.check_strict(E.vector_recover(y, perm), y_ref, scale)
     assert bad == 0, f"worst {worst:.3e}"
 
 

@@ -237,7 +237,7 @@ def test_graded_mesh_asks_for_fewer_partitions(E, O):
     assert st["n_items"] <= 256 and st["sym_pairs"] > 0
     y, written = O.walk_plan(plan, E.vector_reorder(x, m.reorder_list))
     assert written[:m.n].min() == 1 and written[:m.n].max() == 1
-    bad, worst = O.check_tolerance(E.vector_recover(y, m.reorder_list), y_ref, scale)
+    bad, worst = O.check_strict(E.vector_recover(y, m.reorder_list), y_ref, scale)
     assert bad == 0, worst
 
 

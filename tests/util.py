@@ -51,7 +51,7 @@ class Case:
 
     def check(self, yp, tol=None):
         y = self.recover(yp)
-        bad, worst = self.O.check_tolerance(y, self.y_ref, self.scale, tol or self.O.TOLERANCE)
+        bad, worst = self.O.check_strict(y, self.y_ref, self.scale, tol or self.O.TOLERANCE)
         return bad, worst
 
 
