@@ -143,6 +143,8 @@ SIGNATURES = {
     "ehyb_spmv_graph_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _P(_vp)]),
     "ehyb_graph_launch": (C.c_int, [_vp, _vp]),
     "ehyb_graph_destroy": (None, [_vp]),
+    "ehyb_spmm": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int]),
+    "ehyb_spmm_max_k": (C.c_int, [_vp, _ip]),
     "ehyb_plan_tune": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp, _dp]),
     "ehyb_spmv_part": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "ehyb_plan_col_segs": (C.c_int, [_vp, _ip]),

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "ehyb_internal.h"
+#include "ell_device.h"
 
 using namespace ehyb;
 
@@ -126,67 +127,10 @@ __device__ __forceinline__ void er_bin(int lo, int hi, const int64_t* __restrict
 // STAMP:   diagnostic instantiation (tools/stamps.py only): thread 0 records the 100 MHz wall clock
 //          at entry, after the first staging and at exit into a buffer of its own.
 // INLINE_ER: slabs also multiply the residual pairs stored behind their ELL pairs (tiny residuals).
-struct EllArgs {
-    const int4* __restrict__ items;
-    const int4* __restrict__ segs;
-    const int* __restrict__ halo_cols;
-    const uint4* __restrict__ slab_meta;
-    const uint8_t* __restrict__ lane_group;
-    const uint16_t* __restrict__ slab_lrow;  // SYM: the row (place in the LDS image) of every lane, 0xFFFF = none
-    const double2* __restrict__ ell_val;
-    const uint32_t* __restrict__ ell_col;
-    const double* __restrict__ x;
-    double* __restrict__ y;
-    int win_cap;
-    const int* __restrict__ item_map;  // non-null (ehyb_plan_tune): workgroup b takes item item_map[b]
-    int xcd_map;  // 1: workgroup b takes item xcd_item(b), so that each XCD works on one contiguous run of items
-    int windowless_zero;  // 1: a partition without a window gets y = 0 here; 0: the panel residual's second pass assigns its y
-    unsigned long long* __restrict__ stamps;
-    // non-null (ehyb_cg): the workgroup also leaves sum over its rows of y[row] * x[row] in xy_out[blockIdx.x] -- the p.q of
-    // a conjugate-gradient step falls out of the multiply (the rows' x sits in the window, y in registers or accumulators)
-    double* __restrict__ xy_out;
-    // 1: the workgroup walks the slabs of a segment last to first.  Back-to-back multiplies of one plan alternate (cfg.ell_alternate):
-    // what the previous launch streamed LAST is what still sits in the 256 MB Infinity Cache, and this launch reads it FIRST.
-    int reverse;
-    int reverse_items;  // with reverse, and more items than resident workgroups: workgroup b takes the items from the far end too
-    // diagnostic launches only (stamps != null; ehyb_debug_ell_stamps_probe): > 0 = every window entry is staged from THREE vectors instead of
-    // one (x and two shifted copies of it, `probe_n` entries long) -- what folding CG's direction update p = z + beta p into the staging
-    // would gather (r, the old p, 1 / diag): how much longer the launch gets is the price of that fold
-    int probe_n;
-    // The value stream is read ONCE per multiply: loaded with the non-temporal hint it streams past the caches, which then hold what is read
-    // again (column words shared by lanes, lane maps, x) -- 0.69 -> 0.78 of the peak for a launch that walks first to last, every entry stored
-    // 1126 -> 1290 GFLOP/s (profiles/r04_nt_hints_ab.txt).  nt_slabs: the slabs at walk positions below nt_slabs/1024 of a segment are read
-    // that way; the rest, the END of the walk, with plain loads -- what an alternating walk wants the Infinity Cache to keep for the next launch.
-    int nt_slabs;
-};
-
-// Workgroups are handed to the 8 XCDs round robin (b mod 8).  With this map XCD k gets the k-th
-// contiguous eighth of the items: neighbouring partitions, whose halo columns are each other's
-// rows, then share one L2.
-__device__ __forceinline__ int xcd_item(int b, int n)
-{
-    const int k = b & 7, j = b >> 3, chunk = n >> 3, rem = n & 7;
-    return k * chunk + min(k, rem) + j;
-}
-
-// Which work item workgroup b takes: the tuned map of the plan (ehyb_plan_tune: the heaviest items on the XCDs that were
-// measured fastest), else one contiguous run of items per XCD (plain storage), else item b.
-__device__ __forceinline__ int item_of_block(const int* __restrict__ item_map, int xcd_map, int from_the_end = 0)
-{
-    const int b = from_the_end ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-    return item_map ? item_map[b] : (xcd_map ? xcd_item(b, (int)gridDim.x) : b);
-}
+// (The launch arguments EllArgs, the item maps, next_lane and ell_load_pair: ell_device.h, shared with ehyb_spmm.hip.)
 
 // One entry of a slab: gather x from the window; SYM: bit 15 of the column says "this entry also
 // stands for its mirror image": value * x[own row] goes to row `column`'s accumulator in LDS.
-// The value of the next lane (lane + 1), 0 behind the last one: two DPP moves, no LDS traffic.
-__device__ __forceinline__ double next_lane(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // Lanes of a group (equal column lists: the unknowns of a node) send their mirror products to the
 // SAME accumulator.  Summed across the lanes first (`code`: this lane adds for itself and the next
 // 0/1/2 lanes, 3 = a lane before it adds for this one), a group of three costs one ds_add_f64
@@ -214,18 +158,6 @@ __device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double
     }
 }
 
-// the (value, value) pair of one lane: plain, or past the caches
-template <bool NT>
-__device__ __forceinline__ double2 ell_load_pair(const double2* __restrict__ p)
-{
-    if (NT) {
-        double2 r;
-        r.x = __builtin_nontemporal_load(&p->x);
-        r.y = __builtin_nontemporal_load(&p->y);
-        return r;
-    }
-    return *p;
-}
 
 template <bool INLINE_ER, bool SYM, bool NT>
 __device__ __forceinline__ void ell_slab(const EllArgs& A, const double* __restrict__ win, double* yacc, int s, int base,
@@ -842,10 +774,9 @@ __global__ __launch_bounds__(256) void ehyb_read_kernel(const double2* __restric
 
 // ------------------------------------------------------------------ launches
 static size_t ell_lds_bytes(const HostLayout& H) { return ((size_t)H.lds_doubles + 1) / 2 * 16 + 16; }
-static int ell_win_cap(const HostLayout& H) { return (H.lds_doubles + 1) / 2 * 2; }
 
 static thread_local int t_probe_n = 0;   // ehyb_debug_ell_stamps_probe: the stamped launch stages every window entry from three vectors
-static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out = nullptr)
+EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out)
 {
     EllArgs A;
     A.items = (const int4*)P->d_items;
@@ -874,6 +805,30 @@ static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long 
     return A;
 }
 
+// The walk of a launch (ehyb_spmm.hip too): walk >= 0 the caller's explicit direction (ehyb_spmv_walk), -1 the plan's own alternation.
+// (automatic: where the stream does not fit the cache but the cache is still a fair share of it -- the walk from the short slabs
+// up costs the tail of a workgroup a few per cent: audikw_1-like, 439 MB, 83.5 -> 76.0 us; every entry stored, 729 MB, 143.3 ->
+// 136.8; 120 k rows, 65 MB, 15.4 -> 16.2; kkt3d-200, 2.56 GB, 501.9 -> 473.7 once the items are taken from the far end too)
+void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A)
+{
+    const HostLayout& H = P->host;
+    const bool alternates = P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.stats.bytes_format_ell > (256ll << 20) && H.stats.bytes_format_ell <= (8192ll << 20));
+    if (walk >= 0 || alternates) {
+        // the caller's explicit direction (ehyb_spmv_walk), else the plan's own alternation: an atomic flip, so that every one of
+        // several threads launching the same plan draws a direction (plain storage: the result does not depend on it)
+        A->reverse = walk >= 0 ? (walk & 1) : (P->launch_parity.fetch_xor(1, std::memory_order_relaxed) & 1);
+        // more than one round of workgroups: what ran in the last round is what the cache holds, so it runs first now
+        A->reverse_items = (A->reverse && n_items > kNumCU * (lds > 80 * 1024 ? 1 : 2)) ? 1 : 0;
+        // cfg.ell_nt = 3: the END of every walk -- the share of the stream the 256 MB Infinity Cache can hold -- is read with plain loads,
+        // so that it is still there when the next launch starts from that end
+        // (half, three quarters and five quarters of that share measured level: profiles/r04_nt_hints_ab.txt)
+        if (P->cfg.ell_nt == 3) {
+            const double keep = std::min(1.0, (double)(256ll << 20) / (double)std::max<long long>(1, H.stats.bytes_format_ell));
+            A->nt_slabs = (int)(1024.0 * (1.0 - keep));
+        }
+    }
+}
+
 // ell_variant: 0/1 = LDS slab counter (default), 3 = static round-robin (A/B arm, tools/sweep.py --variants)
 
 // The walk direction a caller asked for (ehyb_spmv_walk) while its call is on the stack: -1 = the plan's own alternation.
@@ -896,24 +851,7 @@ static int launch_ell_impl(ehyb_plan* P, const double* x, double* y, hipStream_t
     const size_t lds = ell_lds_bytes(H);
     const bool dyn = P->cfg.ell_variant != 3;
     EllArgs A = ell_args(P, x, y, stamps, xy_out);
-    // (automatic: where the stream does not fit the cache but the cache is still a fair share of it -- the walk from the short slabs
-    // up costs the tail of a workgroup a few per cent: audikw_1-like, 439 MB, 83.5 -> 76.0 us; every entry stored, 729 MB, 143.3 ->
-    // 136.8; 120 k rows, 65 MB, 15.4 -> 16.2; kkt3d-200, 2.56 GB, 501.9 -> 473.7 once the items are taken from the far end too)
-    const bool alternates = P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.stats.bytes_format_ell > (256ll << 20) && H.stats.bytes_format_ell <= (8192ll << 20));
-    if (!STAMP && (t_walk >= 0 || alternates)) {
-        // the caller's explicit direction (ehyb_spmv_walk), else the plan's own alternation: an atomic flip, so that every one of
-        // several threads launching the same plan draws a direction (plain storage: the result does not depend on it)
-        A.reverse = t_walk >= 0 ? (t_walk & 1) : (P->launch_parity.fetch_xor(1, std::memory_order_relaxed) & 1);
-        // more than one round of workgroups: what ran in the last round is what the cache holds, so it runs first now
-        A.reverse_items = (A.reverse && n_items > kNumCU * (lds > 80 * 1024 ? 1 : 2)) ? 1 : 0;
-        // cfg.ell_nt = 3: the END of every walk -- the share of the stream the 256 MB Infinity Cache can hold -- is read with plain loads,
-        // so that it is still there when the next launch starts from that end
-        // (half, three quarters and five quarters of that share measured level: profiles/r04_nt_hints_ab.txt)
-        if (P->cfg.ell_nt == 3 && !STAMP) {
-            const double keep = std::min(1.0, (double)(256ll << 20) / (double)std::max<long long>(1, H.stats.bytes_format_ell));
-            A.nt_slabs = (int)(1024.0 * (1.0 - keep));
-        }
-    }
+    if (!STAMP) ell_walk(P, t_walk, n_items, lds, &A);
     const bool sym = H.sym;
 #define ELL_GO(T, M, I, S)                                                                                  \
     {                                                                                                        \
@@ -1468,6 +1406,7 @@ int ehyb_plan_upload(ehyb_plan* P)
     LDS_ATTR((ehyb_pb_scale_kernel<1024, false, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, false>))
+    if ((rc = spmm_set_lds_attr(lds)) != EHYB_OK) return rc;  // the k-vector window kernels (ehyb_spmm.hip)
 #undef LDS_ATTR_T
 #undef LDS_ATTR_S
 #undef LDS_ATTR

@@ -391,6 +391,20 @@ class Plan:
         _check(self.lib.ehyb_spmv_phase(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), C.c_void_p(stream), phase),
                "ehyb_spmv")
 
+    def spmm(self, x_dev, y_dev, k, ldx=None, ldy=None, stream=0, walk=None):
+        """Asynchronous Y[:, j] = A X[:, j], j < k, on device pointers (ints; column j at X + j*ldx, Y + j*ldy; None = n) --
+        ehyb_spmm: ceil(k / spmm_max_k) passes over the matrix.  walk: None = the plan's own alternation, 0 / 1 explicit."""
+        _check(self.lib.ehyb_spmm(self.h, C.c_void_p(x_dev), self.n if ldx is None else int(ldx), C.c_void_p(y_dev),
+                                  self.n if ldy is None else int(ldy), int(k), C.c_void_p(stream), -1 if walk is None else int(walk)),
+               "ehyb_spmm")
+
+    @property
+    def spmm_max_k(self):
+        """ehyb_spmm_max_k: the widest k one pass over the matrix serves (1..4; build with lds_doubles = 20480 // k for k)."""
+        k = C.c_int(0)
+        _check(self.lib.ehyb_spmm_max_k(self.h, C.byref(k)), "ehyb_spmm_max_k")
+        return k.value
+
     def graph(self, x_dev, y_dev, multiplies=1):
         """ehyb_spmv_graph_create: `multiplies` multiplies captured into a hipGraph that keeps the alternating walk -> SpmvGraph"""
         return SpmvGraph(self, x_dev, y_dev, multiplies)

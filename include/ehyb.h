@@ -470,6 +470,31 @@ int ehyb_spmv_graph_create(ehyb_plan* plan, const double* x_dev, double* y_dev, 
 int ehyb_graph_launch(ehyb_graph* graph, void* stream);
 void ehyb_graph_destroy(ehyb_graph* graph);
 
+/*
+ * SEVERAL VECTORS per pass over the matrix: Y[:, j] = A X[:, j] for j < k.  X, Y: device pointers, column j at X + j*ldx and
+ * Y + j*ldy (column-major: a torch.empty(k, n) is this layout with ld = n); ldx >= n_cols, ldy >= the plan's row_end (n_rows for a
+ * plan of every row).  Only rows [row_begin, row_end) of each Y column are written; nothing between the columns is read or written.
+ * walk: EHYB_WALK_AUTO / _FIRST_TO_LAST / _LAST_TO_FIRST, as ehyb_spmv_walk, for every pass.  Asynchronous on `stream`.
+ * The multiply makes ceil(k / k_max) passes over the matrix (ehyb_spmm_max_k), of widths as even as they come; a pass of width 1
+ * is the ehyb_spmv_walk launch sequence itself, a wider one stages the K columns' windows interleaved in LDS and reads the
+ * matrix's streams once for all of them.  Column j of a plain-storage multiply equals ehyb_spmv of X[:, j] bit for bit, but for
+ * rows the residual splits into several segments (fp64 atomics); with symmetric pair storage the LDS adds' order is free, as
+ * between any two launches.  The non-finite contract of ehyb_spmv holds per column: a non-finite X[c, j] reaches column j only.
+ * EHYB_ERR_ARG for a null pointer, k < 1, an ld too small or a bad walk; EHYB_ERR_STATE on a plan never uploaded.
+ */
+int ehyb_spmm(ehyb_plan* plan, const double* X_dev, int64_t ldx, double* Y_dev, int64_t ldy, int k, void* stream, int walk);
+/*
+ * Widest k one pass over the matrix serves on this plan (1..4).  Host-side only: valid on a plan built by
+ * ehyb_plan_create_host that was never uploaded.
+ *   window plans: min(4, (EHYB_LDS_MAX_DOUBLES * 8 - 16) / (8 * window capacity)) -- K window images (x, with symmetric pair
+ *                 storage the y accumulators too) and the 16-byte slab counter in the 160 KiB of LDS.  A plan built with the
+ *                 default window has k_max = 1: to get a wide plan, build it with cfg.lds_doubles = EHYB_LDS_MAX_DOUBLES / k
+ *                 (the partitions are then sized for k vectors; the one-vector multiply of such a plan still works);
+ *   the direct shape (no window): 4;
+ *   a residual in panel form (stats.er_partials > 0): 1 -- such a plan multiplies one vector per pass.
+ */
+int ehyb_spmm_max_k(const ehyb_plan* plan, int* k_max);
+
 /* phase 1: ELL part only (needs only window columns);  phase 2: residual only
  * (y += ...);  phase 0: both.  Lets a multi-GPU caller overlap the x exchange.
  * Phase 2 must follow phase 1 on the same stream before y is read: where partitions were given up to a
