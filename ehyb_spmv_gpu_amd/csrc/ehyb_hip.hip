@@ -1,6 +1,6 @@
 // HIP kernels for gfx950 (MI355X, CDNA4) and the device half of the C-ABI.
 //
-// Kernels (replace reference kernel.cu:43-284):
+// Kernels (replace reference kernel.cu:43-284; the bodies of the first two are in ell_device.h, written once for K columns):
 //   ehyb_ell_kernel  one workgroup per work item = a run of 64-row slabs of (nearly) equal byte
 //                    count, cut into segments at partition boundaries.  Per segment:
 //                      1. stage the partition's x-window into LDS -- contiguous own segment
@@ -21,6 +21,7 @@
 //                                 accumulators in LDS behind the x image; an entry marked in bit 15
 //                                 of its column also adds value * x[own row] to row `column`
 //                                 (ds_add_f64), so an in-partition pair a_ij == a_ji is read once.
+//                    ehyb_ell_k_kernel is the same kernel for K = 2, 3, 4 columns (ehyb_spmm).
 //   ehyb_er_kernel   CSR residual: G lanes per segment (64/16/4 by segment length), strided
 //                    coalesced (col,val) reads, x gathered from global memory (L2/MALL),
 //                    wavefront shuffle reduction, y[row] += sum -- or one fp64 atomic per
@@ -28,6 +29,8 @@
 //                    kernel.cu:43-67 longRowKernel).  Runs on every multiply that has a residual
 //                    not carried inline (the reference skips it after the first launch: SURVEY 8
 //                    a-10 item 1); it is also phase 2 of the multi-GPU multiply (all remote columns).
+//                    ehyb_er_k_kernel: the same for K = 2, 3, 4 columns.
+//   launch_window / launch_er_csr  the one launch path of each family, for every K.
 // No MFMA: 2 flops per 5.8-10 streamed bytes, HBM-bound.
 //
 // Arms tried and dropped (measurements in DESIGN.md 3.1): software-pipelined slab walk with ping-pong
@@ -40,325 +43,33 @@
 #include <vector>
 
 #include "ehyb_internal.h"
+#include "hip_try.h"
 #include "ell_device.h"
 
 using namespace ehyb;
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            ::ehyb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return _e == hipErrorNoDevice ? EHYB_ERR_NO_DEVICE : EHYB_ERR_HIP;                \
-        }                                                                                     \
-    } while (0)
-
-// ------------------------------------------------------------------ residual segments
-// Residual segments [lo, hi) multiplied by one workgroup: G lanes per segment (64 / 16 / 4 by
-// segment length, longest first), strided coalesced (col,val) reads, x gathered from global
-// memory, shuffle reduction, then y[row] += sum -- plain for rows with one segment (rows are
-// unique, kernel.cu:69-77), one fp64 atomic per segment for split rows (the working form of
-// kernel.cu:43-67).  Called from ehyb_er_kernel, which runs behind the ELL launch.
-// ASSIGN (direct shape, small matrices): y[row] = sum -- every row has exactly one segment.
-// Most residual rows are short (R-MAT 2^22: 22 entries on average), so a lane has one to four entries
-// and the time goes into the CHAIN of dependent loads, not into bandwidth: segment bounds -> (column,
-// value) -> x[column] -> y.  Everything that does not depend on the products is therefore requested up
-// front (row number and the old y with the bounds), and a lane's column/value loads are issued four at
-// a time before the first gather of x (measured on R-MAT 2^22: DESIGN.md 3.2).
-template <int G, int THREADS, bool ASSIGN>
-__device__ __forceinline__ void er_bin(int lo, int hi, const int64_t* __restrict__ seg_ptr,
-                                       const int* __restrict__ seg_row, const int* __restrict__ col,
-                                       const double* __restrict__ val, const double* __restrict__ x,
-                                       double* __restrict__ y)
-{
-    constexpr int SEGS = THREADS / G;
-    const int sub = threadIdx.x % G;
-    for (int base = lo; base < hi; base += SEGS) {  // uniform trip count: every lane reaches the shuffles
-        const int seg = base + threadIdx.x / G;
-        double acc0 = 0.0, acc1 = 0.0;
-        int r = 0;
-        double y_old = 0.0;
-        if (seg < hi) {
-            const int64_t b = seg_ptr[seg], e = seg_ptr[seg + 1];
-            r = seg_row[seg];
-            if (!ASSIGN && sub == 0 && r >= 0) y_old = y[r];  // in flight while the products are formed
-            int64_t k = b + sub;
-            for (; k + 3 * G < e; k += 4 * G) {
-                const int c0 = col[k], c1 = col[k + G], c2 = col[k + 2 * G], c3 = col[k + 3 * G];
-                const double v0 = val[k], v1 = val[k + G], v2 = val[k + 2 * G], v3 = val[k + 3 * G];
-                const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
-                acc0 = fma(v0, x0, acc0);
-                acc1 = fma(v1, x1, acc1);
-                acc0 = fma(v2, x2, acc0);
-                acc1 = fma(v3, x3, acc1);
-            }
-            // up to three more, again all requested before the first use
-            const bool h0 = k < e, h1 = k + G < e, h2 = k + 2 * G < e;
-            const int c0 = h0 ? col[k] : 0, c1 = h1 ? col[k + G] : 0, c2 = h2 ? col[k + 2 * G] : 0;
-            const double v0 = h0 ? val[k] : 0.0, v1 = h1 ? val[k + G] : 0.0, v2 = h2 ? val[k + 2 * G] : 0.0;
-            const double x0 = h0 ? x[c0] : 0.0, x1 = h1 ? x[c1] : 0.0, x2 = h2 ? x[c2] : 0.0;
-            acc0 = fma(v0, x0, acc0);
-            acc1 = fma(v1, x1, acc1);
-            acc0 = fma(v2, x2, acc0);
-        }
-        double acc = acc0 + acc1;
-#pragma unroll
-        for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, G);
-        if (sub == 0 && seg < hi) {
-            if (ASSIGN)
-                y[r] = acc;
-            else if (r < 0)
-                unsafeAtomicAdd(&y[r & 0x7fffffff], acc);
-            else
-                y[r] = y_old + acc;
-        }
-    }
-}
-
-// ------------------------------------------------------------------ ELL kernel
-// items[2b]   = {first segment, end segment, -, -}      items[2b+1] = residual bins of the item
-// segs[2g]    = {partition, first slab, end slab, halo count}
-// segs[2g+1]  = {first row, end row, contiguous window length, halo start}
-// DYN   waves take slabs from an LDS counter (the reference's per-block queue, kernel.cu:142,
-//       164-166; here re-armed per segment) -- the default; false: slabs dealt round-robin (A/B arm).
-//       A third arm -- global per-segment counters plus idle workgroups helping the busiest segment
-//       -- was measured and dropped: the device-scope atomic per slab cost 6 % by itself and the
-//       helping, at ~2 slabs per wave, evened the finish times without shortening the launch.
-// STAMP:   diagnostic instantiation (tools/stamps.py only): thread 0 records the 100 MHz wall clock
-//          at entry, after the first staging and at exit into a buffer of its own.
-// INLINE_ER: slabs also multiply the residual pairs stored behind their ELL pairs (tiny residuals).
-// (The launch arguments EllArgs, the item maps, next_lane and ell_load_pair: ell_device.h, shared with ehyb_spmm.hip.)
-
-// One entry of a slab: gather x from the window; SYM: bit 15 of the column says "this entry also
-// stands for its mirror image": value * x[own row] goes to row `column`'s accumulator in LDS.
-// Lanes of a group (equal column lists: the unknowns of a node) send their mirror products to the
-// SAME accumulator.  Summed across the lanes first (`code`: this lane adds for itself and the next
-// 0/1/2 lanes, 3 = a lane before it adds for this one), a group of three costs one ds_add_f64
-// instead of three that the hardware has to serialise.
-#ifndef EHYB_SYM_GROUP_SUM
-#define EHYB_SYM_GROUP_SUM 1
-#endif
-template <bool SYM>
-__device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double* __restrict__ win, double* yacc, double xi,
-                                          int code, double& acc)
-{
-    if (SYM) {
-        const uint32_t idx = col16 & 0x7fffu;
-        acc = fma(v, win[idx], acc);
-        if (EHYB_SYM_GROUP_SUM) {
-            const double mine = (col16 & 0x8000u) ? v * xi : 0.0;
-            const double n1 = next_lane(mine), n2 = next_lane(n1);
-            const double sum = mine + ((code == 1 || code == 2) ? n1 : 0.0) + (code == 2 ? n2 : 0.0);
-            if ((col16 & 0x8000u) && code != 3) unsafeAtomicAdd(&yacc[idx], sum);  // ds_add_f64
-        } else {
-            if (col16 & 0x8000u) unsafeAtomicAdd(&yacc[idx], v * xi);
-        }
-    } else {
-        acc = fma(v, win[col16], acc);
-    }
-}
-
-
-template <bool INLINE_ER, bool SYM, bool NT>
-__device__ __forceinline__ void ell_slab(const EllArgs& A, const double* __restrict__ win, double* yacc, int s, int base,
-                                         int pe, int lane, double& xy)
-{
-    // slab record {first value pair, first column word, first row, pairs << 16 | residual pairs << 8 | groups - 1}
-    const uint4 sm = A.slab_meta[s];
-    const int np = (int)(sm.w >> 16);
-    const int G = (int)(sm.w & 0x3fu) + 1;  // lanes with equal column lists share one word per pair
-    const double2* __restrict__ v = A.ell_val + (size_t)sm.x * 64 + lane;
-    // the lane's group (bits 0-5) and, with symmetric pairs, its part in the group's sum (bits 6-7)
-    const uint32_t lgb = A.lane_group[(size_t)s * 64 + lane];
-    const int code = SYM ? (int)(lgb >> 6) : 0;
-    const uint32_t* __restrict__ c = A.ell_col + sm.y + (SYM ? (lgb & 0x3fu) : lgb);
-    double acc0 = 0.0, acc1 = 0.0;
-    if (INLINE_ER) {
-        // Inline residual (tiny residuals only): `ner` more pairs behind the slab's ELL pairs, their
-        // columns global -- [pair][2][lane] 32-bit words behind the slab's shared column words.
-        // First, so that the loads are in flight while the ELL pairs stream; only the gather of x
-        // from global memory (L2) waits for them.  No second launch, no read-modify-write of y.
-        const int ner = (int)(sm.w >> 8) & 0xff;
-        const double2* __restrict__ ve = v + (size_t)np * 64;
-        const uint32_t* __restrict__ ce = A.ell_col + sm.y + (size_t)np * G + lane;
-        for (int q = 0; q < ner; ++q) {
-            const double2 vv = ve[q * 64];
-            const uint32_t ca = ce[q * 128], cb = ce[q * 128 + 64];
-            acc0 = fma(vv.x, A.x[ca], acc0);
-            acc1 = fma(vv.y, A.x[cb], acc1);
-        }
-    }
-    // Plain: lane l works on row sm.z + l.  SYM: the rows of a partition sit in its slabs longest
-    // first (any order will do: sums go to the LDS accumulators by row), slab_lrow names the row.
-    const int row = (int)sm.z + lane;
-    const int lrow = SYM ? (int)A.slab_lrow[(size_t)s * 64 + lane] : row - base;  // place in the LDS image
-    const bool has_row = SYM ? lrow != 0xFFFF : row < pe;
-    const double xi = (SYM && has_row) ? win[lrow] : 0.0;
-    // bit 7 of the record: the slab's columns are stored relative to the lane's own row (bands and
-    // stencils: rows with equal offsets share their words); lanes without a row read column 0
-    const uint32_t radd = (!SYM && (sm.w & 0x80u)) ? (uint32_t)lrow : 0u;
-    const uint32_t cmask = (SYM || has_row) ? 0xffffu : 0u;
-#define ELL_COL_LO(c) (SYM ? ((c) & 0xffffu) : ((((c) & 0xffffu) + radd) & cmask))
-#define ELL_COL_HI(c) (SYM ? ((c) >> 16) : ((((c) >> 16) + radd) & cmask))
-    int k = 0;
-    // (an 8-pair step for SYM, 128 VGPRs at 16 waves per CU, measured 1 % slower than this one)
-    for (; k + 4 <= np; k += 4) {
-        const double2 v0 = ell_load_pair<NT>(v + (k + 0) * 64), v1 = ell_load_pair<NT>(v + (k + 1) * 64), v2 = ell_load_pair<NT>(v + (k + 2) * 64), v3 = ell_load_pair<NT>(v + (k + 3) * 64);
-        const uint32_t c0 = c[(k + 0) * G], c1 = c[(k + 1) * G], c2 = c[(k + 2) * G], c3 = c[(k + 3) * G];
-        ell_entry<SYM>(v0.x, ELL_COL_LO(c0), win, yacc, xi, code, acc0);
-        ell_entry<SYM>(v0.y, ELL_COL_HI(c0), win, yacc, xi, code, acc1);
-        ell_entry<SYM>(v1.x, ELL_COL_LO(c1), win, yacc, xi, code, acc0);
-        ell_entry<SYM>(v1.y, ELL_COL_HI(c1), win, yacc, xi, code, acc1);
-        ell_entry<SYM>(v2.x, ELL_COL_LO(c2), win, yacc, xi, code, acc0);
-        ell_entry<SYM>(v2.y, ELL_COL_HI(c2), win, yacc, xi, code, acc1);
-        ell_entry<SYM>(v3.x, ELL_COL_LO(c3), win, yacc, xi, code, acc0);
-        ell_entry<SYM>(v3.y, ELL_COL_HI(c3), win, yacc, xi, code, acc1);
-    }
-    for (; k < np; ++k) {
-        const double2 v0 = ell_load_pair<NT>(v + k * 64);
-        const uint32_t c0 = c[k * G];
-        ell_entry<SYM>(v0.x, ELL_COL_LO(c0), win, yacc, xi, code, acc0);
-        ell_entry<SYM>(v0.y, ELL_COL_HI(c0), win, yacc, xi, code, acc1);
-    }
-#undef ELL_COL_LO
-#undef ELL_COL_HI
-    if (has_row) {
-        if (SYM)
-            unsafeAtomicAdd(&yacc[lrow], acc0 + acc1);  // other lanes scatter into the same accumulator
-        else {
-            A.y[row] = acc0 + acc1;
-            if (A.xy_out != nullptr) xy = fma(acc0 + acc1, win[lrow], xy);  // (own rows are in the window)
-        }
-    }
-}
-
-// Stage the window of segment g and multiply its slabs.
-// SYM (symmetric pair storage): the segment is a whole partition; its rows' accumulators sit in LDS
-// right behind the x image, take the lanes' own sums and the scattered mirror products, and are
-// written to y in one coalesced sweep at the end.
-template <int THREADS, bool DYN, bool INLINE_ER, bool SYM, bool STAMP = false>
-__device__ __forceinline__ void ell_segment(const EllArgs& A, double* __restrict__ win, int* __restrict__ next_slab,
-                                            int g, int lane, int wave, double& xy)
-{
-    constexpr int WAVES = THREADS / 64;
-    const int4 a = A.segs[2 * g], b = A.segs[2 * g + 1];
-    const int sb = a.y, se = a.z, hn = a.w;
-    const int ps = b.x, pe = b.y, wl = b.z, hb = b.w;
-    if (!SYM && wl == 0 && hn == 0) {
-        // a partition whose rows all went to the residual (its window did not pay, plan.cpp): nothing to
-        // stage, no slab to walk -- the residual launch adds to y, so y = 0 in one coalesced sweep
-        // (walking its empty slabs cost 22 us on R-MAT 2^22, 70 us on 2^24)
-        if (!A.windowless_zero) return;  // pb_assign: pass 2 of the panel residual is the only writer of these rows
-        const int r0 = max(ps, (int)A.slab_meta[sb].z), r1 = min(pe, r0 + (se - sb) * 64);
-        for (int i = r0 + (int)threadIdx.x; i < r1; i += THREADS) A.y[i] = 0.0;
-        return;
-    }
-    __syncthreads();  // every wave is done with the previous window and counter
-    // The LDS image starts at the even row at or below the partition start (the layout builder
-    // numbers window-local columns from there); win[0] may hold x[ps-1], unused.
-    const int base = ps & ~1, cnt = wl + (ps & 1);
-    double* yacc = win + cnt + hn;
-    // (SYM: batching all of a thread's staging loads -- indices, then x, stores last -- measured no
-    // faster than these loops: 6.1 vs 6.5 us of staging; the halo gathers set the pace)
-    if (STAMP && A.probe_n > 0) {   // (diagnostic instantiation only: compiled out of the product's kernels)
-        const int n = A.probe_n, o1 = n / 3, o2 = 2 * (n / 3);
-        for (int i = threadIdx.x; i < cnt; i += THREADS) {
-            const int c = min(base + i, n - 1);
-            win[i] = A.x[c] + 1e-300 * (A.x[(c + o1) % n] + A.x[(c + o2) % n]);
-        }
-        for (int i = threadIdx.x; i < hn; i += THREADS) {
-            const int c = A.halo_cols[hb + i];
-            win[cnt + i] = A.x[c] + 1e-300 * (A.x[(c + o1) % n] + A.x[(c + o2) % n]);
-        }
-    } else if (STAMP && A.probe_n < 0) {   // (diagnostic: no halo gather at all -- results wrong, the launch span is what hiding the gather could reach at best)
-        for (int i = threadIdx.x; i < cnt; i += THREADS) win[i] = A.x[base + i];
-        for (int i = threadIdx.x; i < hn; i += THREADS) win[cnt + i] = 1.0;
-    } else {
-        for (int i = threadIdx.x; i < cnt; i += THREADS) win[i] = A.x[base + i];
-        for (int i = threadIdx.x; i < hn; i += THREADS) win[cnt + i] = A.x[A.halo_cols[hb + i]];
-    }
-    if (SYM)
-        for (int i = threadIdx.x; i < cnt; i += THREADS) yacc[i] = 0.0;
-    if (DYN && threadIdx.x == 0) *next_slab = sb + WAVES;  // slabs sb..sb+WAVES-1 are pre-assigned
-    __syncthreads();
-    // diagnostic launches only (tools/stamps.py): when the first window of the item was staged
-    if (A.stamps != nullptr && threadIdx.x == 0 &&
-        g == A.items[2 * item_of_block(A.item_map, A.xcd_map)].x)
-        A.stamps[4 * blockIdx.x + 1] = wall_clock64();
-    int s = sb + wave;  // (logical position in the segment's walk; the slab it stands for depends on the direction)
-    const int nt_end = sb + (int)(((long long)(se - sb) * A.nt_slabs + 1023) >> 10);   // walk positions below it: value stream past the caches
-    while (s < se) {
-        if (s < nt_end)
-            ell_slab<INLINE_ER, SYM, true>(A, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
-        else
-            ell_slab<INLINE_ER, SYM, false>(A, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
-        if (DYN) {
-            int nx = 0;
-            if (lane == 0) nx = atomicAdd(next_slab, 1);
-            s = __builtin_amdgcn_readfirstlane(nx);
-        } else {
-            s += WAVES;
-        }
-    }
-    if (SYM) {
-        __syncthreads();  // all sums and scatters of the partition are in
-        // (Folding the pairs that straddle two partitions as well -- 13 % fewer bytes on the bench
-        // matrix -- would need y zeroed first and this write-out plus one add per halo column done
-        // with global atomics: that alone was measured at +12.5 us per launch, more than the bytes save.)
-        if (A.xy_out != nullptr) {
-            for (int i = threadIdx.x + (ps & 1); i < cnt; i += THREADS) {
-                A.y[base + i] = yacc[i];
-                xy = fma(yacc[i], win[i], xy);
-            }
-        } else {
-            for (int i = threadIdx.x + (ps & 1); i < cnt; i += THREADS) A.y[base + i] = yacc[i];
-        }
-    }
-}
-
-template <int THREADS, bool DYN, bool STAMP, bool INLINE_ER, bool SYM>
+// ------------------------------------------------------------------ window kernel and CSR residual (bodies: ell_device.h)
+// Thin entry points over the K-templated bodies: one instantiation per (workgroup size, K, walk form, inline residual,
+// storage); their names and arguments are what profiles, bench.py and tools/pmc_parse.py know.
 // Plain: <= 64 VGPRs (8 waves per SIMD), so that two 1024-thread workgroups share a CU when the caller picks
 // a window of <= 80 KiB; at the default 160 KiB window one runs per CU (an 8-pair step with 128 VGPRs was
 // measured there too: no gain).  SYM always runs one workgroup per CU (its window holds x and the y
 // accumulators): 4 waves per SIMD, up to 128 VGPRs, no spills.
+template <int THREADS, bool DYN, bool STAMP, bool INLINE_ER, bool SYM>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SYM ? 4 : 8, 8))) void ehyb_ell_kernel(const EllArgs A)
 {
-    extern __shared__ __attribute__((aligned(16))) double win[];
-    int* next_slab = reinterpret_cast<int*>(win + A.win_cap);  // one word behind the window
-    if (STAMP && threadIdx.x == 0) A.stamps[4 * blockIdx.x + 0] = wall_clock64();
-    const int4 it = A.items[2 * item_of_block(A.item_map, A.xcd_map, A.reverse_items)];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double xy = 0.0;
-    for (int sg = it.x; sg < it.y; ++sg) {
-        ell_segment<THREADS, DYN, INLINE_ER, SYM, STAMP>(A, win, next_slab, sg, lane, wave, xy);
-    }
-    if (A.xy_out != nullptr) {  // (wave-uniform: a kernel argument)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) xy += __shfl_xor(xy, off, 64);
-        __syncthreads();  // every wave is done with the last window
-        if (lane == 0) win[wave] = xy;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int w = 0; w < THREADS / 64; ++w) t += win[w];  // fixed order
-            A.xy_out[blockIdx.x] = t;
-        }
-    }
-    if (STAMP) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            A.stamps[4 * blockIdx.x + 2] = wall_clock64();
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            A.stamps[4 * blockIdx.x + 3] = xcc;
-        }
-    }
+    ell_items<THREADS, 1, DYN, STAMP, INLINE_ER, SYM>(A, 0, 0);
 }
 
-// ------------------------------------------------------------------ residual kernel
-// Two-launch form (multi-GPU phase 2, or a residual too large to ride in the ELL launch): one
-// block per descriptor {seg_lo, seg_hi, lanes per segment}, a single pass of same-bin segments.
+// A K-wide window fills the CU: one workgroup per CU for every K and storage, up to 128 VGPRs.
+template <int THREADS, int K, bool INLINE_ER, bool SYM>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void ehyb_ell_k_kernel(const EllArgs A, const long long ldx,
+                                                                                                       const long long ldy)
+{
+    ell_items<THREADS, K, true, false, INLINE_ER, SYM>(A, ldx, ldy);
+}
+
+// Two-launch form (multi-GPU phase 2, or a residual too large to ride in the window launch).
 template <int THREADS, bool ASSIGN>
 __global__ __launch_bounds__(THREADS) void ehyb_er_kernel(const int4* __restrict__ blocks,
                                                           const int64_t* __restrict__ seg_ptr,
@@ -367,13 +78,16 @@ __global__ __launch_bounds__(THREADS) void ehyb_er_kernel(const int4* __restrict
                                                           const double* __restrict__ val,
                                                           const double* __restrict__ x, double* __restrict__ y)
 {
-    const int4 b = blocks[blockIdx.x];  // (the XCD map of the ELL kernel was tried here: no difference on R-MAT)
-    if (b.z == 64)
-        er_bin<64, THREADS, ASSIGN>(b.x, b.y, seg_ptr, seg_row, col, val, x, y);
-    else if (b.z == 16)
-        er_bin<16, THREADS, ASSIGN>(b.x, b.y, seg_ptr, seg_row, col, val, x, y);
-    else
-        er_bin<4, THREADS, ASSIGN>(b.x, b.y, seg_ptr, seg_row, col, val, x, y);
+    er_blocks<THREADS, ASSIGN, 1>(blocks, seg_ptr, seg_row, col, val, x, 0, y, 0);
+}
+
+template <int THREADS, bool ASSIGN, int K>
+__global__ __launch_bounds__(THREADS) void ehyb_er_k_kernel(const int4* __restrict__ blocks, const int64_t* __restrict__ seg_ptr,
+                                                            const int* __restrict__ seg_row, const int* __restrict__ col,
+                                                            const double* __restrict__ val, const double* __restrict__ x, const long long ldx,
+                                                            double* __restrict__ y, const long long ldy)
+{
+    er_blocks<THREADS, ASSIGN, K>(blocks, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
 }
 
 // ------------------------------------------------------------------ panel residual (er_panel.cpp)
@@ -773,10 +487,8 @@ __global__ __launch_bounds__(256) void ehyb_read_kernel(const double2* __restric
 }
 
 // ------------------------------------------------------------------ launches
-static size_t ell_lds_bytes(const HostLayout& H) { return ((size_t)H.lds_doubles + 1) / 2 * 16 + 16; }
-
 static thread_local int t_probe_n = 0;   // ehyb_debug_ell_stamps_probe: the stamped launch stages every window entry from three vectors
-EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out)
+static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out)
 {
     EllArgs A;
     A.items = (const int4*)P->d_items;
@@ -796,7 +508,7 @@ EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* s
     A.reverse_items = 0;
     A.probe_n = stamps ? t_probe_n : 0;
     // a stream the 256 MB Infinity Cache holds whole stays there from one multiply to the next: plain loads (120 k rows, 65 MB: 15.4 us, with the hint
-    // 16.2); cfg.ell_nt = 1 forces the hint.  (launch_ell_impl lowers nt_slabs for an alternating walk with cfg.ell_nt = 3)
+    // 16.2); cfg.ell_nt = 1 forces the hint.  (ell_walk lowers nt_slabs for an alternating walk with cfg.ell_nt = 3)
     A.nt_slabs = (P->cfg.ell_nt == 2 || (P->cfg.ell_nt != 1 && P->host.stats.bytes_format_ell <= (256ll << 20))) ? 0 : 1024;
     // on by default: plain storage 143 -> 134 us on the audikw_1-like matrix; cfg.xcd_map = 2 for the A/B
     A.xcd_map = P->host.sym ? 0 : (P->cfg.xcd_map != 2 ? 1 : 0);
@@ -805,11 +517,11 @@ EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* s
     return A;
 }
 
-// The walk of a launch (ehyb_spmm.hip too): walk >= 0 the caller's explicit direction (ehyb_spmv_walk), -1 the plan's own alternation.
+// The walk of a launch: walk >= 0 the caller's explicit direction (ehyb_spmv_walk, ehyb_spmm), -1 the plan's own alternation.
 // (automatic: where the stream does not fit the cache but the cache is still a fair share of it -- the walk from the short slabs
 // up costs the tail of a workgroup a few per cent: audikw_1-like, 439 MB, 83.5 -> 76.0 us; every entry stored, 729 MB, 143.3 ->
 // 136.8; 120 k rows, 65 MB, 15.4 -> 16.2; kkt3d-200, 2.56 GB, 501.9 -> 473.7 once the items are taken from the far end too)
-void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A)
+static void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A)
 {
     const HostLayout& H = P->host;
     const bool alternates = P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.stats.bytes_format_ell > (256ll << 20) && H.stats.bytes_format_ell <= (8192ll << 20));
@@ -829,8 +541,6 @@ void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A)
     }
 }
 
-// ell_variant: 0/1 = LDS slab counter (default), 3 = static round-robin (A/B arm, tools/sweep.py --variants)
-
 // The walk direction a caller asked for (ehyb_spmv_walk) while its call is on the stack: -1 = the plan's own alternation.
 static thread_local int t_walk = -1;
 namespace {
@@ -841,50 +551,87 @@ struct WalkScope {
 };
 }  // namespace
 
-template <bool STAMP>
-static int launch_ell_impl(ehyb_plan* P, const double* x, double* y, hipStream_t st, bool inl, unsigned long long* stamps, double* xy_out = nullptr)
+// Every window-kernel instantiation: the one-vector kernel with both slab walks (DYN), plain and stamped; the k-vector kernel
+// for K = 2..kSpmmMaxK with the LDS counter only.  Behind every window launch and the LDS opt-in of ehyb_plan_upload.
+struct EllKernel {
+    int threads, k;
+    bool dyn, stamp, inl, sym;
+    const void* fn;
+};
+
+template <int T, int K, bool DYN, bool STAMP, bool INL, bool SYM>
+static EllKernel ell_kernel()
+{
+    if constexpr (K == 1)
+        return {T, K, DYN, STAMP, INL, SYM, (const void*)ehyb_ell_kernel<T, DYN, STAMP, INL, SYM>};
+    else
+        return {T, K, DYN, STAMP, INL, SYM, (const void*)ehyb_ell_k_kernel<T, K, INL, SYM>};
+}
+
+// the four forms (inline residual or not, symmetric pairs or not) of one workgroup size, K, walk and stamping
+template <int T, int K, bool DYN = true, bool STAMP = false>
+static void add_ell_kernels(std::vector<EllKernel>* v)
+{
+    v->insert(v->end(), {ell_kernel<T, K, DYN, STAMP, false, false>(), ell_kernel<T, K, DYN, STAMP, true, false>(),
+                         ell_kernel<T, K, DYN, STAMP, false, true>(), ell_kernel<T, K, DYN, STAMP, true, true>()});
+}
+
+template <int T>
+static void add_ell_kernels(std::vector<EllKernel>* v)
+{
+    add_ell_kernels<T, 1, true, false>(v);
+    add_ell_kernels<T, 1, false, false>(v);
+    add_ell_kernels<T, 1, true, true>(v);
+    add_ell_kernels<T, 1, false, true>(v);
+    add_ell_kernels<T, 2>(v);
+    add_ell_kernels<T, 3>(v);
+    add_ell_kernels<T, 4>(v);
+}
+
+static const std::vector<EllKernel>& ell_kernels()
+{
+    static const std::vector<EllKernel> all = [] {
+        std::vector<EllKernel> v;
+        add_ell_kernels<1024>(&v);  // (the default size first: the launches look their kernel up here)
+        add_ell_kernels<512>(&v);
+        add_ell_kernels<256>(&v);
+        return v;
+    }();
+    return all;
+}
+
+int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, bool inl, int walk,
+                        unsigned long long* stamps, double* xy_out)
 {
     const HostLayout& H = P->host;
     const int n_items = (int)(H.items.size() / 8);
     if (n_items == 0 || H.direct) return EHYB_OK;  // direct shape: the row-segment kernel does everything
     if (H.pb_assign && H.segs.empty()) return EHYB_OK;  // no partition kept its window: pass 2 of the panel residual assigns every row
-    const size_t lds = ell_lds_bytes(H);
-    const bool dyn = P->cfg.ell_variant != 3;
+    // cfg.ell_variant: 0/1 = LDS slab counter (default), 3 = static round-robin (A/B arm, tools/sweep.py --variants; one vector only)
+    const bool dyn = k > 1 || P->cfg.ell_variant != 3;
+    const void* fn = nullptr;
+    for (const EllKernel& e : ell_kernels()) {
+        if (e.threads == P->cfg.threads && e.k == k && e.dyn == dyn && e.stamp == (stamps != nullptr) && e.inl == inl && e.sym == H.sym) {
+            fn = e.fn;
+            break;
+        }
+    }
+    if (!fn) EHYB_FAIL(EHYB_ERR_ARG, "ELL workgroup size %d not built (256/512/1024)", P->cfg.threads);
+    const size_t lds = ell_lds_bytes(H, k);
     EllArgs A = ell_args(P, x, y, stamps, xy_out);
-    if (!STAMP) ell_walk(P, t_walk, n_items, lds, &A);
-    const bool sym = H.sym;
-#define ELL_GO(T, M, I, S)                                                                                  \
-    {                                                                                                        \
-        if (STAMP) HIP_TRY(hipFuncSetAttribute((const void*)ehyb_ell_kernel<T, M, STAMP, I, S>,              \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-        hipLaunchKernelGGL((ehyb_ell_kernel<T, M, STAMP, I, S>), dim3(n_items), dim3(T), lds, st, A);        \
-    }
-#define ELL_MODE(T, I, S)           \
-    if (dyn) ELL_GO(T, true, I, S)  \
-    else ELL_GO(T, false, I, S)
-#define ELL_INL(T, S)                 \
-    if (inl) { ELL_MODE(T, true, S) } \
-    else { ELL_MODE(T, false, S) }
-#define ELL_LAUNCH(T)           \
-    if (sym) { ELL_INL(T, true) } \
-    else { ELL_INL(T, false) }
-    switch (P->cfg.threads) {
-        case 256: ELL_LAUNCH(256) break;
-        case 512: ELL_LAUNCH(512) break;
-        case 1024: ELL_LAUNCH(1024) break;
-        default: EHYB_FAIL(EHYB_ERR_ARG, "ELL workgroup size %d not built (256/512/1024)", P->cfg.threads);
-    }
-#undef ELL_LAUNCH
-#undef ELL_INL
-#undef ELL_MODE
-#undef ELL_GO
+    if (stamps)
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    else
+        ell_walk(P, walk, n_items, lds, &A);
+    void* args[] = {&A, &ldx, &ldy};  // (the one-vector kernel takes A alone)
+    (void)hipLaunchKernel(fn, dim3(n_items), dim3(P->cfg.threads), args, lds, st);  // as <<< >>>: a failed launch is the last error
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
 
 static int launch_ell(ehyb_plan* P, const double* x, double* y, hipStream_t st, bool inl)
 {
-    return launch_ell_impl<false>(P, x, y, st, inl, nullptr);
+    return launch_window(P, x, 0, y, 0, 1, st, inl, t_walk);
 }
 
 // y = A x with x . y as a by-product (ehyb_cg.hip): possible where ONE ELL launch writes the final y of every row from a
@@ -901,7 +648,7 @@ int ehyb::spmv_xy_partials(const ehyb_plan* P)
 int ehyb::spmv_xy(ehyb_plan* P, const double* x, double* y, void* stream, double* xy_partials)
 {
     if (spmv_xy_partials(P) == 0 || !x || !y || !xy_partials) EHYB_FAIL(EHYB_ERR_STATE, "spmv_xy: not a plan that multiplies in one window launch");
-    return launch_ell_impl<false>(P, x, y, (hipStream_t)stream, P->host.inline_er, nullptr, xy_partials);
+    return launch_window(P, x, 0, y, 0, 1, (hipStream_t)stream, P->host.inline_er, t_walk, nullptr, xy_partials);
 }
 
 // which: 1 = pass 1 (scale), 2 = pass 2 (reduce), 3 = both; pass 1 over the items [unit_begin, unit_end) (-1: all)
@@ -982,23 +729,30 @@ static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st
     return EHYB_OK;
 }
 
-static int launch_er(ehyb_plan* P, const double* x, double* y, hipStream_t st)
+int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st)
 {
     const HostLayout& H = P->host;
-    if (H.er_bins[3] == 0 && !H.er_panel) return EHYB_OK;  // (er_bins[3] = CSR segments: a device-built panel form has none)
-    if (H.er_panel) {  // panel form: scale (x panels in LDS) then reduce (y blocks in LDS)
-        return launch_panel(P, x, y, st, 0, 3);  // (probe arms only through ehyb_debug_panel_times)
-    }
+    if (H.er_bins[3] == 0) return EHYB_OK;
     const int n_blocks = (int)(H.er_blocks.size() / 4);
     if (P->cfg.er_threads != 256) EHYB_FAIL(EHYB_ERR_ARG, "residual workgroup size %d not built (256)", P->cfg.er_threads);
-    if (H.direct)
-        hipLaunchKernelGGL((ehyb_er_kernel<256, true>), dim3(n_blocks), dim3(256), 0, st, (const int4*)P->d_er_blocks,
-                           P->d_er_seg_ptr, P->d_er_seg_row, P->d_er_col, P->d_er_val, x, y);
-    else
-        hipLaunchKernelGGL((ehyb_er_kernel<256, false>), dim3(n_blocks), dim3(256), 0, st, (const int4*)P->d_er_blocks,
-                           P->d_er_seg_ptr, P->d_er_seg_row, P->d_er_col, P->d_er_val, x, y);
+    const void* fn[2][kSpmmMaxK] = {
+        {(const void*)ehyb_er_kernel<256, false>, (const void*)ehyb_er_k_kernel<256, false, 2>, (const void*)ehyb_er_k_kernel<256, false, 3>,
+         (const void*)ehyb_er_k_kernel<256, false, 4>},
+        {(const void*)ehyb_er_kernel<256, true>, (const void*)ehyb_er_k_kernel<256, true, 2>, (const void*)ehyb_er_k_kernel<256, true, 3>,
+         (const void*)ehyb_er_k_kernel<256, true, 4>}};
+    const int4* blocks = (const int4*)P->d_er_blocks;
+    void* args1[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &y};
+    void* argsk[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &ldx, &y, &ldy};
+    (void)hipLaunchKernel(fn[H.direct][k - 1], dim3(n_blocks), dim3(256), k == 1 ? args1 : argsk, 0, st);  // ASSIGN: the direct shape
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
+}
+
+static int launch_er(ehyb_plan* P, const double* x, double* y, hipStream_t st)
+{
+    if (P->host.er_panel)  // panel form: scale (x panels in LDS) then reduce (y blocks in LDS)
+        return launch_panel(P, x, y, st, 0, 3);  // (probe arms only through ehyb_debug_panel_times)
+    return launch_er_csr(P, x, 0, y, 0, 1, st);
 }
 
 // Where the residual runs (decided by the layout builder, HostLayout::inline_er).  Its own launch
@@ -1166,7 +920,7 @@ int ehyb_debug_ell_stamps(ehyb_plan* P, const double* x, double* y, unsigned lon
     unsigned long long* d = nullptr;
     HIP_TRY(hipMalloc((void**)&d, (size_t)n_items * 32));
     HIP_TRY(hipMemset(d, 0, (size_t)n_items * 32));
-    int rc = launch_ell_impl<true>(P, x, y, nullptr, P->host.inline_er, d);
+    int rc = launch_window(P, x, 0, y, 0, 1, nullptr, P->host.inline_er, -1, d);
     if (rc == EHYB_OK && hipDeviceSynchronize() != hipSuccess) rc = EHYB_ERR_HIP;
     if (rc == EHYB_OK && hipMemcpy(out_host, d, (size_t)n_items * 32, hipMemcpyDeviceToHost) != hipSuccess) rc = EHYB_ERR_HIP;
     if (rc == EHYB_ERR_HIP) set_error("ehyb_debug_ell_stamps: %s", hipGetErrorString(hipGetLastError()));
@@ -1225,7 +979,7 @@ int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* s
         double span = 0;
         for (int r = 0; r < reps + 1; ++r) {  // the first launch warms the caches and is not counted
             if (hipMemset(d, 0, (size_t)n_items * 32) != hipSuccess) return EHYB_ERR_HIP;
-            const int rc = launch_ell_impl<true>(P, x, y, nullptr, H.inline_er, d);
+            const int rc = launch_window(P, x, 0, y, 0, 1, nullptr, H.inline_er, -1, d);
             if (rc != EHYB_OK) return rc;
             if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(st.data(), d, (size_t)n_items * 32, hipMemcpyDeviceToHost) != hipSuccess) return EHYB_ERR_HIP;
             if (r == 0) continue;
@@ -1385,17 +1139,8 @@ int ehyb_plan_upload(ehyb_plan* P)
     // windows of different sizes can live side by side in one process.
     const int lds = EHYB_LDS_MAX_DOUBLES * 8;
 #define LDS_ATTR(K) HIP_TRY(hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#define LDS_ATTR_S(T, S)                                   \
-    LDS_ATTR((ehyb_ell_kernel<T, false, false, false, S>)) \
-    LDS_ATTR((ehyb_ell_kernel<T, false, false, true, S>))  \
-    LDS_ATTR((ehyb_ell_kernel<T, true, false, false, S>))  \
-    LDS_ATTR((ehyb_ell_kernel<T, true, false, true, S>))
-#define LDS_ATTR_T(T)      \
-    LDS_ATTR_S(T, false)   \
-    LDS_ATTR_S(T, true)
-    LDS_ATTR_T(256)
-    LDS_ATTR_T(512)
-    LDS_ATTR_T(1024)
+    for (const EllKernel& e : ell_kernels())
+        if (!e.stamp) LDS_ATTR(e.fn)  // (a stamped launch opts in itself)
     LDS_ATTR((ehyb_pb_scale_kernel<512, true, false>))
     LDS_ATTR((ehyb_pb_scale_kernel<512, false, false>))
     LDS_ATTR((ehyb_pb_scale_kernel<1024, true, false>))
@@ -1406,9 +1151,6 @@ int ehyb_plan_upload(ehyb_plan* P)
     LDS_ATTR((ehyb_pb_scale_kernel<1024, false, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, false>))
-    if ((rc = spmm_set_lds_attr(lds)) != EHYB_OK) return rc;  // the k-vector window kernels (ehyb_spmm.hip)
-#undef LDS_ATTR_T
-#undef LDS_ATTR_S
 #undef LDS_ATTR
     P->uploaded = true;
     return EHYB_OK;

@@ -1,6 +1,13 @@
-// Device pieces of the window kernel shared by its one-vector form (ehyb_hip.hip) and its k-vector form
-// (ehyb_spmm.hip): the launch arguments, the item maps, the DPP lane shift and the value-pair load.
-// Internal: nothing here is part of the C-ABI.
+// The window kernel and the CSR-segment residual, device side, written once for K = 1..4 columns (ehyb_hip.hip instantiates
+// them: ehyb_ell_kernel / ehyb_er_kernel are K = 1, ehyb_ell_k_kernel / ehyb_er_k_kernel K = 2, 3, 4).  Column j of X and Y is
+// ldx / ldy doubles behind column 0; the value stream, the column words, the lane maps and the slab records are read ONCE for all K
+// columns, what grows with K is the x image in LDS and the x / y traffic.  The window is staged INTERLEAVED, win[c*K + j] =
+// X[col(c) + j*ldx] for own rows and halo alike, so that a lane fetches the K values of one column with one (K = 2) or two (K = 4)
+// LDS reads.  Per column the order of the sums is the one-vector order (inline residual, then even and odd pair halves, then
+// acc0 + acc1): column j of a plain-storage multiply is bit for bit the one-vector multiply of X[:, j].  At K = 1 every piece
+// reduces to the one-vector code (win_load<1> is win[idx], yacc = win + cnt + hn).  Only K = 1 has the round-robin walk (DYN =
+// false), the diagnostic stamps (STAMP, probe_n) and x . y on the side (xy_out); symmetric pairs at K = 4 step two value pairs
+// instead of four.  Internal: nothing here is part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,16 +86,426 @@ __device__ __forceinline__ double2 ell_load_pair(const double2* __restrict__ p)
     return *p;
 }
 
-// Host side of a window launch (ehyb_hip.hip), shared with the k-vector launches
-EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out = nullptr);
-// the walk direction and non-temporal share of a launch: walk >= 0 explicit, -1 the plan's own alternation (flips it)
-void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A);
-// ehyb_plan_upload: the k-vector window kernels (ehyb_spmm.hip) opt in to `lds` bytes of dynamic LDS
-int spmm_set_lds_attr(int lds);
+// The K values of window column `idx`: one ds_read_b128 for K = 2, two for K = 4 (16-byte aligned: 16 K bytes per column).
+template <int K>
+__device__ __forceinline__ void win_load(const double* __restrict__ win, uint32_t idx, double (&w)[K])
+{
+    if constexpr (K == 2) {
+        const double2 a = reinterpret_cast<const double2*>(win)[idx];
+        w[0] = a.x, w[1] = a.y;
+    } else if constexpr (K == 4) {
+        const double2 a = reinterpret_cast<const double2*>(win)[2 * idx], b = reinterpret_cast<const double2*>(win)[2 * idx + 1];
+        w[0] = a.x, w[1] = a.y, w[2] = b.x, w[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) w[j] = win[idx * K + j];
+    }
+}
 
+template <int K>
+__device__ __forceinline__ void win_store(double* __restrict__ win, int idx, const double (&w)[K])
+{
+    if constexpr (K == 2) {
+        reinterpret_cast<double2*>(win)[idx] = make_double2(w[0], w[1]);
+    } else if constexpr (K == 4) {
+        reinterpret_cast<double2*>(win)[2 * idx] = make_double2(w[0], w[1]);
+        reinterpret_cast<double2*>(win)[2 * idx + 1] = make_double2(w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) win[idx * K + j] = w[j];
+    }
+}
+
+// ------------------------------------------------------------------ window kernel
+// items[2b]   = {first segment, end segment, -, -}      items[2b+1] = residual bins of the item
+// segs[2g]    = {partition, first slab, end slab, halo count}
+// segs[2g+1]  = {first row, end row, contiguous window length, halo start}
+// DYN   waves take slabs from an LDS counter (the reference's per-block queue, kernel.cu:142,
+//       164-166; here re-armed per segment) -- the default; false: slabs dealt round-robin (A/B arm).
+//       A third arm -- global per-segment counters plus idle workgroups helping the busiest segment
+//       -- was measured and dropped: the device-scope atomic per slab cost 6 % by itself and the
+//       helping, at ~2 slabs per wave, evened the finish times without shortening the launch.
+// STAMP:   diagnostic instantiation (tools/stamps.py only): thread 0 records the 100 MHz wall clock
+//          at entry, after the first staging and at exit into a buffer of its own.
+// INLINE_ER: slabs also multiply the residual pairs stored behind their ELL pairs (tiny residuals).
+
+// One entry of a slab for K columns: gather x from the window; SYM: bit 15 of the column says "this entry also
+// stands for its mirror image": value * x[own row] goes to row `column`'s accumulator in LDS.
+// Lanes of a group (equal column lists: the unknowns of a node) send their mirror products to the
+// SAME accumulator.  Summed across the lanes first (`code`: this lane adds for itself and the next
+// 0/1/2 lanes, 3 = a lane before it adds for this one), a group of three costs one ds_add_f64
+// instead of three that the hardware has to serialise.
+template <int K, bool SYM>
+__device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double* __restrict__ win, double* yacc, const double (&xi)[K],
+                                          int code, double (&acc)[K])
+{
+    double w[K];
+    if (SYM) {
+        const uint32_t idx = col16 & 0x7fffu;
+        win_load<K>(win, idx, w);
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] = fma(v, w[j], acc[j]);
+        const bool mirror = (col16 & 0x8000u) != 0;
+        if constexpr (K == 1) {  // (written without the loop: even one trip of it costs the one-vector kernel a VGPR)
+            const double mine = mirror ? v * xi[0] : 0.0;
+            const double n1 = next_lane(mine), n2 = next_lane(n1);
+            const double sum = mine + ((code == 1 || code == 2) ? n1 : 0.0) + (code == 2 ? n2 : 0.0);
+            if (mirror && code != 3) unsafeAtomicAdd(&yacc[idx], sum);  // ds_add_f64
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const double mine = mirror ? v * xi[j] : 0.0;
+                const double n1 = next_lane(mine), n2 = next_lane(n1);
+                const double sum = mine + ((code == 1 || code == 2) ? n1 : 0.0) + (code == 2 ? n2 : 0.0);
+                if (mirror && code != 3) unsafeAtomicAdd(&yacc[idx * K + j], sum);
+            }
+        }
+    } else {
+        win_load<K>(win, col16, w);
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] = fma(v, w[j], acc[j]);
+    }
+}
+
+// One slab of 64 rows.  xy (K = 1, A.xy_out set): the lane's running sum of y[row] * x[row].
+template <int K, bool INLINE_ER, bool SYM, bool NT>
+__device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long long ldy, const double* __restrict__ win, double* yacc, int s,
+                                         int base, int pe, int lane, double& xy)
+{
+    // slab record {first value pair, first column word, first row, pairs << 16 | residual pairs << 8 | groups - 1}
+    const uint4 sm = A.slab_meta[s];
+    const int np = (int)(sm.w >> 16);
+    const int G = (int)(sm.w & 0x3fu) + 1;  // lanes with equal column lists share one word per pair
+    const double2* __restrict__ v = A.ell_val + (size_t)sm.x * 64 + lane;
+    // the lane's group (bits 0-5) and, with symmetric pairs, its part in the group's sum (bits 6-7)
+    const uint32_t lgb = A.lane_group[(size_t)s * 64 + lane];
+    const int code = SYM ? (int)(lgb >> 6) : 0;
+    const uint32_t* __restrict__ c = A.ell_col + sm.y + (SYM ? (lgb & 0x3fu) : lgb);
+    double acc0[K], acc1[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc0[j] = 0.0, acc1[j] = 0.0;
+    if (INLINE_ER) {
+        // Inline residual (tiny residuals only): `ner` more pairs behind the slab's ELL pairs, their
+        // columns global -- [pair][2][lane] 32-bit words behind the slab's shared column words.
+        // First, so that the loads are in flight while the ELL pairs stream; only the gather of x
+        // from global memory (L2) waits for them.  No second launch, no read-modify-write of y.
+        const int ner = (int)(sm.w >> 8) & 0xff;
+        const double2* __restrict__ ve = v + (size_t)np * 64;
+        const uint32_t* __restrict__ ce = A.ell_col + sm.y + (size_t)np * G + lane;
+        for (int q = 0; q < ner; ++q) {
+            const double2 vv = ve[q * 64];
+            const uint32_t ca = ce[q * 128], cb = ce[q * 128 + 64];
+            double xa[K], xb[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) xa[j] = A.x[ca + j * ldx], xb[j] = A.x[cb + j * ldx];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                acc0[j] = fma(vv.x, xa[j], acc0[j]);
+                acc1[j] = fma(vv.y, xb[j], acc1[j]);
+            }
+        }
+    }
+    // Plain: lane l works on row sm.z + l.  SYM: the rows of a partition sit in its slabs longest
+    // first (any order will do: sums go to the LDS accumulators by row), slab_lrow names the row.
+    const int row = (int)sm.z + lane;
+    const int lrow = SYM ? (int)A.slab_lrow[(size_t)s * 64 + lane] : row - base;  // place in the LDS image
+    const bool has_row = SYM ? lrow != 0xFFFF : row < pe;
+    double xi[K];
+    if (SYM && has_row)
+        win_load<K>(win, (uint32_t)lrow, xi);
+    else
+#pragma unroll
+        for (int j = 0; j < K; ++j) xi[j] = 0.0;
+    // bit 7 of the record: the slab's columns are stored relative to the lane's own row (bands and
+    // stencils: rows with equal offsets share their words); lanes without a row read column 0
+    const uint32_t radd = (!SYM && (sm.w & 0x80u)) ? (uint32_t)lrow : 0u;
+    const uint32_t cmask = (SYM || has_row) ? 0xffffu : 0u;
+#define ELL_COL_LO(c) (SYM ? ((c) & 0xffffu) : ((((c) & 0xffffu) + radd) & cmask))
+#define ELL_COL_HI(c) (SYM ? ((c) >> 16) : ((((c) >> 16) + radd) & cmask))
+    // Four value pairs per step; symmetric pairs at K = 4 take two, which keeps them within 128 VGPRs.
+    // (an 8-pair step for SYM, 128 VGPRs at 16 waves per CU, measured 1 % slower than four at K = 1)
+    constexpr int STEP = (SYM && K >= 4) ? 2 : 4;
+    int k = 0;
+    for (; k + STEP <= np; k += STEP) {
+        double2 vv[STEP];
+        uint32_t cc[STEP];
+#pragma unroll
+        for (int q = 0; q < STEP; ++q) vv[q] = ell_load_pair<NT>(v + (k + q) * 64);
+#pragma unroll
+        for (int q = 0; q < STEP; ++q) cc[q] = c[(k + q) * G];
+#pragma unroll
+        for (int q = 0; q < STEP; ++q) {
+            ell_entry<K, SYM>(vv[q].x, ELL_COL_LO(cc[q]), win, yacc, xi, code, acc0);
+            ell_entry<K, SYM>(vv[q].y, ELL_COL_HI(cc[q]), win, yacc, xi, code, acc1);
+        }
+    }
+    for (; k < np; ++k) {
+        const double2 v0 = ell_load_pair<NT>(v + k * 64);
+        const uint32_t c0 = c[k * G];
+        ell_entry<K, SYM>(v0.x, ELL_COL_LO(c0), win, yacc, xi, code, acc0);
+        ell_entry<K, SYM>(v0.y, ELL_COL_HI(c0), win, yacc, xi, code, acc1);
+    }
+#undef ELL_COL_LO
+#undef ELL_COL_HI
+    if (has_row) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (SYM)
+                unsafeAtomicAdd(&yacc[lrow * K + j], acc0[j] + acc1[j]);  // other lanes scatter into the same accumulator
+            else
+                A.y[row + j * ldy] = acc0[j] + acc1[j];
+        }
+        if (!SYM && K == 1 && A.xy_out != nullptr) xy = fma(acc0[0] + acc1[0], win[lrow], xy);  // (own rows are in the window)
+    }
+}
+
+// Stage the window of segment g and multiply its slabs.
+// SYM (symmetric pair storage): the segment is a whole partition; its rows' accumulators sit in LDS
+// right behind the K-wide x image, take the lanes' own sums and the scattered mirror products, and are
+// written to y in one coalesced sweep at the end.
+template <int THREADS, int K, bool DYN, bool INLINE_ER, bool SYM, bool STAMP>
+__device__ __forceinline__ void ell_segment(const EllArgs& A, long long ldx, long long ldy, double* __restrict__ win,
+                                            int* __restrict__ next_slab, int g, int lane, int wave, double& xy)
+{
+    constexpr int WAVES = THREADS / 64;
+    const int4 a = A.segs[2 * g], b = A.segs[2 * g + 1];
+    const int sb = a.y, se = a.z, hn = a.w;
+    const int ps = b.x, pe = b.y, wl = b.z, hb = b.w;
+    if (!SYM && wl == 0 && hn == 0) {
+        // a partition whose rows all went to the residual (its window did not pay, plan.cpp): nothing to
+        // stage, no slab to walk -- the residual launch adds to y, so y = 0 in one coalesced sweep
+        // (walking its empty slabs cost 22 us on R-MAT 2^22, 70 us on 2^24)
+        if (!A.windowless_zero) return;  // pb_assign: pass 2 of the panel residual is the only writer of these rows
+        const int r0 = max(ps, (int)A.slab_meta[sb].z), r1 = min(pe, r0 + (se - sb) * 64);
+        for (int i = r0 + (int)threadIdx.x; i < r1; i += THREADS)
+#pragma unroll
+            for (int j = 0; j < K; ++j) A.y[i + j * ldy] = 0.0;
+        return;
+    }
+    __syncthreads();  // every wave is done with the previous window and counter
+    // The LDS image starts at the even row at or below the partition start (the layout builder
+    // numbers window-local columns from there); win[0] may hold x[ps-1], unused.
+    const int base = ps & ~1, cnt = wl + (ps & 1);
+    double* yacc = win + K * (cnt + hn);
+    // (SYM: batching all of a thread's staging loads -- indices, then x, stores last -- measured no
+    // faster than these loops: 6.1 vs 6.5 us of staging; the halo gathers set the pace)
+    if (STAMP && A.probe_n > 0) {   // (diagnostic instantiation only: compiled out of the product's kernels)
+        const int n = A.probe_n, o1 = n / 3, o2 = 2 * (n / 3);
+        for (int i = threadIdx.x; i < cnt; i += THREADS) {
+            const int c = min(base + i, n - 1);
+            win[i] = A.x[c] + 1e-300 * (A.x[(c + o1) % n] + A.x[(c + o2) % n]);
+        }
+        for (int i = threadIdx.x; i < hn; i += THREADS) {
+            const int c = A.halo_cols[hb + i];
+            win[cnt + i] = A.x[c] + 1e-300 * (A.x[(c + o1) % n] + A.x[(c + o2) % n]);
+        }
+    } else if (STAMP && A.probe_n < 0) {   // (diagnostic: no halo gather at all -- results wrong, the launch span is what hiding the gather could reach at best)
+        for (int i = threadIdx.x; i < cnt; i += THREADS) win[i] = A.x[base + i];
+        for (int i = threadIdx.x; i < hn; i += THREADS) win[cnt + i] = 1.0;
+    } else {
+        for (int i = threadIdx.x; i < cnt; i += THREADS) {
+            double w[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) w[j] = A.x[base + i + j * ldx];
+            win_store<K>(win, i, w);
+        }
+        for (int i = threadIdx.x; i < hn; i += THREADS) {
+            const int col = A.halo_cols[hb + i];
+            double w[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) w[j] = A.x[col + j * ldx];
+            win_store<K>(win, cnt + i, w);
+        }
+    }
+    if (SYM)
+        for (int i = threadIdx.x; i < K * cnt; i += THREADS) yacc[i] = 0.0;
+    if (DYN && threadIdx.x == 0) *next_slab = sb + WAVES;  // slabs sb..sb+WAVES-1 are pre-assigned
+    __syncthreads();
+    // diagnostic launches only (tools/stamps.py): when the first window of the item was staged
+    // (a run-time test in every one-vector kernel, absent from the k-vector ones, whose launches never stamp)
+    if (K == 1 && A.stamps != nullptr && threadIdx.x == 0 &&
+        g == A.items[2 * item_of_block(A.item_map, A.xcd_map)].x)
+        A.stamps[4 * blockIdx.x + 1] = wall_clock64();
+    int s = sb + wave;  // (logical position in the segment's walk; the slab it stands for depends on the direction)
+    const int nt_end = sb + (int)(((long long)(se - sb) * A.nt_slabs + 1023) >> 10);   // walk positions below it: value stream past the caches
+    while (s < se) {
+        if (s < nt_end)
+            ell_slab<K, INLINE_ER, SYM, true>(A, ldx, ldy, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
+        else
+            ell_slab<K, INLINE_ER, SYM, false>(A, ldx, ldy, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
+        if (DYN) {
+            int nx = 0;
+            if (lane == 0) nx = atomicAdd(next_slab, 1);
+            s = __builtin_amdgcn_readfirstlane(nx);
+        } else {
+            s += WAVES;
+        }
+    }
+    if (SYM) {
+        __syncthreads();  // all sums and scatters of the partition are in
+        // (Folding the pairs that straddle two partitions as well -- 13 % fewer bytes on the bench
+        // matrix -- would need y zeroed first and this write-out plus one add per halo column done
+        // with global atomics: that alone was measured at +12.5 us per launch, more than the bytes save.)
+        if (K == 1 && A.xy_out != nullptr) {
+            for (int i = threadIdx.x + (ps & 1); i < cnt; i += THREADS) {
+                A.y[base + i] = yacc[i];
+                xy = fma(yacc[i], win[i], xy);
+            }
+        } else {
+            for (int i = threadIdx.x + (ps & 1); i < cnt; i += THREADS)
+#pragma unroll
+                for (int j = 0; j < K; ++j) A.y[base + i + j * ldy] = yacc[i * K + j];
+        }
+    }
+}
+
+// The body of the window kernel: one workgroup per work item, its segments one after the other.  The LDS slab counter
+// sits right behind the K window images.
+template <int THREADS, int K, bool DYN, bool STAMP, bool INLINE_ER, bool SYM>
+__device__ __forceinline__ void ell_items(const EllArgs& A, long long ldx, long long ldy)
+{
+    static_assert(K == 1 || (DYN && !STAMP), "the k-vector window kernel is built with the LDS counter only, without stamps");
+    extern __shared__ __attribute__((aligned(16))) double win[];
+    int* next_slab = reinterpret_cast<int*>(win + K * A.win_cap);
+    if (STAMP && threadIdx.x == 0) A.stamps[4 * blockIdx.x + 0] = wall_clock64();
+    const int4 it = A.items[2 * item_of_block(A.item_map, A.xcd_map, A.reverse_items)];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double xy = 0.0;
+    for (int sg = it.x; sg < it.y; ++sg) ell_segment<THREADS, K, DYN, INLINE_ER, SYM, STAMP>(A, ldx, ldy, win, next_slab, sg, lane, wave, xy);
+    if (K == 1 && A.xy_out != nullptr) {  // (wave-uniform: a kernel argument)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) xy += __shfl_xor(xy, off, 64);
+        __syncthreads();  // every wave is done with the last window
+        if (lane == 0) win[wave] = xy;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int w = 0; w < THREADS / 64; ++w) t += win[w];  // fixed order
+            A.xy_out[blockIdx.x] = t;
+        }
+    }
+    if (STAMP) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            A.stamps[4 * blockIdx.x + 2] = wall_clock64();
+            unsigned xcc;
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            A.stamps[4 * blockIdx.x + 3] = xcc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ residual segments
+// Residual segments [lo, hi) multiplied by one workgroup: G lanes per segment (64 / 16 / 4 by
+// segment length, longest first), strided coalesced (col,val) reads, x gathered from global
+// memory K times, shuffle reduction per column, then y[row] += sum -- plain for rows with one segment (rows are
+// unique, kernel.cu:69-77), one fp64 atomic per segment and column for split rows (the working form of
+// kernel.cu:43-67).  Called from ehyb_er_kernel / ehyb_er_k_kernel, which run behind the window launch.
+// ASSIGN (direct shape, small matrices): y[row] = sum -- every row has exactly one segment.
+// Most residual rows are short (R-MAT 2^22: 22 entries on average), so a lane has one to four entries
+// and the time goes into the CHAIN of dependent loads, not into bandwidth: segment bounds -> (column,
+// value) -> x[column] -> y.  Everything that does not depend on the products is therefore requested up
+// front (row number and the old y with the bounds), and a lane's column/value loads are issued four at
+// a time before the first gather of x (measured on R-MAT 2^22: DESIGN.md 3.2).
+template <int G, int THREADS, bool ASSIGN, int K>
+__device__ __forceinline__ void er_bin(int lo, int hi, const int64_t* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                       const int* __restrict__ col, const double* __restrict__ val, const double* __restrict__ x, long long ldx,
+                                       double* __restrict__ y, long long ldy)
+{
+    constexpr int SEGS = THREADS / G;
+    const int sub = threadIdx.x % G;
+    for (int base = lo; base < hi; base += SEGS) {  // uniform trip count: every lane reaches the shuffles
+        const int seg = base + threadIdx.x / G;
+        double acc0[K], acc1[K], y_old[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc0[j] = 0.0, acc1[j] = 0.0, y_old[j] = 0.0;
+        int r = 0;
+        if (seg < hi) {
+            const int64_t b = seg_ptr[seg], e = seg_ptr[seg + 1];
+            r = seg_row[seg];
+            if (!ASSIGN && sub == 0 && r >= 0)  // in flight while the products are formed
+#pragma unroll
+                for (int j = 0; j < K; ++j) y_old[j] = y[r + j * ldy];
+            int64_t k = b + sub;
+            for (; k + 3 * G < e; k += 4 * G) {
+                const int c0 = col[k], c1 = col[k + G], c2 = col[k + 2 * G], c3 = col[k + 3 * G];
+                const double v0 = val[k], v1 = val[k + G], v2 = val[k + 2 * G], v3 = val[k + 3 * G];
+                double x0[K], x1[K], x2[K], x3[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) x0[j] = x[c0 + j * ldx], x1[j] = x[c1 + j * ldx], x2[j] = x[c2 + j * ldx], x3[j] = x[c3 + j * ldx];
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    acc0[j] = fma(v0, x0[j], acc0[j]);
+                    acc1[j] = fma(v1, x1[j], acc1[j]);
+                    acc0[j] = fma(v2, x2[j], acc0[j]);
+                    acc1[j] = fma(v3, x3[j], acc1[j]);
+                }
+            }
+            // up to three more, again all requested before the first use
+            const bool h0 = k < e, h1 = k + G < e, h2 = k + 2 * G < e;
+            const int c0 = h0 ? col[k] : 0, c1 = h1 ? col[k + G] : 0, c2 = h2 ? col[k + 2 * G] : 0;
+            const double v0 = h0 ? val[k] : 0.0, v1 = h1 ? val[k + G] : 0.0, v2 = h2 ? val[k + 2 * G] : 0.0;
+            double x0[K], x1[K], x2[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                x0[j] = h0 ? x[c0 + j * ldx] : 0.0;
+                x1[j] = h1 ? x[c1 + j * ldx] : 0.0;
+                x2[j] = h2 ? x[c2 + j * ldx] : 0.0;
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                acc0[j] = fma(v0, x0[j], acc0[j]);
+                acc1[j] = fma(v1, x1[j], acc1[j]);
+                acc0[j] = fma(v2, x2[j], acc0[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            double acc = acc0[j] + acc1[j];
+#pragma unroll
+            for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, G);
+            if (sub == 0 && seg < hi) {
+                if (ASSIGN)
+                    y[r + j * ldy] = acc;
+                else if (r < 0)
+                    unsafeAtomicAdd(&y[(r & 0x7fffffff) + j * ldy], acc);
+                else
+                    y[r + j * ldy] = y_old[j] + acc;
+            }
+        }
+    }
+}
+
+// One workgroup per descriptor {seg_lo, seg_hi, lanes per segment}: a single pass of same-bin segments.
+template <int THREADS, bool ASSIGN, int K>
+__device__ __forceinline__ void er_blocks(const int4* __restrict__ blocks, const int64_t* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                          const int* __restrict__ col, const double* __restrict__ val, const double* __restrict__ x, long long ldx,
+                                          double* __restrict__ y, long long ldy)
+{
+    const int4 b = blocks[blockIdx.x];  // (the XCD map of the window kernel was tried here: no difference on R-MAT)
+    if (b.z == 64)
+        er_bin<64, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+    else if (b.z == 16)
+        er_bin<16, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+    else
+        er_bin<4, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+}
+
+// ------------------------------------------------------------------ host side (ehyb_hip.hip)
 namespace ehyb {
+constexpr int kSpmmMaxK = 4;  // widest window / residual kernel built
+
 // Doubles of the LDS x image per vector (the window, with symmetric pair storage the y accumulators behind it); the kernel's
 // slab counter sits right behind the image(s).
 inline int ell_win_cap(const HostLayout& H) { return (H.lds_doubles + 1) / 2 * 2; }
+// Dynamic LDS of a window launch for k columns: k images and the slab counter
+inline size_t ell_lds_bytes(const HostLayout& H, int k) { return (size_t)k * ell_win_cap(H) * 8 + 16; }
 
+// The window launch of a multiply for k = 1..kSpmmMaxK columns ldx / ldy doubles apart.  walk: >= 0 explicit, -1 the plan's own
+// alternation.  k = 1 only: stamps (diagnostic; no walk of its own) and xy_out (x . y on the side).
+int launch_window(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, bool inl, int walk,
+                  unsigned long long* stamps = nullptr, double* xy_out = nullptr);
+// The CSR-segment residual launch for k columns (none where the plan has no CSR segments)
+int launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st);
 }  // namespace ehyb

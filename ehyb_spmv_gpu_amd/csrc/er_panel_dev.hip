@@ -33,17 +33,9 @@
 #include <vector>
 
 #include "ehyb_internal.h"
+#include "hip_try.h"
 
 using namespace ehyb;
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            ::ehyb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return _e == hipErrorNoDevice ? EHYB_ERR_NO_DEVICE : EHYB_ERR_HIP;                \
-        }                                                                                     \
-    } while (0)
 
 namespace {
 
