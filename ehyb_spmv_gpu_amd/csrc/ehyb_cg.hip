@@ -296,6 +296,381 @@ extern "C" int ehyb_pcg(ehyb_plan* P, const double* dinv, const double* b, doubl
     return EHYB_OK;
 }
 
+// ------------------------------------------------------------------ k right-hand sides, one multiply (ehyb_pcg_multi)
+// k independent solves on the same matrix that share every multiply: per iteration one ehyb_spmm of the k directions and the three
+// vector kernels K columns wide (K <= 4 per launch, ceil(k / 4) launches each).  Column j keeps its own alpha, beta and stopping
+// test and its own set of partial slots (s + j * A_COUNT * kMaxGrid); every kernel walks the indices with the grid and the
+// four-stride unroll of the one-vector kernels and does the same arithmetic in the same order per column, so column j is
+// ehyb_pcg(b_j) wherever the multiply is (plain storage).  One thread serves the K columns at one index: the inv_diag load is
+// shared and K times the loads are in flight.  A column whose active flag is 0 (converged or broken down) is skipped: its x, r,
+// p and partials stay as they are.
+namespace {
+
+constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
+
+// the sums of block_sum for N values at once: per value the same shuffle tree and the same order over the waves
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&v)[N])
+{
+    __shared__ double part[N][kThreads / 64];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) part[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) s += part[c][w];
+        v[c] = s;
+    }
+}
+
+__device__ __forceinline__ double partials_of(const double* __restrict__ part)
+{
+    double v = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
+    return v;
+}
+
+template <typename T>
+__device__ __forceinline__ T* slot(T* s, int col, int which)
+{
+    return s + ((size_t)col * A_COUNT + which) * kMaxGrid;
+}
+
+// columns c0 .. c0 + K - 1: P, Q, R with leading dimension n, X with ldx
+template <int K>
+__global__ __launch_bounds__(kThreads) void cg_multi_dot_kernel(int n, const double* __restrict__ P, const double* __restrict__ Q,
+                                                                double* __restrict__ s, const int* __restrict__ active, int c0)
+{
+    bool on[K];
+    double acc[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = active[c0 + c] != 0;
+        acc[c] = 0.0;
+    }
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            const size_t o = (size_t)(c0 + c) * n + i;
+            if (on[c]) acc[c] = fma(P[o], Q[o], acc[c]);
+        }
+    }
+    block_sum_n(acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) slot(s, c0 + c, A_PQ)[blockIdx.x] = acc[c];
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const double* __restrict__ P, const double* __restrict__ Q,
+                                                                   const double* __restrict__ dinv, double* __restrict__ X, long long ldx,
+                                                                   double* __restrict__ R, double* __restrict__ s,
+                                                                   const int* __restrict__ active, int c0, int cur)
+{
+    bool on[K];
+    double sums[2 * K], alpha[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = active[c0 + c] != 0;
+        sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
+        sums[K + c] = partials_of(slot(s, c0 + c, A_PQ));
+    }
+    block_sum_n(sums);
+    double rz[K], rr[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        alpha[c] = sums[c] / sums[K + c];
+        rz[c] = rr[c] = 0.0;
+    }
+    const double* p[K];
+    const double* q[K];
+    double* x[K];
+    double* r[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        p[c] = P + (size_t)(c0 + c) * n;
+        q[c] = Q + (size_t)(c0 + c) * n;
+        r[c] = R + (size_t)(c0 + c) * n;
+        x[c] = X + (size_t)(c0 + c) * ldx;
+    }
+    // as cg_update_kernel: four grid strides per trip, q and x past the caches; the loads of every column first
+    const int stride = (int)gridDim.x * kThreads;
+    int i = blockIdx.x * kThreads + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+        double pv[K][4], qv[K][4], xv[K][4], rv[K][4], dv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                pv[c][u] = p[c][i + u * stride];
+                qv[c][u] = __builtin_nontemporal_load(&q[c][i + u * stride]);
+                xv[c][u] = __builtin_nontemporal_load(&x[c][i + u * stride]);
+                rv[c][u] = r[c][i + u * stride];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                __builtin_nontemporal_store(fma(alpha[c], pv[c][u], xv[c][u]), &x[c][i + u * stride]);
+                const double ri = fma(-alpha[c], qv[c][u], rv[c][u]);
+                r[c][i + u * stride] = ri;
+                rz[c] = fma(ri, dinv ? ri * dv[u] : ri, rz[c]);
+                rr[c] = fma(ri, ri, rr[c]);
+            }
+        }
+    }
+    for (; i < n; i += stride) {
+        const double di = dinv ? dinv[i] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+            x[c][i] = fma(alpha[c], p[c][i], x[c][i]);
+            const double ri = fma(-alpha[c], q[c][i], r[c][i]);
+            r[c][i] = ri;
+            rz[c] = fma(ri, dinv ? ri * di : ri, rz[c]);
+            rr[c] = fma(ri, ri, rr[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        sums[c] = rz[c];
+        sums[K + c] = rr[c];
+    }
+    block_sum_n(sums);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+            slot(s, c0 + c, A_RZ0 + 2 * (cur ^ 1))[blockIdx.x] = sums[c];
+            slot(s, c0 + c, A_RR)[blockIdx.x] = sums[K + c];
+        }
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, const double* __restrict__ R, const double* __restrict__ dinv,
+                                                                      double* __restrict__ P, const double* __restrict__ s,
+                                                                      const int* __restrict__ active, int c0, int cur)
+{
+    bool on[K];
+    double sums[2 * K], beta[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = active[c0 + c] != 0;
+        sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * (cur ^ 1)));
+        sums[K + c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
+    }
+    block_sum_n(sums);
+    const double* r[K];
+    double* p[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        beta[c] = sums[c] / sums[K + c];
+        r[c] = R + (size_t)(c0 + c) * n;
+        p[c] = P + (size_t)(c0 + c) * n;
+    }
+    const int stride = (int)gridDim.x * kThreads;
+    int i = blockIdx.x * kThreads + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+        double pv[K][4], rv[K][4], dv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                pv[c][u] = p[c][i + u * stride];
+                rv[c][u] = r[c][i + u * stride];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) p[c][i + u * stride] = fma(beta[c], pv[c][u], dinv ? rv[c][u] * dv[u] : rv[c][u]);
+        }
+    }
+    for (; i < n; i += stride) {
+        const double di = dinv ? dinv[i] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) p[c][i] = fma(beta[c], p[c][i], dinv ? r[c][i] * di : r[c][i]);
+    }
+}
+
+// the three kernels of one iteration for columns c0 .. c0 + w - 1
+template <int K>
+void launch_multi_vector_kernels(int grid, hipStream_t st, int n, double* P, const double* Q, const double* dinv, double* X,
+                                 long long ldx, double* R, double* s, const int* active, int c0, int cur)
+{
+    hipLaunchKernelGGL(cg_multi_dot_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, s, active, c0);
+    hipLaunchKernelGGL(cg_multi_update_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, dinv, X, ldx, R, s, active, c0, cur);
+    hipLaunchKernelGGL(cg_multi_direction_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, R, dinv, P, s, active, c0, cur);
+}
+
+struct MultiWorkspace : Workspace {
+    int* active = nullptr;
+    ~MultiWorkspace()
+    {
+        if (active) (void)hipFree(active);
+    }
+};
+
+}  // namespace
+
+extern "C" int ehyb_cg_multi(ehyb_plan* P, const double* B, int64_t ldb, double* X, int64_t ldx, int k, int max_iter, double rtol,
+                             int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    return ehyb_pcg_multi(P, nullptr, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done, rel_residual);
+}
+
+extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                              int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    clear_error();
+    if (!P || !B || !X) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: null argument");
+    if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: k = %d right-hand sides (at least 1)", k);
+    if (max_iter < 0 || !(rtol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: max_iter %d, rtol %g", max_iter, rtol);
+    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: needs a plan over all rows");
+    const int n = P->host.n_cols;
+    if (ldb < n || ldx < n)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, n);
+    if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_pcg_multi: plan not uploaded (no CPU fallback exists)");
+    hipStream_t st = (hipStream_t)stream;
+    if (check_every <= 0) check_every = 10;
+    check_every += check_every & 1;
+    MultiWorkspace W;
+    if (!st) {
+        HIP_TRY(hipStreamCreate(&W.own));
+        st = W.own;
+        stream = (void*)W.own;
+    }
+    const size_t nk = (size_t)n * k, set = (size_t)A_COUNT * kMaxGrid;
+    HIP_TRY(hipMalloc((void**)&W.r, std::max<size_t>(1, nk) * 8));
+    HIP_TRY(hipMalloc((void**)&W.p, std::max<size_t>(1, nk) * 8));
+    HIP_TRY(hipMalloc((void**)&W.q, std::max<size_t>(1, nk) * 8));
+    HIP_TRY(hipMalloc((void**)&W.s, (size_t)k * set * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&W.active, (size_t)k * sizeof(int)));
+    double *R = W.r, *Pd = W.p, *Q = W.q, *s = W.s;
+    const int grid = std::max(1, std::min((n + kThreads - 1) / kThreads, kMaxGrid / 2));  // the one-vector solve's grid
+
+    int rc = ehyb_spmm(P, X, ldx, Q, n, k, stream, EHYB_WALK_AUTO);  // Q = A X0
+    if (rc != EHYB_OK) return rc;
+    for (int j = 0; j < k; ++j)
+        hipLaunchKernelGGL(cg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, B + (size_t)j * ldb, Q + (size_t)j * n, dinv,
+                           R + (size_t)j * n, Pd + (size_t)j * n, s + (size_t)j * set);
+    std::vector<double> h((size_t)k * set);
+    auto read_scalar = [&](int j, int which) {  // fixed order, like the device
+        double t = 0.0;
+        for (int i = 0; i < grid; ++i) t += h[(size_t)j * set + (size_t)which * kMaxGrid + i];
+        return t;
+    };
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> bb(k), rs(k);
+    std::vector<int> live(k), iters(k, 0);
+    int n_live = 0;
+    for (int j = 0; j < k; ++j) {
+        const double bb0 = read_scalar(j, A_BB);
+        bb[j] = bb0 > 0 ? bb0 : 1.0;
+        rs[j] = read_scalar(j, A_RR);
+        live[j] = std::sqrt(rs[j] / bb[j]) > rtol;  // (NaN: frozen at once, reported as a breakdown)
+        n_live += live[j];
+    }
+    HIP_TRY(hipMemcpyAsync(W.active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
+
+    // column groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
+    const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
+    auto enqueue_iteration = [&](int cur, int walk) -> int {
+        const int e = ehyb_spmm(P, Pd, n, Q, n, k, stream, walk);  // Q = A P, frozen columns included (their q is not read)
+        if (e != EHYB_OK) return e;
+        for (int g = 0, c0 = 0; g < groups; ++g) {
+            const int w = k / groups + (g < k % groups ? 1 : 0);
+            switch (w) {
+            case 1: launch_multi_vector_kernels<1>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
+            case 2: launch_multi_vector_kernels<2>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
+            case 3: launch_multi_vector_kernels<3>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
+            default: launch_multi_vector_kernels<4>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
+            }
+            c0 += w;
+        }
+        return EHYB_OK;
+    };
+    // as ehyb_pcg: an even and an odd iteration captured once and replayed.  The captured multiplies state their walks (first to
+    // last, then last to first), since a captured launch keeps the direction it was captured with.
+    if (P->cfg.graphs != 2 && max_iter >= 2 && n_live > 0 &&
+        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        int erc = enqueue_iteration(0, EHYB_WALK_FIRST_TO_LAST);
+        if (erc == EHYB_OK) erc = enqueue_iteration(1, EHYB_WALK_LAST_TO_FIRST);
+        const hipError_t eend = hipStreamEndCapture(st, &W.graph);
+        if (erc != EHYB_OK || eend != hipSuccess || hipGraphInstantiate(&W.exec, W.graph, nullptr, nullptr, 0) != hipSuccess)
+            W.exec = nullptr;
+        (void)hipGetLastError();
+    }
+    int it = 0;
+    bool broke = false;
+    while (it < max_iter && n_live > 0) {
+        const int burst = std::min(check_every, max_iter - it);
+        int b = 0;
+        for (; b + 2 <= burst; b += 2) {
+            if (W.exec) {
+                HIP_TRY(hipGraphLaunch(W.exec, st));
+            } else {
+                if ((rc = enqueue_iteration(0, EHYB_WALK_AUTO)) != EHYB_OK || (rc = enqueue_iteration(1, EHYB_WALK_AUTO)) != EHYB_OK)
+                    return rc;
+            }
+        }
+        if (b < burst && (rc = enqueue_iteration(0, EHYB_WALK_AUTO)) != EHYB_OK) return rc;
+        it += burst;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        bool changed = false;
+        for (int j = 0; j < k; ++j) {
+            if (!live[j]) continue;
+            rs[j] = read_scalar(j, A_RR);
+            const double rz = read_scalar(j, A_RZ0 + 2 * (burst & 1));
+            if (!(rs[j] == rs[j]) || !(rz == rz)) rs[j] = NAN;  // breakdown of this column: frozen, the others go on
+            if (!(std::sqrt(rs[j] / bb[j]) > rtol)) {
+                live[j] = 0;
+                iters[j] = it;
+                --n_live;
+                changed = true;
+            }
+        }
+        if (changed && n_live > 0)
+            HIP_TRY(hipMemcpyAsync(W.active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    for (int j = 0; j < k; ++j) {
+        if (live[j]) iters[j] = it;
+        if (iters_done) iters_done[j] = iters[j];
+        if (rel_residual) rel_residual[j] = std::sqrt(rs[j] / bb[j]);
+        broke = broke || !(rs[j] == rs[j]);
+    }
+    if (broke) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: breakdown in a column (is the matrix symmetric positive definite?)");
+    return EHYB_OK;
+}
+
 // ------------------------------------------------------------------ building blocks for a multi-GPU caller
 // The same four vector kernels for a caller that owns the loop (ehyb_spmv_gpu_amd/dist.py HaloCG: one
 // process per GPU, the multiply through the halo exchange): every rank runs them on its rows with the

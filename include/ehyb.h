@@ -710,6 +710,27 @@ int ehyb_pcg(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, d
              double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
 
 /*
+ * k INDEPENDENT solves on the plan's matrix that share every multiply: column j of X is what ehyb_pcg(b_j) makes of it (not a
+ * block CG: every column keeps its own alpha, beta and stopping test).  Per iteration one ehyb_spmm of the k directions
+ * (ceil(k / ehyb_spmm_max_k) passes over the matrix) and three vector kernels up to four columns wide.  B, X: device pointers,
+ * column j at B + j*ldb and X + j*ldx (column-major, as ehyb_spmm), ldb, ldx >= n; only rows [0, n) of each column are read or
+ * written.  X holds the initial guesses on entry and the solutions on return.  inv_diag_dev: one Jacobi preconditioner for
+ * every column, as ehyb_pcg (NULL = none).  iters_done, rel_residual: host arrays of k entries, may be NULL.
+ * Stopping, per column: at each check point (every `check_every` iterations, as ehyb_pcg) a column with ||r_j|| <= rtol ||b_j||
+ * is frozen -- its x, r and p stop changing -- and iters_done[j] is that check point; the call returns when every column is
+ * frozen or after max_iter iterations.  A column whose r.r or r.z turns NaN is frozen with rel_residual[j] = NaN, the others go
+ * on, and the call returns EHYB_ERR_ARG (breakdown) at the end with every output written.  With plain storage column j equals
+ * ehyb_pcg on b_j bit for bit, but for rows the residual splits into several segments (ehyb_spmm).  Iterations are replayed
+ * from a hipGraph as in ehyb_pcg (cfg.graphs = 2: plain launches); cfg.cg_fused_dot is ignored: p . (A p) always comes from a
+ * dot kernel of its own.  Needs a plan over all rows.  EHYB_ERR_ARG for a null pointer, k < 1, ldb or ldx < n, max_iter < 0, a
+ * negative or NaN rtol or a plan not over all rows; EHYB_ERR_STATE on a plan never uploaded -- all before any device work.
+ */
+int ehyb_cg_multi(ehyb_plan* plan, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k, int max_iter, double rtol,
+                  int check_every, void* stream, int* iters_done, double* rel_residual);
+int ehyb_pcg_multi(ehyb_plan* plan, const double* inv_diag_dev, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k,
+                   int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
