@@ -184,6 +184,7 @@ SIGNATURES = {
     "ehyb_measure_read_bw": (C.c_int, [C.c_size_t, C.c_int, _dp]),
     "ehyb_cg": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cg_multi": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cg_layout": (C.c_int, [_ip, _ip, _ip, _ip, _ip, _ip]),

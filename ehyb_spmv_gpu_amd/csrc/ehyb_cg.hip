@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ehyb_internal.h"
+#include "vec_reduce.h"
 
 using namespace ehyb;
 
@@ -41,44 +42,10 @@ using namespace ehyb;
 
 namespace {
 
-#ifndef EHYB_CG_THREADS
-#define EHYB_CG_THREADS 256
-#endif
-constexpr int kThreads = EHYB_CG_THREADS;
-constexpr int kMaxGrid = 1024;  // partial sums per dot product
-
 // partial arrays, kMaxGrid doubles each
 // (r.r sits between the two r.z slots, so that the pair an iteration writes -- its new r.z and r.r -- is one
 // contiguous range for a multi-GPU caller's all-reduce: slot of r.z number c = A_RZ0 + 2 c)
 enum { A_BB = 0, A_PQ = 1, A_RZ0 = 2, A_RR = 3, A_RZ1 = 4, A_COUNT = 5 };
-
-// sum over the workgroup, returned to every thread; fixed order
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double part[kThreads / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();  // a previous call's readers are done with part[]
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-    return s;
-}
-
-__device__ __forceinline__ double sum_partials(const double* __restrict__ part)
-{
-    double v = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
-    return block_sum(v);
-}
-
-__device__ __forceinline__ void put_partial(double v, double* __restrict__ part)
-{
-    const double s = block_sum(v);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
 
 // r = b - q (q = A x0), z = dinv .* r (or r), p = z; partials of r.z, r.r, b.b
 __global__ __launch_bounds__(kThreads) void cg_init_kernel(int n, const double* __restrict__ b,
@@ -307,38 +274,6 @@ extern "C" int ehyb_pcg(ehyb_plan* P, const double* dinv, const double* b, doubl
 namespace {
 
 constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
-
-// the sums of block_sum for N values at once: per value the same shuffle tree and the same order over the waves
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N])
-{
-    __shared__ double part[N][kThreads / 64];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) part[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[c][w];
-        v[c] = s;
-    }
-}
-
-__device__ __forceinline__ double partials_of(const double* __restrict__ part)
-{
-    double v = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
-    return v;
-}
 
 template <typename T>
 __device__ __forceinline__ T* slot(T* s, int col, int which)

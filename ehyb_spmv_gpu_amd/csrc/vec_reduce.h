@@ -1,0 +1,77 @@
+// Fixed-order reductions of the device-resident solvers (ehyb_cg.hip, ehyb_bicgstab.hip).  A vector kernel writes one
+// partial sum per workgroup (put_partial); the kernel that needs the scalar adds the partials of a slot up again
+// (sum_partials) -- every workgroup for itself, in the same order, so every workgroup gets the same bits and a solve is
+// reproducible run to run.  No atomics.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+namespace {
+
+#ifndef EHYB_CG_THREADS
+#define EHYB_CG_THREADS 256
+#endif
+constexpr int kThreads = EHYB_CG_THREADS;
+constexpr int kMaxGrid = 1024;  // partial sums per dot product
+
+// sum over the workgroup, returned to every thread; fixed order
+__device__ __forceinline__ double block_sum(double v)
+{
+    __shared__ double part[kThreads / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();  // a previous call's readers are done with part[]
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) s += part[w];
+    return s;
+}
+
+__device__ __forceinline__ double sum_partials(const double* __restrict__ part)
+{
+    double v = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
+    return block_sum(v);
+}
+
+__device__ __forceinline__ void put_partial(double v, double* __restrict__ part)
+{
+    const double s = block_sum(v);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// the sums of block_sum for N values at once: per value the same shuffle tree and the same order over the waves
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&v)[N])
+{
+    __shared__ double part[N][kThreads / 64];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) part[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) s += part[c][w];
+        v[c] = s;
+    }
+}
+
+__device__ __forceinline__ double partials_of(const double* __restrict__ part)
+{
+    double v = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
+    return v;
+}
+
+}  // namespace

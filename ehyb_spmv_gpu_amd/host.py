@@ -484,6 +484,21 @@ class Plan:
             raise EhybError(rc, "ehyb_pcg_multi")
         return dx.download().reshape(k, n), it, rel
 
+    def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
+        b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative residual).  A breakdown raises EhybError,
+        unless allow_breakdown: then x is the last good iterate and the counts are those of the device."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        db = DeviceBuffer(self.n).upload(b)
+        dx = DeviceBuffer(self.n).upload(np.zeros(self.n) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64))
+        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
+        it, rel = C.c_int(0), C.c_double(0)
+        rc = self.lib.ehyb_bicgstab(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), C.c_void_p(dx.ptr), max_iter,
+                                    rtol, check_every, C.c_void_p(stream), C.byref(it), C.byref(rel))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, "ehyb_bicgstab")
+        return dx.download(), it.value, rel.value
+
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)

@@ -710,6 +710,31 @@ int ehyb_pcg(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, d
              double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
 
 /*
+ * BiCGSTAB for a general (unsymmetric) A x = b on the plan's matrix, entirely on the device, right-preconditioned with
+ * M = diag(A): inv_diag_dev[i] = 1 / a_ii in the permuted numbering (NULL = no preconditioner).  Arguments, stream and
+ * outputs as ehyb_pcg: x_dev holds the initial guess on entry and the solution on return, stream NULL = a private stream,
+ * check_every <= 0 = 10 (odd values rounded up to even), outputs may be NULL, the plan must cover all rows.
+ * Recurrences (shadow residual rh = r0 = b - A x0, p^ = M^-1 r0; only p^ = M^-1 p and s^ = M^-1 s are stored):
+ *   v = A p^;  alpha = rho / (rh.v);  s = r - alpha v;  s^ = M^-1 s;  t = A s^;  omega = (t.s) / (t.t);
+ *   x += alpha p^ + omega s^;  r = s - omega t;  rho_new = rh.r;  beta = (rho_new / rho) (alpha / omega);
+ *   p^ = M^-1 r + beta (p^ - omega M^-1 v)
+ * Two multiplies (walking first to last, then last to first) and five vector kernels per iteration; an even and an odd
+ * iteration are replayed from one hipGraph (cfg.graphs = 2: plain launches; cfg.cg_fused_dot is ignored).
+ * Stopping and breakdown are decided on the device, after every iteration: converged when r.r <= rtol^2 b.b, or after
+ * the half step when s.s <= rtol^2 b.b (then x += alpha p^, r = s); the convergence test comes first.  A zero or non-finite
+ * rho, rh.v, t.t or omega as a divisor, or a non-finite rho_new, is a breakdown: the kernel that meets it changes nothing and
+ * every later one returns at once.  x is the last iterate whose update had finite scalars, iters_done the exact number of
+ * such updates (the device's counter), rel_residual = sqrt(r.r / b.b) of that iterate (b.b = 0: 1 in its place); the host
+ * only looks every check_every iterations, to stop launching.  With plain storage x, iters_done and rel_residual are
+ * therefore the same bits for every check_every, for graphs and plain launches, and from run to run.  A breakdown returns
+ * EHYB_ERR_ARG ("breakdown" in ehyb_last_error) after every output is written; so does a NaN in b, x0 or the initial residual,
+ * with x unchanged.  EHYB_ERR_ARG for a null plan, b or x, max_iter < 0, a negative or NaN rtol or a plan not over all rows;
+ * EHYB_ERR_STATE on a plan never uploaded -- all before any device work.
+ */
+int ehyb_bicgstab(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, double* x_dev, int max_iter, double rtol,
+                  int check_every, void* stream, int* iters_done, double* rel_residual);
+
+/*
  * k INDEPENDENT solves on the plan's matrix that share every multiply: column j of X is what ehyb_pcg(b_j) makes of it (not a
  * block CG: every column keeps its own alpha, beta and stopping test).  Per iteration one ehyb_spmm of the k directions
  * (ceil(k / ehyb_spmm_max_k) passes over the matrix) and three vector kernels up to four columns wide.  B, X: device pointers,
