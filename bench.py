@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- fp64 EHYB SpMV throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one SpMV of the whole matrix, y = A x, through libehyb.so's HIP kernels.
+
+A plain run does what `value` needs and nothing else: build the matrix, partition, plan and tune, W warm-up steps,
+K timed steps, --dump-outputs, the JSON line.  `--full` adds everything else the line can carry (each listed below,
+each with a --no-* switch of its own): the check of the timed result against the CPU oracle, `cpu_baseline`,
+per-kernel times and `roofline` (with its live rocprofv3 --pmc children), and the side arms -- at N = 1 `walk`,
+`numeric_refill`, plain_storage, dropin_path, scaling_anchor (and, opt-in, vendor_baseline); at N > 1 the per-part
+times of the local multiply and single_gpu_same_matrix.
 
 N = 1  workload = BASELINE.json configs[1], audikw_1 -- as a statistically matched synthetic, because
        no .mtx file exists offline: 943,695 rows, 3 unknowns per node of a 68x68x69 grid truncated to
        314,565 nodes, 27-point node coupling plus hashed second-shell couplings tuned to audikw_1's
        77.65 M entries (82.3 per row), node labels scrambled so that locality has to come from the
-       partitioner.  `data` says so.  The same line also carries
+       partitioner.  `data` says so.  With --full the same line also carries
          plain_storage   the same matrix with every entry stored (no symmetric pair storage),
          dropin_path     the same matrix through the reference-named calls with the reference driver's
                          own sizing (matrixReorder -> vectorReorder -> spmvGPuEHYB -> vectorRecover),
@@ -27,7 +34,7 @@ N > 1  one process per GPU (the driver launches them with torch.distributed.run;
          --scaling weak             the N = 1 matrix once per GPU (fem3d workloads), rank-local build,
                halo exchange.
 
-Output: ONE JSON line on rank 0 with the contract's keys plus
+Output: ONE JSON line on rank 0 with the contract's keys plus (--full; null in a plain run)
   roofline      the dominant kernel (roofline_block): frac = the counters' bytes per launch (rocprofv3 --pmc FETCH_SIZE /
                 WRITE_SIZE taken by this run, else the table entry of exactly this layout, else the format's bytes)
                 / the launch's share of one multiply in the graph-replayed loop (HIP events on the launch stream)
@@ -313,7 +320,6 @@ def run_weak(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     rank r owning (and generating) block r only -- and a halo exchange of the x entries of the two
     grid layers next to each block boundary.  Per-GPU work is the N = 1 workload plus ~1 % coupling."""
     from ehyb_spmv_gpu_amd import dist as D
-    from oracle import oracle as O
 
     gen, gargs, desc = WORKLOADS[args.workload]
     n_loc = gargs[0]
@@ -325,10 +331,13 @@ def run_weak(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     cuts = [n_loc * r for r in range(world + 1)]
     r0, r1 = cuts[rank], cuts[rank + 1]
     log(f"[bench] rank 0 generated its block: {n_loc} rows, {len(V)} entries in {time.time() - t0:.1f}s")
-    # checker (not timed): the oracle on this rank's rows; x is a function of the global index
-    x = E.x_glibc(n_glob)
-    y_cpu = O.spmv_coo(n_glob, I, J, V, x)[r0:r1]
-    scale = O.abs_rowsum(n_glob, I, J, V, x)[r0:r1]
+    x = E.x_glibc(n_glob)   # a function of the global index
+    if args.full:
+        from oracle import oracle as O
+
+        # checker (not timed): the oracle on this rank's rows
+        y_cpu = O.spmv_coo(n_glob, I, J, V, x)[r0:r1]
+        scale = O.abs_rowsum(n_glob, I, J, V, x)[r0:r1]
     t0 = time.time()
     L = D.RankLocalMatrix(I, J, V, cuts, rank, cfg, symmetric=True)  # partition + permute the diagonal block, ghost slots
     del I, J
@@ -339,15 +348,18 @@ def run_weak(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     log(f"[bench] rank 0: reorder + plan in {time.time() - t0:.1f}s: ell {st['nnz_ell']} residual {st['nnz_er']} "
         f"ghost slots {L.n_ghost} (receives from {int((L.recv_counts.sum(axis=0) > 0).sum())} ranks)")
     elapsed = timed_steps(sh.step, args, torch, dist, world, dev)
-    # parity of what was just timed, every rank on its own rows
-    bad, worst = O.check_tolerance(sh.y_local(), y_cpu, scale)
-    bad, worst = all_ranks_agree_or_exit(bad, worst, torch, dist, world, dev, "weak scaling")
+    parity = None
+    if args.full:
+        # parity of what was just timed, every rank on its own rows
+        bad, worst = O.check_tolerance(sh.y_local(), y_cpu, scale)
+        bad, worst = all_ranks_agree_or_exit(bad, worst, torch, dist, world, dev, "weak scaling")
+        parity = {"rows_over_1e-12": bad, "worst_rel": worst}
+        log(f"[bench] parity vs CPU oracle (all ranks, own rows): {bad} rows over 1e-12, worst {worst:.3e}")
     tot = torch.tensor([float(len(V)), float(L.n_ghost)], dtype=torch.float64, device=dev)
     mx = torch.tensor([float(L.n_ghost)], dtype=torch.float64, device=dev)
     dist.all_reduce(tot)
     dist.all_reduce(mx, op=dist.ReduceOp.MAX)
     nnz = int(tot[0].item())
-    log(f"[bench] parity vs CPU oracle (all ranks, own rows): {bad} rows over 1e-12, worst {worst:.3e}")
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         out = {
@@ -365,7 +377,7 @@ def run_weak(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
                        "exchange": "halo: gather of the requested x entries + RCCL all_to_all_single into the ghost slots, "
                                    "overlapped with the ELL phase" if not stage_on_cpu else "halo via gloo point-to-point (functional mode)"},
             "alg_GBps": round((12 * nnz + 4 * (n_glob + 1) + 16 * n_glob) / (elapsed / args.steps) / 1e9, 1),
-            "roofline": None, "cpu_baseline": None, "parity": {"rows_over_1e-12": bad, "worst_rel": worst},
+            "roofline": None, "cpu_baseline": None, "parity": parity,
         }
         print(json.dumps(out), flush=True)
     if comm is not None:
@@ -386,7 +398,6 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     import numpy as np
 
     from ehyb_spmv_gpu_amd import dist as D
-    from oracle import oracle as O
 
     gen, gargs, desc = WORKLOADS[args.workload]
     if args.exchange is None:
@@ -426,8 +437,12 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     I, J, V = m.I[k0:k1].copy(), m.J[k0:k1].copy(), m.V[k0:k1].copy()
     symmetric = gen in SYMMETRIC_GENERATORS
     m.free()
-    y_cpu = O.spmv_coo(n, I, J, V, x)[r0:r1]      # checker (not timed): the oracle on this rank's rows
-    scale = O.abs_rowsum(n, I, J, V, x)[r0:r1]
+    O = None
+    if args.full:
+        from oracle import oracle as O
+
+        y_cpu = O.spmv_coo(n, I, J, V, x)[r0:r1]      # checker (not timed): the oracle on this rank's rows
+        scale = O.abs_rowsum(n, I, J, V, x)[r0:r1]
     t0 = time.time()
     # default: the hot quarter of every owner's ghost columns first (on R-MAT 2^24 at 8 ranks it carries 73-75 % of a rank's
     # entries: tools/dist_stats.py), the rest while those panels multiply
@@ -444,13 +459,18 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     log(f"[bench] rank 0: rows [{r0},{r1}) reorder + plan in {time.time() - t0:.1f}s: ell {st['nnz_ell']} residual {st['nnz_er']} "
         f"ghost columns {L.n_ghost} of {n - (r1 - r0)} remote")
     elapsed = timed_steps(sh.step, args, torch, dist, world, dev)
-    bad, worst = O.check_tolerance(sh.y_local(), y_cpu, scale)
-    bad, worst = all_ranks_agree_or_exit(bad, worst, torch, dist, world, dev, "strong scaling")
-    # per-rank time of the local multiply alone (no exchange), max over ranks: what is left is the exchange
-    if args.exchange in ("halo", "cover"):
-        own_ms, sh_local_ms = sh.time_parts(args.steps)   # the part that needs the rank's own columns only, and the whole
-    else:
-        own_ms, sh_local_ms = 0.0, sh.time_local(args.steps)
+    parity = None
+    own_ms = sh_local_ms = 0.0
+    if args.full:
+        bad, worst = O.check_tolerance(sh.y_local(), y_cpu, scale)
+        bad, worst = all_ranks_agree_or_exit(bad, worst, torch, dist, world, dev, "strong scaling")
+        parity = {"rows_over_1e-12": bad, "worst_rel": worst}
+        log(f"[bench] parity vs CPU oracle (all ranks, own rows): {bad} rows over 1e-12, worst {worst:.3e}")
+        # per-rank time of the local multiply alone (no exchange), max over ranks: what is left is the exchange
+        if args.exchange in ("halo", "cover"):
+            own_ms, sh_local_ms = sh.time_parts(args.steps)   # the part that needs the rank's own columns only, and the whole
+        else:
+            own_ms, sh_local_ms = 0.0, sh.time_local(args.steps)
     n_partials = int(L.yrecv_counts.sum())       # exchange "cover": partial sums this rank receives per step (0 otherwise)
     stats = torch.tensor([float(L.n_ghost), float(sh_local_ms), float(L.nnz), float(own_ms), float(L.nnz_own_cols), float(n_partials), float(L.nnz_exported)],
                          dtype=torch.float64, device=dev)
@@ -461,7 +481,6 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
     vol = torch.zeros(world, L.chunks * world, dtype=torch.float64, device=dev)
     vol[rank] = torch.from_numpy(L.recv_counts.astype(np.float64).reshape(-1)).to(dev)
     dist.all_reduce(vol)
-    log(f"[bench] parity vs CPU oracle (all ranks, own rows): {bad} rows over 1e-12, worst {worst:.3e}")
     # ---- the SAME matrix on ONE GPU, in this very run: rank 0 multiplies the whole matrix on its GPU while the others wait,
     # so that the line carries its own N = 1 point (the N = 1 default of bench.py is BASELINE config 2, another matrix)
     single = None
@@ -501,10 +520,10 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
                                                           for row in vol.cpu().numpy()] if world <= 8 else None,
                        "ghost_columns_per_gpu_max": int(mx[0].item()),
                        "functional_mode": "gloo, host-staged" if stage_on_cpu else None},
-            "local_multiply_ms_max_over_ranks": round(float(mx[1].item()), 5),
+            "local_multiply_ms_max_over_ranks": round(float(mx[1].item()), 5) if args.full else None,
             # what can run while the first exchange step is on the wire: the ELL launch + the panels of the rank's own columns
-            "own_columns_part_ms_max_over_ranks": round(float(mx[3].item()), 5),
-            "phase1_share_of_local_ms": round(float(mx[3].item()) / max(float(mx[1].item()), 1e-9), 4),
+            "own_columns_part_ms_max_over_ranks": round(float(mx[3].item()), 5) if args.full else None,
+            "phase1_share_of_local_ms": round(float(mx[3].item()) / max(float(mx[1].item()), 1e-9), 4) if args.full else None,
             "own_columns_share_of_entries": round(float(stats[4].item()) / max(float(stats[2].item()), 1.0), 4),
             "host_us_per_step": round(args.host_us_per_step, 1),
             # strong scaling read off ONE run: the whole job against the same matrix on rank 0's GPU alone
@@ -515,7 +534,7 @@ def run_strong(args, E, torch, dist, rank, world, dev, cfg, log, stage_on_cpu):
                               "the N = 1 line's value (same matrix, one GPU)" if args.workload == "audikw_1-like" else
                               f"bench.py --workload {args.workload} (N = 1)"),
             "alg_GBps": round((12 * nnz + 4 * (n + 1) + 16 * n) / (elapsed / args.steps) / 1e9, 1),
-            "roofline": None, "cpu_baseline": None, "parity": {"rows_over_1e-12": bad, "worst_rel": worst},
+            "roofline": None, "cpu_baseline": None, "parity": parity,
         }
         print(json.dumps(out), flush=True)
     if comm is not None:
@@ -735,6 +754,9 @@ def main():
     ap.add_argument("--ell-nt", type=int, default=0, help="cfg.ell_nt (A/B: 1 the whole value stream past the caches, 2 plain loads as in rounds 1-3; default: plain loads for the end of an alternating walk only)")
     ap.add_argument("--balance", type=int, default=0, help="cfg.balance (symmetric pairs, A/B: 1 = partitions balanced on entries, 2 = on rows)")
     ap.add_argument("--graph-compress", type=int, default=0, help="cfg.graph_compress of the k-way partitioner (A/B: 1 on, 2 off, 3 on + refinement on the rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides `value`: the check against the CPU oracle, the CPU baseline, per-kernel times and the roofline, and every side arm "
+                         "(module docstring); without it a run does only what `value` needs.  The --no-* options below switch parts of --full off")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the TIMED CPU legs (the parity check stays)")
     ap.add_argument("--no-overlap", action="store_true", help="N>1: exchange first, then multiply (no stream overlap)")
     ap.add_argument("--no-plain-arm", action="store_true",
@@ -748,7 +770,7 @@ def main():
     ap.add_argument("--no-refill-arm", action="store_true",
                     help="N=1: build the plan without slot maps and skip the timing of the numeric phase on the device (ehyb_plan_set_values)")
     ap.add_argument("--no-scaling-anchor", action="store_true", help="N=1: skip the one-GPU run of the N>1 default workload")
-    ap.add_argument("--vendor-baseline", action="store_true", help="N=1: also time rocSPARSE CSR SpMV on the same matrix (opt-in)")
+    ap.add_argument("--vendor-baseline", action="store_true", help="N=1 with --full: also time rocSPARSE CSR SpMV on the same matrix (opt-in)")
     ap.add_argument("--sym-pairs", default="auto", choices=["auto", "on", "off"],
                     help="symmetric pair storage (cfg.sym_pairs): auto = on for the symmetric workloads")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
@@ -781,6 +803,12 @@ def main():
         raise SystemExit("bench.py: --steps must be at least 1")
     if args.dump_outputs and args.gpus != 1:
         raise SystemExit("bench.py: --dump-outputs is an N = 1 option")
+    if args.vendor_baseline and not args.full:
+        raise SystemExit("bench.py: --vendor-baseline is a side arm of --full")
+    if not args.full:
+        # a plain run: no side arm (the oracle check, the roofline and the N > 1 per-part times are skipped where they stand)
+        args.no_cpu_baseline = args.no_plain_arm = args.no_dropin_arm = args.no_walk_arm = True
+        args.no_live_pmc = args.no_refill_arm = args.no_scaling_anchor = args.no_single_gpu_anchor = True
     args.host_us_per_step = 0.0
 
     world_env = os.environ.get("WORLD_SIZE")
@@ -868,8 +896,6 @@ def main():
         return
 
     # ================================================================== N = 1
-    from oracle import oracle as O
-
     if sym:
         kw["sym_pairs"] = 1
     cfg = E.make_config(partitioner=partitioner_for(E, gen), verbose=1 if args.verbose else 0, value_map=0 if args.no_refill_arm else 1, **kw)
@@ -878,26 +904,29 @@ def main():
     n, nnz = m.n, m.nnz
     log(f"[bench] {'read' if args.mtx else 'generated'} {args.workload}: n={n} nnz={nnz} in {time.time() - t0:.1f}s")
 
-    # ---- CPU baseline on the un-permuted matrix: the oracle, timed; its y is also the parity checker
-    cpu_baseline = None
+    # ---- CPU baseline on the un-permuted matrix: the oracle, timed; its y is also the parity checker (--full)
+    O = y_cpu = scale = cpu_baseline = None
     x = E.x_glibc(n)
-    if args.no_cpu_baseline:
-        y_cpu = O.spmv_coo(n, m.I, m.J, m.V, x)  # checker only, untimed
-    else:
-        rowptr = m.row_idx.astype(np.int64)
-        O.set_threads(E.host_threads())  # the CPUs this process owns (cgroup quota), not the ones it sees
-        t_coo, y_cpu = O.time_spmv(0, rowptr, m.I, m.J, m.V, x, reps=3)
-        t_csr1, _ = O.time_spmv(1, rowptr, m.I, m.J, m.V, x, reps=3)
-        t_omp, _ = O.time_spmv(2, rowptr, m.I, m.J, m.V, x, reps=5)
-        cores = O.max_threads()
-        cpu_baseline = {
-            "value": round(2.0 * nnz / t_omp / 1e9, 3), "unit": "GFLOP/s", "cores": cores, "kind": "port",
-            "sample": (f"whole {args.workload} matrix, best of 5 CSR fp64 SpMVs with OpenMP on {cores} threads; "
-                       f"1-thread CSR {2.0 * nnz / t_csr1 / 1e9:.3f} GFLOP/s; literal reference order "
-                       f"(solver_test.c:102, 1 thread) {2.0 * nnz / t_coo / 1e9:.3f} GFLOP/s"),
-        }
-        log(f"[bench] cpu baseline: {cpu_baseline['value']} GFLOP/s on {cores} threads")
-    scale = O.abs_rowsum(n, m.I, m.J, m.V, x)
+    if args.full:
+        from oracle import oracle as O
+
+        if args.no_cpu_baseline:
+            y_cpu = O.spmv_coo(n, m.I, m.J, m.V, x)  # checker only, untimed
+        else:
+            rowptr = m.row_idx.astype(np.int64)
+            O.set_threads(E.host_threads())  # the CPUs this process owns (cgroup quota), not the ones it sees
+            t_coo, y_cpu = O.time_spmv(0, rowptr, m.I, m.J, m.V, x, reps=3)
+            t_csr1, _ = O.time_spmv(1, rowptr, m.I, m.J, m.V, x, reps=3)
+            t_omp, _ = O.time_spmv(2, rowptr, m.I, m.J, m.V, x, reps=5)
+            cores = O.max_threads()
+            cpu_baseline = {
+                "value": round(2.0 * nnz / t_omp / 1e9, 3), "unit": "GFLOP/s", "cores": cores, "kind": "port",
+                "sample": (f"whole {args.workload} matrix, best of 5 CSR fp64 SpMVs with OpenMP on {cores} threads; "
+                           f"1-thread CSR {2.0 * nnz / t_csr1 / 1e9:.3f} GFLOP/s; literal reference order "
+                           f"(solver_test.c:102, 1 thread) {2.0 * nnz / t_coo / 1e9:.3f} GFLOP/s"),
+            }
+            log(f"[bench] cpu baseline: {cpu_baseline['value']} GFLOP/s on {cores} threads")
+        scale = O.abs_rowsum(n, m.I, m.J, m.V, x)
 
     # ---- host pre-step: partition + permute (matrixReorder), then the plan
     t0 = time.time()
@@ -935,58 +964,61 @@ def main():
 
     elapsed = timed_steps(step, args, torch, dist, 1, dev)
 
-    # ---- parity of what was just timed against the CPU oracle
-    y = E.vector_recover(y_d.cpu().numpy(), perm)
+    parity = roofline = None
+    if args.dump_outputs or args.full:
+        y = E.vector_recover(y_d.cpu().numpy(), perm)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, y, np, log)
-    bad, worst = O.check_tolerance(y, y_cpu, scale)
-    parity = {"rows_over_1e-12": bad, "worst_rel": worst}
-    log(f"[bench] parity vs CPU oracle: {bad} rows over 1e-12, worst {worst:.3e}")
-    if bad:
-        raise SystemExit("bench.py: GPU result differs from the CPU oracle; refusing to report a number")
+    if args.full:
+        # ---- parity of what was just timed against the CPU oracle
+        bad, worst = O.check_tolerance(y, y_cpu, scale)
+        parity = {"rows_over_1e-12": bad, "worst_rel": worst}
+        log(f"[bench] parity vs CPU oracle: {bad} rows over 1e-12, worst {worst:.3e}")
+        if bad:
+            raise SystemExit("bench.py: GPU result differs from the CPU oracle; refusing to report a number")
 
-    # ---- per-kernel timing with HIP events on the launch stream; roofline of the dominant kernel
-    r = plan.bench(xp, yp, stream, warmup=5, iters=min(args.steps, 200))
-    ell_ms, er_ms = r["ms_ell_avg"], r["ms_er_avg"]
-    inline = st["er_inline"] > 0  # the ELL launch also multiplies the (tiny) residual: one launch per SpMV
-    empty = st["nnz_er"] == 0
-    if inline or empty:
-        er_ms = 0.0  # no residual launch: the interval between the two events is event overhead
-    step_ms = r["ms_total"] / min(args.steps, 200)   # the graph-replayed loop between two HIP events on the launch stream
-    kname = dominant_kernel(st, ell_ms, er_ms)
-    traffic = pmc_traffic(args.workload, st["sym_pairs"] > 0, kname, st)
-    traffic_table, live_detail = traffic, None
-    if not args.no_live_pmc:
-        # the counters taken by THIS run (child processes under rocprofv3, after the timed loop: nothing of it is inside `value`)
-        live, live_detail = side_arm_pair("live PMC traffic", lambda: live_pmc_traffic(args.workload, st["sym_pairs"] > 0, kname, st, log, mtx=args.mtx), log)
-        if live:
-            traffic = live
-        else:
-            log(f"[bench] no live PMC measurement ({live_detail}): " + ("the table entry of this layout is quoted" if traffic else "format bytes are quoted"))
-    basis = ("rocprofv3 PMC bytes per launch measured by this run (tools/pmc_run.py under --pmc FETCH_SIZE and --pmc WRITE_SIZE, "
-             "separate passes, FETCH_SIZE calibrated on a 1 GiB streaming read in the same process)" if (traffic and traffic is not traffic_table) else
-             "rocprofv3 PMC bytes per launch of this workload, storage and kernel (profiles/pmc_traffic.json)"
-             if traffic else "format bytes per launch (what this layout makes the kernel move; no PMC measurement of exactly this layout on file)")
-    roofline = roofline_block(st, ell_ms, er_ms, step_ms, traffic, basis)
-    roofline["traffic_table"] = traffic_table
-    roofline["traffic_live"] = live_detail if isinstance(live_detail, dict) else None
-    achieved = roofline["achieved"]
-    # the second ceiling SURVEY 8d asks for: a streaming read of 4 GiB measured on this box in this run
-    try:
-        import ctypes as C
+        # ---- per-kernel timing with HIP events on the launch stream; roofline of the dominant kernel
+        r = plan.bench(xp, yp, stream, warmup=5, iters=min(args.steps, 200))
+        ell_ms, er_ms = r["ms_ell_avg"], r["ms_er_avg"]
+        inline = st["er_inline"] > 0  # the ELL launch also multiplies the (tiny) residual: one launch per SpMV
+        empty = st["nnz_er"] == 0
+        if inline or empty:
+            er_ms = 0.0  # no residual launch: the interval between the two events is event overhead
+        step_ms = r["ms_total"] / min(args.steps, 200)   # the graph-replayed loop between two HIP events on the launch stream
+        kname = dominant_kernel(st, ell_ms, er_ms)
+        traffic = pmc_traffic(args.workload, st["sym_pairs"] > 0, kname, st)
+        traffic_table, live_detail = traffic, None
+        if not args.no_live_pmc:
+            # the counters taken by THIS run (child processes under rocprofv3, after the timed loop: nothing of it is inside `value`)
+            live, live_detail = side_arm_pair("live PMC traffic", lambda: live_pmc_traffic(args.workload, st["sym_pairs"] > 0, kname, st, log, mtx=args.mtx), log)
+            if live:
+                traffic = live
+            else:
+                log(f"[bench] no live PMC measurement ({live_detail}): " + ("the table entry of this layout is quoted" if traffic else "format bytes are quoted"))
+        basis = ("rocprofv3 PMC bytes per launch measured by this run (tools/pmc_run.py under --pmc FETCH_SIZE and --pmc WRITE_SIZE, "
+                 "separate passes, FETCH_SIZE calibrated on a 1 GiB streaming read in the same process)" if (traffic and traffic is not traffic_table) else
+                 "rocprofv3 PMC bytes per launch of this workload, storage and kernel (profiles/pmc_traffic.json)"
+                 if traffic else "format bytes per launch (what this layout makes the kernel move; no PMC measurement of exactly this layout on file)")
+        roofline = roofline_block(st, ell_ms, er_ms, step_ms, traffic, basis)
+        roofline["traffic_table"] = traffic_table
+        roofline["traffic_live"] = live_detail if isinstance(live_detail, dict) else None
+        achieved = roofline["achieved"]
+        # the second ceiling SURVEY 8d asks for: a streaming read of 4 GiB measured on this box in this run
+        try:
+            import ctypes as C
 
-        from ehyb_spmv_gpu_amd import _lib
+            from ehyb_spmv_gpu_amd import _lib
 
-        bw = C.c_double(0)
-        if _lib.load().ehyb_measure_read_bw(C.c_size_t(1 << 32), 5, C.byref(bw)) == 0 and bw.value > 0:
-            roofline["measured_read_ceiling_GBps"] = round(bw.value, 1)
-            roofline["frac_of_measured_ceiling"] = round(achieved / bw.value, 4)
-    except Exception:  # the probe is a convenience: never let it cost the bench line
-        pass
-    if st["sym_pairs"] > 0:
-        roofline["note"] = ("symmetric pair storage: %d of the %d entries are in-partition pairs a_ij == a_ji stored once "
-                            "(one value read, two FMAs, the mirror product added in LDS): frac counts the bytes really "
-                            "moved; alg_frac prices every entry at 12 B (SURVEY 8d) and may exceed 1" % (2 * st["sym_pairs"], st["nnz"]))
+            bw = C.c_double(0)
+            if _lib.load().ehyb_measure_read_bw(C.c_size_t(1 << 32), 5, C.byref(bw)) == 0 and bw.value > 0:
+                roofline["measured_read_ceiling_GBps"] = round(bw.value, 1)
+                roofline["frac_of_measured_ceiling"] = round(achieved / bw.value, 4)
+        except Exception:  # the probe is a convenience: never let it cost the bench line
+            pass
+        if st["sym_pairs"] > 0:
+            roofline["note"] = ("symmetric pair storage: %d of the %d entries are in-partition pairs a_ij == a_ji stored once "
+                                "(one value read, two FMAs, the mirror product added in LDS): frac counts the bytes really "
+                                "moved; alg_frac prices every entry at 12 B (SURVEY 8d) and may exceed 1" % (2 * st["sym_pairs"], st["nnz"]))
     # ---- numeric phase of the build on the device: the plan's own values handed over again, as a host
     # array and as a device array, then the multiply checked once more.  After the timed loop: it cannot touch `value`.
     refill = None

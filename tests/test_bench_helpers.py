@@ -91,6 +91,14 @@ def test_world_size_must_match_gpus(monkeypatch):
     assert "WORLD_SIZE=2" in str(e.value)
 
 
+def test_vendor_baseline_needs_full(monkeypatch):
+    """--vendor-baseline is a side arm of --full: asked for in a plain run it is refused, not ignored."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--vendor-baseline"])
+    with pytest.raises(SystemExit) as e:
+        B.main()
+    assert "--full" in str(e.value)
+
+
 def test_rmat_row_blocks_are_the_rows_of_the_full_matrix(E):
     """ehyb_gen_rmat_block (strong scaling: every process generates its own row block only): the blocks of
     all processes are exactly the rows of ehyb_gen_rmat's matrix, the cuts are the same on every process

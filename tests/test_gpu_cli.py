@@ -84,7 +84,7 @@ def test_bench_vendor_baseline_arm(gpu):
     import sys
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "20", "--warmup", "3",
-                        "--vendor-baseline", "--no-cpu-baseline", "--no-plain-arm", "--no-live-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--vendor-baseline", "--no-cpu-baseline", "--no-plain-arm", "--no-live-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-2500:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -104,7 +104,7 @@ def test_bench_measures_its_traffic_in_the_run(gpu):
     import sys
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "20", "--warmup", "3",
-                        "--no-cpu-baseline", "--no-plain-arm", "--no-dropin-arm", "--no-scaling-anchor", "--no-refill-arm"],
+                        "--full", "--no-cpu-baseline", "--no-plain-arm", "--no-dropin-arm", "--no-scaling-anchor", "--no-refill-arm"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-2500:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -114,3 +114,34 @@ def test_bench_measures_its_traffic_in_the_run(gpu):
     # what the counters see is what the format says the kernel moves, to the partial cache lines at the ends of its streams
     assert 0.9 * r["format_bytes_per_launch"] < r["traffic"] < 1.25 * r["format_bytes_per_launch"], (r["traffic"], r["format_bytes_per_launch"])
     assert out["parity"]["rows_over_1e-12"] == 0
+
+
+def test_bench_plain_run_is_the_headline_only(E, O, gpu, tmp_path):
+    """bench.py without --full: the contract's keys, none of --full's checks, figures or side arms (no rocprofv3 child
+    either) -- and what it dumps is the product the CPU oracle computes, checked here since the plain run does not."""
+    import json
+    import sys
+
+    import numpy as np
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "20", "--warmup", "3",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-2500:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["value"] > 0 and out["unit"] == "GFLOP/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 20 and out["warmup"] == 3 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(2.0 * out["config"]["nnz"] / (out["ms_per_step"] * 1e6), rel=2e-3)
+    assert out["parity"] is None and out["roofline"] is None and out["cpu_baseline"] is None and out["walk"] is None
+    for key in ("numeric_refill", "plain_storage", "dropin_path", "vendor_baseline", "scaling_anchor"):
+        assert key not in out
+    assert "PMC" not in p.stderr and "cpu baseline" not in p.stderr
+    import bench as Bn
+
+    gen, gargs, _ = Bn.WORKLOADS["small"]
+    m = E.Matrix.generate(gen, *gargs)
+    x = E.x_glibc(m.n)
+    bad, worst = O.check_tolerance(np.load(tmp_path / "y.npy"), O.spmv_coo(m.n, m.I, m.J, m.V, x), O.abs_rowsum(m.n, m.I, m.J, m.V, x))
+    assert bad == 0, worst
+

@@ -1,7 +1,7 @@
 """The N > 1 paths on one GPU: `bench.py --gpus 2` with both ranks on cuda:0 over gloo (a functional
 run -- RCCL refuses ranks that share a device).  The HIP kernels, the two-phase multiply, the
 stream overlap and the exchange logic are the ones the multi-GPU run uses; only the transport
-differs.  bench.py checks its own result against the CPU oracle and refuses to print otherwise."""
+differs.  bench.py --full checks its own result against the CPU oracle and refuses to print otherwise."""
 import json
 import os
 import socket
@@ -21,12 +21,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _bench(world, extra, workload="small", launcher=True):
+def _bench(world, extra, workload="small", launcher=True, full=True):
     """launcher=True: as the driver starts it (torch.distributed.run); False: `python bench.py --gpus N`
     invoked plainly, which must start its ranks itself as a child process."""
     env = dict(os.environ, EHYB_BENCH_ONE_DEVICE="1", EHYB_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--workload", workload] + extra
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--workload", workload] + (["--full"] if full else []) + extra
     if launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + tail
@@ -71,6 +71,13 @@ def test_strong_allgather_three_ranks(gpu):
     assert "all_gather_into_tensor" in out["config"]["exchange"]
     # the row blocks come from a graph partition: a GPU's rows reference only a fraction of the others' columns
     assert out["config"]["ghost_columns_per_gpu_max"] < out["config"]["rows"] // 6
+
+
+def test_strong_plain_line_two_ranks(gpu):
+    """Without --full the N > 1 line is the headline alone: no oracle check, no per-part times, no single-GPU anchor."""
+    out = _bench(2, [], workload="rmat-18", full=False)
+    assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["parity"] is None and out["local_multiply_ms_max_over_ranks"] is None and out["single_gpu_same_matrix"] is None
 
 
 def test_world_size_mismatch_is_refused(gpu):

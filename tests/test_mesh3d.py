@@ -48,7 +48,7 @@ def test_bench_on_a_matrix_market_file(E, gpu, tmp_path):
     m = E.Matrix.generate("mesh3d", 60000, 3, 12, 1500, 3)
     path = tmp_path / "mesh60k.mtx"
     m.write_mtx(path, symmetric_lower_only=True)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mtx", str(path), "--steps", "20", "--warmup", "3", "--no-scaling-anchor"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mtx", str(path), "--steps", "20", "--warmup", "3", "--full", "--no-scaling-anchor"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-2500:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -45,9 +45,9 @@ for pass in miss hit; do
   grep -a "filename\|parts is\|reorder time\|plan cache\|iter is\|strict check\|PASSED\|FAILED\|wall clock\|symmetric pair\|CPU reference" $O/${TAG}_solver_test_$pass.txt
 done
 cd $GRAFT_REPO_ROOT
-python bench.py --mtx $W/read/audikw_1_like.mtx --steps 200 --warmup 20 --no-scaling-anchor > $O/${TAG}_bench_mtx.json 2> $O/${TAG}_bench_mtx.err || tail -5 $O/${TAG}_bench_mtx.err
+python bench.py --mtx $W/read/audikw_1_like.mtx --steps 200 --warmup 20 --full --no-scaling-anchor > $O/${TAG}_bench_mtx.json 2> $O/${TAG}_bench_mtx.err || tail -5 $O/${TAG}_bench_mtx.err
 grep -a "^\[bench\]" $O/${TAG}_bench_mtx.err | head -12
-python bench.py --steps 200 --warmup 20 --no-scaling-anchor --no-dropin-arm --no-plain-arm > $O/${TAG}_bench_generator.json 2> $O/${TAG}_bench_generator.err || tail -5 $O/${TAG}_bench_generator.err
+python bench.py --steps 200 --warmup 20 --full --no-scaling-anchor --no-dropin-arm --no-plain-arm > $O/${TAG}_bench_generator.json 2> $O/${TAG}_bench_generator.err || tail -5 $O/${TAG}_bench_generator.err
 python - $O/${TAG}_bench_mtx.json $O/${TAG}_bench_generator.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:
