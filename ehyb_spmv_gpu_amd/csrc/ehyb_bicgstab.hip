@@ -23,22 +23,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
-#include <vector>
+#include <cstring>
 
 #include "ehyb_internal.h"
-#include "vec_reduce.h"
+#include "solve_loop.h"
 
 using namespace ehyb;
-
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _e = (expr);                                                                             \
-        if (_e != hipSuccess) {                                                                             \
-            ::ehyb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return EHYB_ERR_HIP;                                                                            \
-        }                                                                                                   \
-    } while (0)
 
 namespace {
 
@@ -296,114 +286,56 @@ __global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const d
     }
 }
 
-// everything a solve owns; released on every way out
-struct Workspace {
-    double *r = nullptr, *rh = nullptr, *p = nullptr, *v = nullptr, *sv = nullptr, *sh = nullptr, *t = nullptr, *s = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t own = nullptr;
-    ~Workspace()
-    {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (own) (void)hipStreamDestroy(own);
-        for (double* a : {r, rh, p, v, sv, sh, t, s})
-            if (a) (void)hipFree(a);
-    }
-};
-
 }  // namespace
 
 extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
                              int check_every, void* stream, int* iters_done, double* rel_residual)
 {
-    clear_error();
-    if (!P || !b || !x) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab: null argument");
-    if (max_iter < 0 || !(rtol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab: max_iter %d, rtol %g", max_iter, rtol);
-    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab: needs a plan over all rows");
-    if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_bicgstab: plan not uploaded (no CPU fallback exists)");
+    int rc = solve_prologue("ehyb_bicgstab", P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
     const int n = P->host.n_cols;
-    hipStream_t st = (hipStream_t)stream;
-    if (check_every <= 0) check_every = 10;
-    check_every += check_every & 1;  // iterations are issued in even/odd pairs
-    Workspace W;
-    if (!st) {  // the legacy default stream cannot be captured: solve on a private (blocking) stream instead
-        HIP_TRY(hipStreamCreate(&W.own));
-        st = W.own;
-        stream = (void*)W.own;
-    }
-    for (double** a : {&W.r, &W.rh, &W.p, &W.v, &W.sv, &W.sh, &W.t}) HIP_TRY(hipMalloc((void**)a, std::max(1, n) * sizeof(double)));
-    const size_t s_doubles = (size_t)B_COUNT * kMaxGrid, s_bytes = s_doubles * sizeof(double) + F_COUNT * sizeof(int);
-    HIP_TRY(hipMalloc((void**)&W.s, s_bytes));
-    double *r = W.r, *rh = W.rh, *p = W.p, *v = W.v, *sv = W.sv, *sh = W.sh, *t = W.t, *s = W.s;
-    int* flags = (int*)(s + s_doubles);
-    const int grid = std::max(1, std::min((n + kThreads - 1) / kThreads, kMaxGrid / 2));  // as ehyb_pcg
+    SolveLoop L(n, check_every);
+    const int grid = L.grid;
+    double *r, *rh, *p, *v, *sv, *sh, *t, *s;
+    HIP_TRY(L.begin(stream, {&r, &rh, &p, &v, &sv, &sh, &t}, n, &s, B_COUNT, 1));  // the flags in the double behind the slots
+    int* flags = (int*)(s + (size_t)B_COUNT * kMaxGrid);
+    const hipStream_t st = L.st;
     const double thr = rtol * rtol;
 
     HIP_TRY(hipMemsetAsync(flags, 0, F_COUNT * sizeof(int), st));
     // v = A x0, walked last to first so that the first iteration's first-to-last walk starts on what it left in the cache
-    int rc = ehyb_spmv_walk(P, x, v, stream, EHYB_WALK_LAST_TO_FIRST);
-    if (rc != EHYB_OK) return rc;
+    if ((rc = ehyb_spmv_walk(P, x, v, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return rc;
     hipLaunchKernelGGL(bicg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, v, dinv, r, rh, p, s);
-    HIP_TRY(hipGetLastError());
-    std::vector<unsigned char> h(s_bytes);
-    auto read_scalar = [&](int which) {  // fixed order, like the device
-        const double* d = (const double*)h.data() + (size_t)which * kMaxGrid;
-        double sum = 0.0;
-        for (int i = 0; i < grid; ++i) sum += d[i];
-        return sum;
-    };
-    auto read_flag = [&](int which) { return ((const int*)(h.data() + s_doubles * sizeof(double)))[which]; };
-    HIP_TRY(hipMemcpyAsync(h.data(), s, s_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const double bb0 = read_scalar(B_BB), bb = bb0 > 0 ? bb0 : 1.0;
-    double rr = read_scalar(B_RR);
+    HIP_TRY(L.read());
+    const double bb0 = L.sum(B_BB), bb = bb0 > 0 ? bb0 : 1.0;
+    double rr = L.sum(B_RR);
     int status = !std::isfinite(bb0) || !std::isfinite(rr) ? ST_BREAKDOWN : rr <= thr * bb ? ST_CONVERGED : ST_RUNNING;
-    int done = 0;
+    int done = 0, it = 0;
 
-    auto enqueue_iteration = [&](int cur) -> int {
-        int e = ehyb_spmv_walk(P, p, v, stream, EHYB_WALK_FIRST_TO_LAST);  // v = A p^
-        if (e != EHYB_OK) return e;
-        hipLaunchKernelGGL(bicg_dot_kernel, dim3(grid), dim3(kThreads), 0, st, n, rh, v, s, flags);
-        hipLaunchKernelGGL(bicg_s_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, sv, sh, s, flags, cur);
-        if ((e = ehyb_spmv_walk(P, sh, t, stream, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // t = A s^
-        hipLaunchKernelGGL(bicg_dot2_kernel, dim3(grid), dim3(kThreads), 0, st, n, t, sv, s, flags);
-        hipLaunchKernelGGL(bicg_update_kernel, dim3(grid), dim3(kThreads), 0, st, n, p, sh, sv, t, rh, x, r, s, flags, cur, thr);
-        hipLaunchKernelGGL(bicg_direction_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, p, s, flags, cur, thr);
-        return EHYB_OK;
-    };
     // An even and an odd iteration -- four multiplies walking first to last, last to first, first to last, last to first --
-    // captured once and replayed.  cfg.graphs = 2 keeps the plain launches.
-    if (P->cfg.graphs != 2 && max_iter >= 2 && status == ST_RUNNING &&
-        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        int erc = enqueue_iteration(0);
-        if (erc == EHYB_OK) erc = enqueue_iteration(1);
-        const hipError_t eend = hipStreamEndCapture(st, &W.graph);
-        if (erc != EHYB_OK || eend != hipSuccess || hipGraphInstantiate(&W.exec, W.graph, nullptr, nullptr, 0) != hipSuccess)
-            W.exec = nullptr;
-        (void)hipGetLastError();
-    }
-    int it = 0;
-    while (it < max_iter && status == ST_RUNNING) {
-        const int burst = std::min(check_every, max_iter - it);  // even, except possibly the very last one
-        int k = 0;
-        for (; k + 2 <= burst; k += 2) {
-            if (W.exec) {
-                HIP_TRY(hipGraphLaunch(W.exec, st));
-            } else {
-                if ((rc = enqueue_iteration(0)) != EHYB_OK || (rc = enqueue_iteration(1)) != EHYB_OK) return rc;
-            }
-        }
-        if (k < burst && (rc = enqueue_iteration(0)) != EHYB_OK) return rc;
-        it += burst;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h.data(), s, s_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        status = read_flag(F_STATUS);
-        done = read_flag(F_ITERS);
-        rr = read_scalar(B_RR);
-    }
+    // are one graph; the plain launches use the same walks.
+    rc = L.run(
+        P, max_iter, it, [&] { return status == ST_RUNNING; },
+        [&](int cur, bool) -> int {
+            int e = ehyb_spmv_walk(P, p, v, st, EHYB_WALK_FIRST_TO_LAST);  // v = A p^
+            if (e != EHYB_OK) return e;
+            hipLaunchKernelGGL(bicg_dot_kernel, dim3(grid), dim3(kThreads), 0, st, n, rh, v, s, flags);
+            hipLaunchKernelGGL(bicg_s_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, sv, sh, s, flags, cur);
+            if ((e = ehyb_spmv_walk(P, sh, t, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // t = A s^
+            hipLaunchKernelGGL(bicg_dot2_kernel, dim3(grid), dim3(kThreads), 0, st, n, t, sv, s, flags);
+            hipLaunchKernelGGL(bicg_update_kernel, dim3(grid), dim3(kThreads), 0, st, n, p, sh, sv, t, rh, x, r, s, flags, cur, thr);
+            hipLaunchKernelGGL(bicg_direction_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, p, s, flags, cur, thr);
+            return EHYB_OK;
+        },
+        [&](int) -> int {
+            int f[F_COUNT];
+            std::memcpy(f, &L.h[(size_t)B_COUNT * kMaxGrid], sizeof f);
+            status = f[F_STATUS];
+            done = f[F_ITERS];
+            rr = L.sum(B_RR);
+            return EHYB_OK;
+        });
+    if (rc != EHYB_OK) return rc;
     if (iters_done) *iters_done = done;
     if (rel_residual) *rel_residual = std::sqrt(rr / bb);
     if (status == ST_BREAKDOWN)

@@ -23,22 +23,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <vector>
 
 #include "ehyb_internal.h"
-#include "vec_reduce.h"
+#include "solve_loop.h"
 
 using namespace ehyb;
-
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _e = (expr);                                                                             \
-        if (_e != hipSuccess) {                                                                             \
-            ::ehyb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return EHYB_ERR_HIP;                                                                            \
-        }                                                                                                   \
-    } while (0)
 
 namespace {
 
@@ -68,211 +58,15 @@ __global__ __launch_bounds__(kThreads) void cg_init_kernel(int n, const double* 
     put_partial(bb, s + A_BB * kMaxGrid);
 }
 
-__global__ __launch_bounds__(kThreads) void cg_dot_kernel(int n, const double* __restrict__ p,
-                                                          const double* __restrict__ q, double* __restrict__ s)
-{
-    double acc = 0.0;
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) acc = fma(p[i], q[i], acc);
-    put_partial(acc, s + A_PQ * kMaxGrid);
-}
-
-// cur: which of the two r.z arrays holds this iteration's r.z; the new one goes to the other
-__global__ __launch_bounds__(kThreads) void cg_update_kernel(int n, const double* __restrict__ p,
-                                                             const double* __restrict__ q, const double* __restrict__ dinv,
-                                                             double* __restrict__ x, double* __restrict__ r,
-                                                             double* __restrict__ s, int cur)
-{
-    const double alpha = sum_partials(s + (A_RZ0 + 2 * cur) * kMaxGrid) / sum_partials(s + A_PQ * kMaxGrid);
-    double rz = 0.0, rr = 0.0;
-    // four grid strides per trip: sixteen (twenty with a preconditioner) loads in flight per thread instead of four -- a thread
-    // sees only seven elements of the bench matrix's vectors, and one load round trip per element was most of this kernel's time
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double pv[4], qv[4], xv[4], rv[4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            pv[u] = p[i + u * stride];
-            qv[u] = __builtin_nontemporal_load(&q[i + u * stride]);   // q is dead after this kernel, x is not read again before the next
-            xv[u] = __builtin_nontemporal_load(&x[i + u * stride]);   // update: streamed past the caches, which hold the matrix's tail
-            rv[u] = r[i + u * stride];
-            dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            __builtin_nontemporal_store(fma(alpha, pv[u], xv[u]), &x[i + u * stride]);
-            const double ri = fma(-alpha, qv[u], rv[u]);
-            r[i + u * stride] = ri;
-            rz = fma(ri, dinv ? ri * dv[u] : ri, rz);
-            rr = fma(ri, ri, rr);
-        }
-    }
-    for (; i < n; i += stride) {
-        x[i] = fma(alpha, p[i], x[i]);
-        const double ri = fma(-alpha, q[i], r[i]);
-        r[i] = ri;
-        rz = fma(ri, dinv ? ri * dinv[i] : ri, rz);
-        rr = fma(ri, ri, rr);
-    }
-    put_partial(rz, s + (A_RZ0 + 2 * (cur ^ 1)) * kMaxGrid);
-    put_partial(rr, s + A_RR * kMaxGrid);
-}
-
-// p = z + beta p  (the reference's kernelMyxpy with gamma = beta)
-__global__ __launch_bounds__(kThreads) void cg_direction_kernel(int n, const double* __restrict__ r,
-                                                                const double* __restrict__ dinv, double* __restrict__ p,
-                                                                const double* __restrict__ s, int cur)
-{
-    const double beta = sum_partials(s + (A_RZ0 + 2 * (cur ^ 1)) * kMaxGrid) / sum_partials(s + (A_RZ0 + 2 * cur) * kMaxGrid);
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {  // (as in the update kernel: the loads of four strides in flight together)
-        double pv[4], rv[4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            pv[u] = p[i + u * stride];
-            rv[u] = r[i + u * stride];
-            dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[i + u * stride] = fma(beta, pv[u], dinv ? rv[u] * dv[u] : rv[u]);
-    }
-    for (; i < n; i += stride) p[i] = fma(beta, p[i], dinv ? r[i] * dinv[i] : r[i]);
-}
-
-// everything a solve owns; released on every way out
-struct Workspace {
-    double *r = nullptr, *p = nullptr, *q = nullptr, *s = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t own = nullptr;
-    ~Workspace()
-    {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (own) (void)hipStreamDestroy(own);
-        if (r) (void)hipFree(r);
-        if (p) (void)hipFree(p);
-        if (q) (void)hipFree(q);
-        if (s) (void)hipFree(s);
-    }
-};
-
-}  // namespace
-
-extern "C" int ehyb_cg(ehyb_plan* P, const double* b, double* x, int max_iter, double rtol, int check_every,
-                       void* stream, int* iters_done, double* rel_residual)
-{
-    return ehyb_pcg(P, nullptr, b, x, max_iter, rtol, check_every, stream, iters_done, rel_residual);
-}
-
-extern "C" int ehyb_pcg(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
-                        int check_every, void* stream, int* iters_done, double* rel_residual)
-{
-    clear_error();
-    if (!P || !b || !x || max_iter < 0 || !(rtol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_cg: bad arguments");
-    if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_cg: plan not uploaded (no CPU fallback exists)");
-    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_cg: needs a plan over all rows");
-    const int n = P->host.n_cols;
-    hipStream_t st = (hipStream_t)stream;
-    if (check_every <= 0) check_every = 10;
-    check_every += check_every & 1;  // iterations are issued in even/odd pairs
-    Workspace W;
-    if (!st) {  // the legacy default stream cannot be captured: solve on a private (blocking) stream instead
-        HIP_TRY(hipStreamCreate(&W.own));
-        st = W.own;
-        stream = (void*)W.own;
-    }
-    HIP_TRY(hipMalloc((void**)&W.r, (size_t)n * 8));
-    HIP_TRY(hipMalloc((void**)&W.p, (size_t)n * 8));
-    HIP_TRY(hipMalloc((void**)&W.q, (size_t)n * 8));
-    HIP_TRY(hipMalloc((void**)&W.s, (size_t)A_COUNT * kMaxGrid * sizeof(double)));
-    double *r = W.r, *p = W.p, *q = W.q, *s = W.s;
-    // two workgroups per CU: 115.7 us per iteration on the audikw_1-like matrix against 118-120 with
-    // 1024 workgroups (twice the partials to re-add) and 126 with 256
-    const int grid = std::max(1, std::min((n + kThreads - 1) / kThreads, kMaxGrid / 2));
-
-    int rc = ehyb_spmv(P, x, q, stream);  // q = A x0
-    if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(cg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, q, dinv, r, p, s);
-    std::vector<double> h((size_t)A_COUNT * kMaxGrid);
-    auto read_scalar = [&](int which) {  // fixed order, like the device
-        double t = 0.0;
-        for (int i = 0; i < grid; ++i) t += h[(size_t)which * kMaxGrid + i];
-        return t;
-    };
-    HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const double bb0 = read_scalar(A_BB), bb = bb0 > 0 ? bb0 : 1.0;
-    double rs = read_scalar(A_RR);  // ||r||^2 (the preconditioned product r.z drives the recurrences, not the stop test)
-
-    // p . q as a by-product of the multiply where one window launch writes all of q (the rows' p sits in its LDS window): the
-    // launch leaves one partial per workgroup in the slot the dot kernel would fill -- at most `grid` of them, the rest of the
-    // slot stays zero, and the update kernel adds the slot up in the same fixed order as ever.
-    const int xy_parts = P->cfg.cg_fused_dot != 2 ? spmv_xy_partials(P) : 0;
-    const bool fused = xy_parts > 0 && xy_parts <= grid;
-    if (fused) HIP_TRY(hipMemsetAsync(s + (size_t)A_PQ * kMaxGrid, 0, kMaxGrid * sizeof(double), st));
-    auto enqueue_iteration = [&](int cur) -> int {
-        // q = A p: x of the multiply changes every time
-        const int e = fused ? spmv_xy(P, p, q, stream, s + (size_t)A_PQ * kMaxGrid) : ehyb_spmv(P, p, q, stream);
-        if (e != EHYB_OK) return e;
-        if (!fused) hipLaunchKernelGGL(cg_dot_kernel, dim3(grid), dim3(kThreads), 0, st, n, p, q, s);
-        hipLaunchKernelGGL(cg_update_kernel, dim3(grid), dim3(kThreads), 0, st, n, p, q, dinv, x, r, s, cur);
-        hipLaunchKernelGGL(cg_direction_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, dinv, p, s, cur);
-        return EHYB_OK;
-    };
-    // An even and an odd iteration, captured once and replayed: one submission per two iterations
-    // instead of eight or ten launches.  cfg.graphs = 2 keeps the plain launches (A/B, debugging).
-    if (P->cfg.graphs != 2 && max_iter >= 2 &&
-        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        int erc = enqueue_iteration(0);
-        if (erc == EHYB_OK) erc = enqueue_iteration(1);
-        const hipError_t eend = hipStreamEndCapture(st, &W.graph);
-        if (erc != EHYB_OK || eend != hipSuccess ||
-            hipGraphInstantiate(&W.exec, W.graph, nullptr, nullptr, 0) != hipSuccess)
-            W.exec = nullptr;
-        (void)hipGetLastError();
-    }
-    int it = 0;
-    while (it < max_iter && std::sqrt(rs / bb) > rtol) {
-        const int burst = std::min(check_every, max_iter - it);  // even, except possibly the very last one
-        int k = 0;
-        for (; k + 2 <= burst; k += 2) {
-            if (W.exec) {
-                HIP_TRY(hipGraphLaunch(W.exec, st));
-            } else {
-                if ((rc = enqueue_iteration(0)) != EHYB_OK || (rc = enqueue_iteration(1)) != EHYB_OK) return rc;
-            }
-        }
-        if (k < burst && (rc = enqueue_iteration(0)) != EHYB_OK) return rc;
-        it += burst;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        rs = read_scalar(A_RR);
-        const double rz = read_scalar(A_RZ0 + 2 * (burst & 1));
-        if (!(rs == rs) || !(rz == rz)) {
-            rs = NAN;
-            break;  // NaN: breakdown (matrix or preconditioner not positive definite)
-        }
-    }
-    if (iters_done) *iters_done = it;
-    if (rel_residual) *rel_residual = std::sqrt(rs / bb);
-    if (!(rs == rs)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_cg: breakdown (is the matrix symmetric positive definite?)");
-    return EHYB_OK;
-}
-
-// ------------------------------------------------------------------ k right-hand sides, one multiply (ehyb_pcg_multi)
-// k independent solves on the same matrix that share every multiply: per iteration one ehyb_spmm of the k directions and the three
-// vector kernels K columns wide (K <= 4 per launch, ceil(k / 4) launches each).  Column j keeps its own alpha, beta and stopping
-// test and its own set of partial slots (s + j * A_COUNT * kMaxGrid); every kernel walks the indices with the grid and the
-// four-stride unroll of the one-vector kernels and does the same arithmetic in the same order per column, so column j is
-// ehyb_pcg(b_j) wherever the multiply is (plain storage).  One thread serves the K columns at one index: the inv_diag load is
-// shared and K times the loads are in flight.  A column whose active flag is 0 (converged or broken down) is skipped: its x, r,
-// p and partials stay as they are.
-namespace {
-
+// ------------------------------------------------------------------ the vector kernels, K columns per launch
+// One iteration of k independent solves on the same matrix that share every multiply (ehyb_pcg_multi) launches the three vector
+// kernels K columns wide (K <= 4 per launch, ceil(k / 4) launches each); the one-vector solve (ehyb_pcg, and the ehyb_cg_*_step
+// building blocks) launches them with K = 1.  Column j keeps its own alpha, beta and stopping test and its own set of partial
+// slots (s + j * A_COUNT * kMaxGrid; column 0's set is the one-vector layout); every kernel walks the indices with the same grid
+// and four-stride unroll and does the same arithmetic in the same order per column, so column j is ehyb_pcg(b_j) wherever the
+// multiply is (plain storage).  One thread serves the K columns at one index: the inv_diag load is shared and K times the loads
+// are in flight.  A column whose active flag is 0 (converged or broken down) is skipped: its x, r, p and partials stay as they
+// are.  A one-vector launch passes no flags (active = null: its column is live; K = 1 only, the wider kernels' code stays as it is).
 constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
 
 template <typename T>
@@ -281,7 +75,7 @@ __device__ __forceinline__ T* slot(T* s, int col, int which)
     return s + ((size_t)col * A_COUNT + which) * kMaxGrid;
 }
 
-// columns c0 .. c0 + K - 1: P, Q, R with leading dimension n, X with ldx
+// columns c0 .. c0 + K - 1: P, Q, R with leading dimension n, X with ldx.  pq = p . q
 template <int K>
 __global__ __launch_bounds__(kThreads) void cg_multi_dot_kernel(int n, const double* __restrict__ P, const double* __restrict__ Q,
                                                                 double* __restrict__ s, const int* __restrict__ active, int c0)
@@ -290,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void cg_multi_dot_kernel(int n, const dou
     double acc[K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-        on[c] = active[c0 + c] != 0;
+        on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         acc[c] = 0.0;
     }
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
@@ -308,6 +102,8 @@ __global__ __launch_bounds__(kThreads) void cg_multi_dot_kernel(int n, const dou
     }
 }
 
+// x += alpha p ; r -= alpha q ; rz_new = r . z ; rr = r . r  (alpha = rz / pq).  cur: which of the two r.z slots holds this
+// iteration's r.z; the new one goes to the other
 template <int K>
 __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const double* __restrict__ P, const double* __restrict__ Q,
                                                                    const double* __restrict__ dinv, double* __restrict__ X, long long ldx,
@@ -318,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
     double sums[2 * K], alpha[K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-        on[c] = active[c0 + c] != 0;
+        on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
         sums[K + c] = partials_of(slot(s, c0 + c, A_PQ));
     }
@@ -340,7 +136,10 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
         r[c] = R + (size_t)(c0 + c) * n;
         x[c] = X + (size_t)(c0 + c) * ldx;
     }
-    // as cg_update_kernel: four grid strides per trip, q and x past the caches; the loads of every column first
+    // four grid strides per trip, the loads of every column first: sixteen (twenty with a preconditioner) loads in flight per
+    // thread and column instead of four -- a thread sees only seven elements of the bench matrix's vectors, and one load round
+    // trip per element was most of this kernel's time.  q is dead after this kernel and x is not read again before the next
+    // update: both streamed past the caches, which hold the matrix's tail.
     const int stride = (int)gridDim.x * kThreads;
     int i = blockIdx.x * kThreads + threadIdx.x;
     for (; i + 3 * stride < n; i += 4 * stride) {
@@ -399,6 +198,7 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
     }
 }
 
+// p = z + beta p  (beta = rz_new / rz; the reference's kernelMyxpy with gamma = beta), four grid strides per trip as in the update
 template <int K>
 __global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, const double* __restrict__ R, const double* __restrict__ dinv,
                                                                       double* __restrict__ P, const double* __restrict__ s,
@@ -408,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, con
     double sums[2 * K], beta[K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-        on[c] = active[c0 + c] != 0;
+        on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * (cur ^ 1)));
         sums[K + c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
     }
@@ -451,26 +251,71 @@ __global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, con
     }
 }
 
-// the three kernels of one iteration for columns c0 .. c0 + w - 1
+// the kernels of one iteration for columns c0 .. c0 + K - 1 (dot: p . q is not a by-product of the multiply)
 template <int K>
-void launch_multi_vector_kernels(int grid, hipStream_t st, int n, double* P, const double* Q, const double* dinv, double* X,
-                                 long long ldx, double* R, double* s, const int* active, int c0, int cur)
+void launch_vector_kernels(int grid, hipStream_t st, int n, double* P, const double* Q, const double* dinv, double* X, long long ldx,
+                           double* R, double* s, const int* active, int c0, int cur, bool dot = true)
 {
-    hipLaunchKernelGGL(cg_multi_dot_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, s, active, c0);
+    if (dot) hipLaunchKernelGGL(cg_multi_dot_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, s, active, c0);
     hipLaunchKernelGGL(cg_multi_update_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, dinv, X, ldx, R, s, active, c0, cur);
     hipLaunchKernelGGL(cg_multi_direction_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, R, dinv, P, s, active, c0, cur);
 }
 
-struct MultiWorkspace : Workspace {
-    int* active = nullptr;
-    ~MultiWorkspace()
-    {
-        if (active) (void)hipFree(active);
-    }
-};
-
 }  // namespace
 
+extern "C" int ehyb_cg(ehyb_plan* P, const double* b, double* x, int max_iter, double rtol, int check_every,
+                       void* stream, int* iters_done, double* rel_residual)
+{
+    return ehyb_pcg(P, nullptr, b, x, max_iter, rtol, check_every, stream, iters_done, rel_residual);
+}
+
+extern "C" int ehyb_pcg(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
+                        int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    int rc = solve_prologue("ehyb_pcg", P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    const int n = P->host.n_cols;
+    SolveLoop L(n, check_every);
+    const int grid = L.grid;
+    double *r, *p, *q, *s;
+    HIP_TRY(L.begin(stream, {&r, &p, &q}, n, &s, A_COUNT));
+    const hipStream_t st = L.st;
+
+    if ((rc = ehyb_spmv(P, x, q, st)) != EHYB_OK) return rc;  // q = A x0
+    hipLaunchKernelGGL(cg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, q, dinv, r, p, s);
+    HIP_TRY(L.read());
+    const double bb0 = L.sum(A_BB), bb = bb0 > 0 ? bb0 : 1.0;
+    double rs = L.sum(A_RR);  // ||r||^2 (the preconditioned product r.z drives the recurrences, not the stop test)
+
+    // p . q as a by-product of the multiply where one window launch writes all of q (the rows' p sits in its LDS window): the
+    // launch leaves one partial per workgroup in the slot the dot kernel would fill -- at most `grid` of them, the rest of the
+    // slot stays zero, and the update kernel adds the slot up in the same fixed order as ever.
+    const int xy_parts = P->cfg.cg_fused_dot != 2 ? spmv_xy_partials(P) : 0;
+    const bool fused = xy_parts > 0 && xy_parts <= grid;
+    if (fused) HIP_TRY(hipMemsetAsync(s + (size_t)A_PQ * kMaxGrid, 0, kMaxGrid * sizeof(double), st));
+    int it = 0;
+    rc = L.run(
+        P, max_iter, it, [&] { return std::sqrt(rs / bb) > rtol; },
+        [&](int cur, bool) -> int {
+            // q = A p: x of the multiply changes every time
+            const int e = fused ? spmv_xy(P, p, q, st, s + (size_t)A_PQ * kMaxGrid) : ehyb_spmv(P, p, q, st);
+            if (e == EHYB_OK) launch_vector_kernels<1>(grid, st, n, p, q, dinv, x, n, r, s, nullptr, 0, cur, !fused);
+            return e;
+        },
+        [&](int cur) -> int {
+            rs = L.sum(A_RR);
+            const double rz = L.sum(A_RZ0 + 2 * cur);
+            if (!(rs == rs) || !(rz == rz)) rs = NAN;  // NaN: breakdown (matrix or preconditioner not positive definite)
+            return EHYB_OK;
+        });
+    if (rc != EHYB_OK) return rc;
+    if (iters_done) *iters_done = it;
+    if (rel_residual) *rel_residual = std::sqrt(rs / bb);
+    if (!(rs == rs)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg: breakdown (is the matrix symmetric positive definite?)");
+    return EHYB_OK;
+}
+
+// ------------------------------------------------------------------ k right-hand sides, one multiply (ehyb_pcg_multi)
 extern "C" int ehyb_cg_multi(ehyb_plan* P, const double* B, int64_t ldb, double* X, int64_t ldx, int k, int max_iter, double rtol,
                              int check_every, void* stream, int* iters_done, double* rel_residual)
 {
@@ -480,122 +325,78 @@ extern "C" int ehyb_cg_multi(ehyb_plan* P, const double* B, int64_t ldb, double*
 extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
                               int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
 {
-    clear_error();
-    if (!P || !B || !X) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: null argument");
     if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: k = %d right-hand sides (at least 1)", k);
-    if (max_iter < 0 || !(rtol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: max_iter %d, rtol %g", max_iter, rtol);
-    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: needs a plan over all rows");
-    const int n = P->host.n_cols;
-    if (ldb < n || ldx < n)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, n);
-    if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_pcg_multi: plan not uploaded (no CPU fallback exists)");
-    hipStream_t st = (hipStream_t)stream;
-    if (check_every <= 0) check_every = 10;
-    check_every += check_every & 1;
-    MultiWorkspace W;
-    if (!st) {
-        HIP_TRY(hipStreamCreate(&W.own));
-        st = W.own;
-        stream = (void*)W.own;
-    }
-    const size_t nk = (size_t)n * k, set = (size_t)A_COUNT * kMaxGrid;
-    HIP_TRY(hipMalloc((void**)&W.r, std::max<size_t>(1, nk) * 8));
-    HIP_TRY(hipMalloc((void**)&W.p, std::max<size_t>(1, nk) * 8));
-    HIP_TRY(hipMalloc((void**)&W.q, std::max<size_t>(1, nk) * 8));
-    HIP_TRY(hipMalloc((void**)&W.s, (size_t)k * set * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&W.active, (size_t)k * sizeof(int)));
-    double *R = W.r, *Pd = W.p, *Q = W.q, *s = W.s;
-    const int grid = std::max(1, std::min((n + kThreads - 1) / kThreads, kMaxGrid / 2));  // the one-vector solve's grid
-
-    int rc = ehyb_spmm(P, X, ldx, Q, n, k, stream, EHYB_WALK_AUTO);  // Q = A X0
+    if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, P->host.n_cols);
+    int rc = solve_prologue("ehyb_pcg_multi", P, B && X, max_iter, rtol);
     if (rc != EHYB_OK) return rc;
+    const int n = P->host.n_cols;
+    SolveLoop L(n, check_every);
+    const int grid = L.grid;
+    double *R, *Pd, *Q, *s;
+    HIP_TRY(L.begin(stream, {&R, &Pd, &Q}, (size_t)n * k, &s, (size_t)k * A_COUNT, (k + 1) / 2));  // the active flags behind the slots
+    int* active = (int*)(s + (size_t)k * A_COUNT * kMaxGrid);
+    const hipStream_t st = L.st;
+
+    if ((rc = ehyb_spmm(P, X, ldx, Q, n, k, st, EHYB_WALK_AUTO)) != EHYB_OK) return rc;  // Q = A X0
     for (int j = 0; j < k; ++j)
         hipLaunchKernelGGL(cg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, B + (size_t)j * ldb, Q + (size_t)j * n, dinv,
-                           R + (size_t)j * n, Pd + (size_t)j * n, s + (size_t)j * set);
-    std::vector<double> h((size_t)k * set);
-    auto read_scalar = [&](int j, int which) {  // fixed order, like the device
-        double t = 0.0;
-        for (int i = 0; i < grid; ++i) t += h[(size_t)j * set + (size_t)which * kMaxGrid + i];
-        return t;
-    };
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+                           R + (size_t)j * n, Pd + (size_t)j * n, s + (size_t)j * A_COUNT * kMaxGrid);
+    HIP_TRY(L.read());
     std::vector<double> bb(k), rs(k);
     std::vector<int> live(k), iters(k, 0);
     int n_live = 0;
     for (int j = 0; j < k; ++j) {
-        const double bb0 = read_scalar(j, A_BB);
+        const double bb0 = L.sum(j * A_COUNT + A_BB);
         bb[j] = bb0 > 0 ? bb0 : 1.0;
-        rs[j] = read_scalar(j, A_RR);
+        rs[j] = L.sum(j * A_COUNT + A_RR);
         live[j] = std::sqrt(rs[j] / bb[j]) > rtol;  // (NaN: frozen at once, reported as a breakdown)
         n_live += live[j];
     }
-    HIP_TRY(hipMemcpyAsync(W.active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
 
     // column groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
     const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
-    auto enqueue_iteration = [&](int cur, int walk) -> int {
-        const int e = ehyb_spmm(P, Pd, n, Q, n, k, stream, walk);  // Q = A P, frozen columns included (their q is not read)
-        if (e != EHYB_OK) return e;
-        for (int g = 0, c0 = 0; g < groups; ++g) {
-            const int w = k / groups + (g < k % groups ? 1 : 0);
-            switch (w) {
-            case 1: launch_multi_vector_kernels<1>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
-            case 2: launch_multi_vector_kernels<2>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
-            case 3: launch_multi_vector_kernels<3>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
-            default: launch_multi_vector_kernels<4>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, W.active, c0, cur); break;
-            }
-            c0 += w;
-        }
-        return EHYB_OK;
-    };
-    // as ehyb_pcg: an even and an odd iteration captured once and replayed.  The captured multiplies state their walks (first to
-    // last, then last to first), since a captured launch keeps the direction it was captured with.
-    if (P->cfg.graphs != 2 && max_iter >= 2 && n_live > 0 &&
-        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        int erc = enqueue_iteration(0, EHYB_WALK_FIRST_TO_LAST);
-        if (erc == EHYB_OK) erc = enqueue_iteration(1, EHYB_WALK_LAST_TO_FIRST);
-        const hipError_t eend = hipStreamEndCapture(st, &W.graph);
-        if (erc != EHYB_OK || eend != hipSuccess || hipGraphInstantiate(&W.exec, W.graph, nullptr, nullptr, 0) != hipSuccess)
-            W.exec = nullptr;
-        (void)hipGetLastError();
-    }
     int it = 0;
+    rc = L.run(
+        P, max_iter, it, [&] { return n_live > 0; },
+        [&](int cur, bool captured) -> int {
+            // Q = A P, frozen columns included (their q is not read).  A captured multiply keeps the direction it was captured
+            // with, so the captured ones state their walks: first to last, then last to first.
+            const int walk = !captured ? EHYB_WALK_AUTO : cur ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST;
+            const int e = ehyb_spmm(P, Pd, n, Q, n, k, st, walk);
+            if (e != EHYB_OK) return e;
+            for (int g = 0, c0 = 0; g < groups; ++g) {
+                const int w = k / groups + (g < k % groups ? 1 : 0);
+                switch (w) {
+                case 1: launch_vector_kernels<1>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
+                case 2: launch_vector_kernels<2>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
+                case 3: launch_vector_kernels<3>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
+                default: launch_vector_kernels<4>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
+                }
+                c0 += w;
+            }
+            return EHYB_OK;
+        },
+        [&](int cur) -> int {
+            bool changed = false;
+            for (int j = 0; j < k; ++j) {
+                if (!live[j]) continue;
+                rs[j] = L.sum(j * A_COUNT + A_RR);
+                const double rz = L.sum(j * A_COUNT + A_RZ0 + 2 * cur);
+                if (!(rs[j] == rs[j]) || !(rz == rz)) rs[j] = NAN;  // breakdown of this column: frozen, the others go on
+                if (!(std::sqrt(rs[j] / bb[j]) > rtol)) {
+                    live[j] = 0;
+                    iters[j] = it;
+                    --n_live;
+                    changed = true;
+                }
+            }
+            if (changed && n_live > 0) HIP_TRY(hipMemcpyAsync(active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
+            return EHYB_OK;
+        });
+    if (rc != EHYB_OK) return rc;
     bool broke = false;
-    while (it < max_iter && n_live > 0) {
-        const int burst = std::min(check_every, max_iter - it);
-        int b = 0;
-        for (; b + 2 <= burst; b += 2) {
-            if (W.exec) {
-                HIP_TRY(hipGraphLaunch(W.exec, st));
-            } else {
-                if ((rc = enqueue_iteration(0, EHYB_WALK_AUTO)) != EHYB_OK || (rc = enqueue_iteration(1, EHYB_WALK_AUTO)) != EHYB_OK)
-                    return rc;
-            }
-        }
-        if (b < burst && (rc = enqueue_iteration(0, EHYB_WALK_AUTO)) != EHYB_OK) return rc;
-        it += burst;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h.data(), s, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        bool changed = false;
-        for (int j = 0; j < k; ++j) {
-            if (!live[j]) continue;
-            rs[j] = read_scalar(j, A_RR);
-            const double rz = read_scalar(j, A_RZ0 + 2 * (burst & 1));
-            if (!(rs[j] == rs[j]) || !(rz == rz)) rs[j] = NAN;  // breakdown of this column: frozen, the others go on
-            if (!(std::sqrt(rs[j] / bb[j]) > rtol)) {
-                live[j] = 0;
-                iters[j] = it;
-                --n_live;
-                changed = true;
-            }
-        }
-        if (changed && n_live > 0)
-            HIP_TRY(hipMemcpyAsync(W.active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
-    }
     for (int j = 0; j < k; ++j) {
         if (live[j]) iters[j] = it;
         if (iters_done) iters_done[j] = iters[j];
@@ -607,10 +408,11 @@ extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B,
 }
 
 // ------------------------------------------------------------------ building blocks for a multi-GPU caller
-// The same four vector kernels for a caller that owns the loop (ehyb_spmv_gpu_amd/dist.py HaloCG: one
-// process per GPU, the multiply through the halo exchange): every rank runs them on its rows with the
-// SAME grid, and an all_reduce (sum) of a slot of the partial array turns every rank's partials into
-// the element-wise global ones -- the kernel that needs the scalar adds them up as before.
+// The same four vector kernels (those of an iteration with K = 1) for a caller that owns the loop
+// (ehyb_spmv_gpu_amd/dist.py HaloCG: one process per GPU, the multiply through the halo exchange): every
+// rank runs them on its rows with the SAME grid, and an all_reduce (sum) of a slot of the partial array
+// turns every rank's partials into the element-wise global ones -- the kernel that needs the scalar adds
+// them up as before.
 //   s: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout); r.z number c (0/1) lives in slot rz0 + 2 c, r.r
 //   between the two; every launch uses slot_doubles / 2 workgroups.
 extern "C" int ehyb_cg_layout(int* slots, int* slot_doubles, int* slot_bb, int* slot_pq, int* slot_rr, int* slot_rz0)
@@ -645,7 +447,7 @@ extern "C" int ehyb_cg_dot_step(int n, const double* p, const double* q, double*
 {
     int rc = check_vec(n, p, q, s, "ehyb_cg_dot_step");
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(cg_dot_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, s);
+    hipLaunchKernelGGL(cg_multi_dot_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, s, nullptr, 0);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -655,7 +457,8 @@ extern "C" int ehyb_cg_update_step(int n, const double* p, const double* q, cons
 {
     int rc = check_vec(n, p, q, s, "ehyb_cg_update_step");
     if (rc != EHYB_OK || !x || !r) return rc != EHYB_OK ? rc : EHYB_ERR_ARG;
-    hipLaunchKernelGGL(cg_update_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, dinv, x, r, s, cur & 1);
+    hipLaunchKernelGGL(cg_multi_update_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, dinv, x, n, r, s,
+                       nullptr, 0, cur & 1);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -664,7 +467,8 @@ extern "C" int ehyb_cg_direction_step(int n, const double* r, const double* dinv
 {
     int rc = check_vec(n, r, p, s, "ehyb_cg_direction_step");
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(cg_direction_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, r, dinv, p, s, cur & 1);
+    hipLaunchKernelGGL(cg_multi_direction_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, r, dinv, p, s, nullptr,
+                       0, cur & 1);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }

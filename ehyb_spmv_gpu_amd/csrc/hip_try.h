@@ -1,5 +1,5 @@
 // HIP_TRY(expr): a failed HIP call records its error (set_error) and returns EHYB_ERR_NO_DEVICE or EHYB_ERR_HIP from the calling
-// C-ABI function.  (ehyb_cg.hip and ehyb_comm.hip map errors their own way.)
+// C-ABI function.  (ehyb_comm.hip maps errors its own way.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // Fixed-order reductions of the device-resident solvers (ehyb_cg.hip, ehyb_bicgstab.hip).  A vector kernel writes one
 // partial sum per workgroup (put_partial); the kernel that needs the scalar adds the partials of a slot up again
-// (sum_partials) -- every workgroup for itself, in the same order, so every workgroup gets the same bits and a solve is
-// reproducible run to run.  No atomics.
+// (block_sum_n over partials_of) -- every workgroup for itself, in the same order, so every workgroup gets the same bits and a
+// solve is reproducible run to run.  No atomics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,13 +27,6 @@ __device__ __forceinline__ double block_sum(double v)
 #pragma unroll
     for (int w = 0; w < kThreads / 64; ++w) s += part[w];
     return s;
-}
-
-__device__ __forceinline__ double sum_partials(const double* __restrict__ part)
-{
-    double v = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) v += part[i];
-    return block_sum(v);
 }
 
 __device__ __forceinline__ void put_partial(double v, double* __restrict__ part)

@@ -1,5 +1,5 @@
-"""ehyb_bicgstab on the host: every argument check of the BiCGSTAB solve, on plans that were never uploaded -- the checks
-come before any device work, so nothing here needs a GPU."""
+"""ehyb_bicgstab and ehyb_pcg on the host: every argument check of the two one-vector solves (the same C signature), on plans
+that were never uploaded -- the checks come before any device work, so nothing here needs a GPU."""
 import ctypes as C
 
 import pytest
@@ -23,49 +23,56 @@ def plan(E):
 
 
 B, X, D = C.c_void_p(0x10000), C.c_void_p(0x20000), C.c_void_p(0x30000)   # never read: every call fails before device work
+SOLVERS = ["ehyb_bicgstab", "ehyb_pcg"]
 
 
-def call(lib, plan, h=None, d=D, b=B, x=X, max_iter=50, rtol=1e-8, check_every=10, outputs=True):
+def call(lib, plan, who, h=None, d=D, b=B, x=X, max_iter=50, rtol=1e-8, check_every=10, outputs=True):
     it, rel = C.c_int(-5), C.c_double(-5.0)
     h = plan.h if h is None else h
-    rc = lib.ehyb_bicgstab(h, d, b, x, max_iter, rtol, check_every, None, C.byref(it) if outputs else None,
+    rc = getattr(lib, who)(h, d, b, x, max_iter, rtol, check_every, None, C.byref(it) if outputs else None,
                            C.byref(rel) if outputs else None)
     return rc, lib.ehyb_last_error()
 
 
-def test_never_uploaded_plan_is_a_state_error(E, plan):
+@pytest.mark.parametrize("who", SOLVERS)
+def test_never_uploaded_plan_is_a_state_error(E, plan, who):
     lib = E.host._lib.load()
-    rc, msg = call(lib, plan)
-    assert rc == ERR_STATE and b"upload" in msg and b"ehyb_bicgstab" in msg
+    rc, msg = call(lib, plan, who)
+    assert rc == ERR_STATE and b"upload" in msg and who.encode() in msg
     # zero iterations, rtol = 0, check_every <= 0, no preconditioner, no outputs: still only the upload is missing
     for kw in (dict(max_iter=0), dict(rtol=0.0), dict(check_every=0), dict(check_every=-3), dict(d=None), dict(outputs=False)):
-        rc, _ = call(lib, plan, **kw)
+        rc, _ = call(lib, plan, who, **kw)
         assert rc == ERR_STATE, kw
 
 
 BAD = [dict(b=None), dict(x=None), dict(max_iter=-1), dict(rtol=-1e-9), dict(rtol=float("nan")), dict(rtol=float("-inf"))]
+BAD_IDS = ["b", "x", "max_iter", "rtol-neg", "rtol-nan", "rtol-neg-inf"]
+# ids: the bad argument alone for ehyb_bicgstab, prefixed with the entry point for the others
+CASES = [pytest.param(who, bad, id=i if who == "ehyb_bicgstab" else f"{who}-{i}") for who in SOLVERS for bad, i in zip(BAD, BAD_IDS)]
 
 
-@pytest.mark.parametrize("bad", BAD, ids=["b", "x", "max_iter", "rtol-neg", "rtol-nan", "rtol-neg-inf"])
-def test_argument_errors_come_before_the_state_error(E, plan, bad):
+@pytest.mark.parametrize("who,bad", CASES)
+def test_argument_errors_come_before_the_state_error(E, plan, who, bad):
     lib = E.host._lib.load()
-    rc, msg = call(lib, plan, **bad)
+    rc, msg = call(lib, plan, who, **bad)
     assert rc == ERR_ARG, bad
-    assert b"ehyb_bicgstab" in msg, (bad, msg)
+    assert who.encode() in msg, (bad, msg)
 
 
-def test_null_plan(E):
+@pytest.mark.parametrize("who", SOLVERS)
+def test_null_plan(E, who):
     lib = E.host._lib.load()
-    rc = lib.ehyb_bicgstab(None, D, B, X, 10, 1e-8, 10, None, None, None)
+    rc = getattr(lib, who)(None, D, B, X, 10, 1e-8, 10, None, None, None)
     assert rc == ERR_ARG and lib.ehyb_last_error()
 
 
-def test_plan_over_some_rows_is_refused(E):
+@pytest.mark.parametrize("who", SOLVERS)
+def test_plan_over_some_rows_is_refused(E, who):
     lib = E.host._lib.load()
     part = host_plan(E, half=True, direct=2)
     assert 0 < part.rows[1] < part.n
-    rc, msg = call(lib, part)
+    rc, msg = call(lib, part, who)
     assert rc == ERR_ARG and b"all rows" in msg
-    rc, _ = call(lib, part, max_iter=-1)
+    rc, _ = call(lib, part, who, max_iter=-1)
     assert rc == ERR_ARG
 
