@@ -81,7 +81,8 @@ class Config(C.Structure):
         ("col_map", C.c_int32),
         ("er_nt", C.c_int32),
         ("ell_nt", C.c_int32),
-        ("reserved", C.c_int32 * 21),
+        ("ell_keep", C.c_int32),
+        ("reserved", C.c_int32 * 20),
     ]
 
 
@@ -136,6 +137,9 @@ SIGNATURES = {
     "ehyb_plan_save": (C.c_int, [_vp, _ip, C.c_uint64, C.c_char_p]),
     "ehyb_plan_load": (C.c_int, [C.c_char_p, C.c_uint64, _P(_vp), _ip]),
     "ehyb_plan_stats": (C.c_int, [_vp, _P(Stats)]),
+    "ehyb_plan_resident_bytes": (C.c_int64, [_vp]),
+    "ehyb_ell_slab_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ehyb_ell_auto_keep1024": (C.c_int, [C.c_int64, C.c_int64]),
     "ehyb_plan_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
     "ehyb_spmv": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_spmv_phase": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),

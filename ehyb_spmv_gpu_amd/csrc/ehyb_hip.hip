@@ -487,6 +487,58 @@ __global__ __launch_bounds__(256) void ehyb_read_kernel(const double2* __restric
 }
 
 // ------------------------------------------------------------------ launches
+// ---- which slabs of the window kernel's value stream stay in the Infinity Cache (ell_device.h: ell_slab_resident)
+constexpr long long kInfinityCache = 256ll << 20;
+// The share of the cache a pinned set may take of what the launch's other traffic leaves (chosen from tools/resident_sweep.py:
+// profiles/r05_resident_sweep.txt)
+constexpr double kEllKeepSafety = 0.9;
+
+// The automatic share of a value stream of `value_bytes` that is pinned, in 1/1024: what the cache holds beside the bytes the
+// launch reads again and writes with plain accesses (column words, lane maps, slab records, items, x, y, halo lists), times
+// the safety factor; all of a stream that fits the cache together with them.
+static int ell_auto_keep1024(long long value_bytes, long long plain_bytes)
+{
+    if (value_bytes <= 0 || value_bytes + plain_bytes <= kInfinityCache) return 1024;
+    const double room = std::max(0.0, (double)(kInfinityCache - plain_bytes)) * kEllKeepSafety;
+    return (int)std::min(1024.0, std::floor(1024.0 * room / (double)value_bytes));
+}
+
+// successive launches of the plan walk in alternating directions by themselves (cfg.ell_alternate): where the stream does not
+// fit the cache but the cache is still a fair share of it.  A pinned set is the same for both directions: such plans do not alternate.
+static bool ell_alternates(const ehyb_plan* P)
+{
+    const long long b = P->host.stats.bytes_format_ell;
+    const bool pinned = P->cfg.ell_nt == 4 || P->cfg.ell_nt == 5;
+    return P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && !pinned && b > kInfinityCache && b <= (8192ll << 20));
+}
+
+// cfg.ell_nt -> (keep1024, shape) of a launch; alternating_walk: the launch is one of an alternating walk (ell_walk)
+static void ell_keep_rule(const ehyb_plan* P, bool alternating_walk, int* keep1024, int* shape)
+{
+    const ehyb_stats& S = P->host.stats;
+    const int nt = P->cfg.ell_nt;
+    // a stream the 256 MB Infinity Cache holds whole stays there from one multiply to the next: plain loads (120 k rows, 65 MB: 15.4 us, with
+    // the hint 16.2)
+    const bool fits = S.bytes_format_ell <= kInfinityCache;
+    *shape = nt == 4 ? ELL_KEEP_SPREAD : (nt == 5 ? ELL_KEEP_BLOCK : ELL_KEEP_WALK_END);
+    if (nt == 1 || nt == 2) {
+        *keep1024 = nt == 2 ? 1024 : 0;   // the A/B arms: never / always the hint
+    } else if (nt == 4 || nt == 5) {
+        const long long value_bytes = 8 * S.size_block_ell;
+        *keep1024 = P->cfg.ell_keep > 0 ? (int)((long long)P->cfg.ell_keep * 1024 / 1000) : ell_auto_keep1024(value_bytes, S.bytes_format_ell - value_bytes);
+    } else if (fits) {
+        *keep1024 = 1024;
+    } else if (alternating_walk) {
+        // cfg.ell_nt = 3: the END of every walk -- the share of the stream the cache can hold -- is read with plain loads, so that it is
+        // still there when the next launch starts from that end (half, three quarters and five quarters of that share measured level:
+        // profiles/r04_nt_hints_ab.txt)
+        const double keep = std::min(1.0, (double)kInfinityCache / (double)std::max<long long>(1, S.bytes_format_ell));
+        *keep1024 = 1024 - (int)(1024.0 * (1.0 - keep));
+    } else {
+        *keep1024 = 0;
+    }
+}
+
 static thread_local int t_probe_n = 0;   // ehyb_debug_ell_stamps_probe: the stamped launch stages every window entry from three vectors
 static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long long* stamps, double* xy_out)
 {
@@ -507,9 +559,7 @@ static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long 
     A.reverse = 0;
     A.reverse_items = 0;
     A.probe_n = stamps ? t_probe_n : 0;
-    // a stream the 256 MB Infinity Cache holds whole stays there from one multiply to the next: plain loads (120 k rows, 65 MB: 15.4 us, with the hint
-    // 16.2); cfg.ell_nt = 1 forces the hint.  (ell_walk lowers nt_slabs for an alternating walk with cfg.ell_nt = 3)
-    A.nt_slabs = (P->cfg.ell_nt == 2 || (P->cfg.ell_nt != 1 && P->host.stats.bytes_format_ell <= (256ll << 20))) ? 0 : 1024;
+    ell_keep_rule(P, false, &A.keep1024, &A.keep_shape);
     // on by default: plain storage 143 -> 134 us on the audikw_1-like matrix; cfg.xcd_map = 2 for the A/B
     A.xcd_map = P->host.sym ? 0 : (P->cfg.xcd_map != 2 ? 1 : 0);
     A.item_map = P->d_item_map;  // symmetric pairs: items are sorted heaviest first, dispatched in that order
@@ -523,21 +573,13 @@ static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long 
 // 136.8; 120 k rows, 65 MB, 15.4 -> 16.2; kkt3d-200, 2.56 GB, 501.9 -> 473.7 once the items are taken from the far end too)
 static void ell_walk(ehyb_plan* P, int walk, int n_items, size_t lds, EllArgs* A)
 {
-    const HostLayout& H = P->host;
-    const bool alternates = P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.stats.bytes_format_ell > (256ll << 20) && H.stats.bytes_format_ell <= (8192ll << 20));
-    if (walk >= 0 || alternates) {
+    if (walk >= 0 || ell_alternates(P)) {
         // the caller's explicit direction (ehyb_spmv_walk), else the plan's own alternation: an atomic flip, so that every one of
         // several threads launching the same plan draws a direction (plain storage: the result does not depend on it)
         A->reverse = walk >= 0 ? (walk & 1) : (P->launch_parity.fetch_xor(1, std::memory_order_relaxed) & 1);
         // more than one round of workgroups: what ran in the last round is what the cache holds, so it runs first now
         A->reverse_items = (A->reverse && n_items > kNumCU * (lds > 80 * 1024 ? 1 : 2)) ? 1 : 0;
-        // cfg.ell_nt = 3: the END of every walk -- the share of the stream the 256 MB Infinity Cache can hold -- is read with plain loads,
-        // so that it is still there when the next launch starts from that end
-        // (half, three quarters and five quarters of that share measured level: profiles/r04_nt_hints_ab.txt)
-        if (P->cfg.ell_nt == 3) {
-            const double keep = std::min(1.0, (double)(256ll << 20) / (double)std::max<long long>(1, H.stats.bytes_format_ell));
-            A->nt_slabs = (int)(1024.0 * (1.0 - keep));
-        }
+        ell_keep_rule(P, true, &A->keep1024, &A->keep_shape);   // (cfg.ell_nt = 3: the end of an alternating walk is read with plain loads)
     }
 }
 
@@ -1188,6 +1230,29 @@ int ehyb_spmv_walk(ehyb_plan* P, const double* x, double* y, void* stream, int w
     return ehyb_spmv_phase(P, x, y, stream, 0);
 }
 
+// ---- the pinned share of the value stream, for tools and tests (host arithmetic; no device needed)
+int ehyb_ell_slab_resident(int pos, int n, int keep1024, int shape) { return ell_slab_resident(pos, n, keep1024, shape) ? 1 : 0; }
+
+int ehyb_ell_auto_keep1024(int64_t value_bytes, int64_t plain_bytes) { return ell_auto_keep1024(value_bytes, plain_bytes); }
+
+int64_t ehyb_plan_resident_bytes(const ehyb_plan* P)
+{
+    if (!P) {
+        set_error("ehyb_plan_resident_bytes: null argument");
+        return -1;
+    }
+    const HostLayout& H = P->host;
+    int keep1024 = 0, shape = 0;
+    ell_keep_rule(P, ell_alternates(P), &keep1024, &shape);
+    int64_t bytes = 0;
+    for (size_t sg = 0; sg < H.segs.size(); sg += 8) {
+        const int sb = H.segs[sg + 1], se = H.segs[sg + 2];
+        for (int s = sb; s < se; ++s)   // (WALK_END: the walk first to last)
+            if (ell_slab_resident(s - sb, se - sb, keep1024, shape)) bytes += (int64_t)(H.slab_meta[(size_t)s * 4 + 3] >> 16) * kSlabRows * 16;
+    }
+    return bytes;
+}
+
 // ---- a captured multiply (or run of multiplies) that keeps the alternation: see ehyb.h
 struct ehyb_graph {
     hipGraphExec_t exec[2] = {nullptr, nullptr};   // [d]: the run starting with direction d; equal runs (even count, or a plan that does not alternate) share exec[0]
@@ -1204,7 +1269,10 @@ int ehyb_spmv_graph_create(ehyb_plan* P, const double* x, double* y, int multipl
     hipStream_t own = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
     ehyb_graph* G = new ehyb_graph;
-    G->two = (multiplies & 1) != 0;   // an odd run ends on the direction it began with: the next launch must begin with the other
+    // a window-only plan with a pinned set reads the same slabs from the cache in either direction: every captured multiply walks first
+    // to last and one executable serves (a panel residual's first pass still alternates: such plans are captured as before)
+    const bool one_way = (P->cfg.ell_nt == 4 || P->cfg.ell_nt == 5) && !ell_alternates(P) && !P->host.er_panel;
+    G->two = !one_way && (multiplies & 1) != 0;   // an odd run ends on the direction it began with: the next launch must begin with the other
     int rc = EHYB_OK;
     for (int d = 0; d < (G->two ? 2 : 1) && rc == EHYB_OK; ++d) {
         hipGraph_t g = nullptr;
@@ -1212,7 +1280,7 @@ int ehyb_spmv_graph_create(ehyb_plan* P, const double* x, double* y, int multipl
             rc = EHYB_ERR_HIP;
             break;
         }
-        for (int i = 0; i < multiplies && rc == EHYB_OK; ++i) rc = ehyb_spmv_walk(P, x, y, (void*)own, (d + i) & 1);
+        for (int i = 0; i < multiplies && rc == EHYB_OK; ++i) rc = ehyb_spmv_walk(P, x, y, (void*)own, one_way ? 0 : (d + i) & 1);
         const hipError_t e = hipStreamEndCapture(own, &g);
         if (rc == EHYB_OK && (e != hipSuccess || hipGraphInstantiate(&G->exec[d], g, nullptr, nullptr, 0) != hipSuccess)) rc = EHYB_ERR_HIP;
         if (g) (void)hipGraphDestroy(g);

@@ -108,11 +108,13 @@ struct Config {
     int er_queue;           // 0 automatic (queues from six items per resident workgroup up), 1 per-XCD work queues with stealing, 2 one workgroup per item
     int symbolic;           // where the panel form is built by ehyb_plan_create[_segs]: 1 host, 2 device (default)
     int cg_fused_dot;       // 1 on (default), 2 off
-    int ell_alternate;      // 0 automatic (streams that do not fit the Infinity Cache), 1 on, 2 off
+    int ell_alternate;      // 0 automatic (streams that do not fit the Infinity Cache, ell_nt 1-3), 1 on, 2 off
     int row_split;          // panel form: no row block of pass 2 straddles this row (0 = none)
     int col_map;            // host builder: 1 per-thread column look-up arrays where they fit (default), 2 sorted lists + binary search
     int er_nt;              // panel form, pass 2 reads past the caches: 0 by size, 1 always, 2 never
-    int ell_nt;             // window kernel, value stream past the caches: 3 all but the end of an alternating walk (default), 1 every slab, 2 never
+    int ell_nt;             // window kernel, value stream past the caches: 4 (default) / 5 all but a fixed set of slabs that stays in the Infinity
+                            // Cache (spread over a segment / its first slabs), 3 all but the end of an alternating walk, 1 every slab, 2 never
+    int ell_keep;           // ell_nt 4 / 5: the share of the slabs in that set, per mille; 0 = from the cache's size (ehyb_hip.hip)
 };
 Config resolve_config(const ehyb_config* cfg);
 

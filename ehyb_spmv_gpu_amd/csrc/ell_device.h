@@ -43,10 +43,28 @@ struct EllArgs {
     int probe_n;
     // The value stream is read ONCE per multiply: loaded with the non-temporal hint it streams past the caches, which then hold what is read
     // again (column words shared by lanes, lane maps, x) -- 0.69 -> 0.78 of the peak for a launch that walks first to last, every entry stored
-    // 1126 -> 1290 GFLOP/s (profiles/r04_nt_hints_ab.txt).  nt_slabs: the slabs at walk positions below nt_slabs/1024 of a segment are read
-    // that way; the rest, the END of the walk, with plain loads -- what an alternating walk wants the Infinity Cache to keep for the next launch.
-    int nt_slabs;
+    // 1126 -> 1290 GFLOP/s (profiles/r04_nt_hints_ab.txt).  The slabs that ell_slab_resident(.., keep1024, keep_shape) marks are read with
+    // plain loads instead, so that the 256 MB Infinity Cache keeps them for the next launch; every other slab with the hint.
+    int keep1024;    // share of a segment's slabs read with plain loads, in 1/1024 (0 = none, 1024 = all)
+    int keep_shape;  // ELL_KEEP_*: which slabs those are
 };
+
+// Which slabs of a segment are read with plain loads (and so stay in the Infinity Cache), the rest with the non-temporal hint.
+//   SPREAD, BLOCK: a FIXED set, a function of the slab's index in its segment -- the same slabs in every launch, whatever the walk
+//     direction, so that after the first launch nothing but x, y and the column words allocates in the cache and nothing evicts the set.
+//     SPREAD picks evenly over the index (Bresenham; the slabs of a partition are sorted by length, so evenly over the bytes too), BLOCK
+//     the first keep1024 / 1024 of the segment.  Both mark floor(n * keep1024 / 1024) slabs, never more than the share asked for.
+//   WALK_END (cfg.ell_nt = 3, rounds 4-5): a function of the walk POSITION -- the last keep1024 / 1024 of every walk, which the
+//     next launch of an alternating plan reads first.
+enum { ELL_KEEP_WALK_END = 0, ELL_KEEP_SPREAD = 1, ELL_KEEP_BLOCK = 2 };
+
+// pos: SPREAD, BLOCK the slab's index in its segment of n slabs; WALK_END its position in the walk
+__host__ __device__ inline bool ell_slab_resident(int pos, int n, int keep1024, int shape)
+{
+    if (shape == ELL_KEEP_SPREAD) return (((long long)(pos + 1) * keep1024) >> 10) != (((long long)pos * keep1024) >> 10);
+    if (shape == ELL_KEEP_BLOCK) return pos < (int)(((long long)n * keep1024) >> 10);
+    return pos >= (int)(((long long)n * (1024 - keep1024) + 1023) >> 10);
+}
 
 // Workgroups are handed to the 8 XCDs round robin (b mod 8).  With this map XCD k gets the k-th
 // contiguous eighth of the items: neighbouring partitions, whose halo columns are each other's
@@ -327,12 +345,12 @@ __device__ __forceinline__ void ell_segment(const EllArgs& A, long long ldx, lon
         g == A.items[2 * item_of_block(A.item_map, A.xcd_map)].x)
         A.stamps[4 * blockIdx.x + 1] = wall_clock64();
     int s = sb + wave;  // (logical position in the segment's walk; the slab it stands for depends on the direction)
-    const int nt_end = sb + (int)(((long long)(se - sb) * A.nt_slabs + 1023) >> 10);   // walk positions below it: value stream past the caches
     while (s < se) {
-        if (s < nt_end)
-            ell_slab<K, INLINE_ER, SYM, true>(A, ldx, ldy, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
+        const int slab = A.reverse ? se - 1 - (s - sb) : s;
+        if (ell_slab_resident((A.keep_shape == ELL_KEEP_WALK_END ? s : slab) - sb, se - sb, A.keep1024, A.keep_shape))
+            ell_slab<K, INLINE_ER, SYM, false>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);
         else
-            ell_slab<K, INLINE_ER, SYM, false>(A, ldx, ldy, win, yacc, A.reverse ? se - 1 - (s - sb) : s, base, pe, lane, xy);
+            ell_slab<K, INLINE_ER, SYM, true>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);   // value stream past the caches
         if (DYN) {
             int nx = 0;
             if (lane == 0) nx = atomicAdd(next_slab, 1);

@@ -8,6 +8,7 @@
 // interchange format.  A file whose magic, version, key or sizes do not fit is rejected.
 #include "ehyb_internal.h"
 
+#include <cstddef>
 #include <cstdio>
 #include <memory>
 #include <new>
@@ -38,6 +39,16 @@ template <class T>
 bool get(FILE* f, T& v)
 {
     return fread(&v, sizeof(T), 1, f) == 1;
+}
+// The configuration as the files hold it: the fields up to ell_nt.  Knobs added since (ell_keep: how a launch reads, nothing of
+// the layout) stay out, so that files written before them remain valid; a loaded plan has them at 0 = automatic.
+constexpr size_t kCfgFileBytes = offsetof(Config, ell_keep);
+static_assert(kCfgFileBytes + sizeof(int) == sizeof(Config), "fields added to Config go behind ell_keep and stay out of plan files");
+bool put_cfg(FILE* f, const Config& c) { return fwrite(&c, kCfgFileBytes, 1, f) == 1; }
+bool get_cfg(FILE* f, Config& c)
+{
+    c.ell_keep = 0;
+    return fread(&c, kCfgFileBytes, 1, f) == 1;
 }
 template <class T, class A>
 bool put_vec(FILE* f, const std::vector<T, A>& v)
@@ -153,7 +164,7 @@ int ehyb_plan_save(const ehyb_plan* plan, const int* reorder_list, uint64_t matr
     memcpy(s.er_bins, H.er_bins, sizeof s.er_bins);
     std::vector<int32_t> perm;
     if (reorder_list) perm.assign(reorder_list, reorder_list + H.n_cols);
-    bool ok = fwrite(kMagic, 8, 1, f.get()) == 1 && put(f.get(), matrix_key) && put(f.get(), plan->cfg) && put(f.get(), s) &&
+    bool ok = fwrite(kMagic, 8, 1, f.get()) == 1 && put(f.get(), matrix_key) && put_cfg(f.get(), plan->cfg) && put(f.get(), s) &&
               put(f.get(), H.stats) && put_vec(f.get(), perm) &&
               each_array(H, [&](auto& v) { return put_vec(f.get(), v); }) && fwrite(kEnd, 8, 1, f.get()) == 1;
     FILE* raw = f.release();
@@ -186,7 +197,7 @@ int ehyb_plan_load(const char* path, uint64_t expect_key, ehyb_plan** plan, int*
     std::vector<int32_t> perm;
     const uint64_t limit = 1ull << 36;  // sanity bound for any array count
     try {
-        bool ok = get(f.get(), P->cfg) && get(f.get(), s) && get(f.get(), H.stats) && get_vec(f.get(), perm, limit) &&
+        bool ok = get_cfg(f.get(), P->cfg) && get(f.get(), s) && get(f.get(), H.stats) && get_vec(f.get(), perm, limit) &&
                   each_array(H, [&](auto& v) { return get_vec(f.get(), v, limit); });
         char end[8];
         ok = ok && fread(end, 8, 1, f.get()) == 1 && memcmp(end, kEnd, 8) == 0;

@@ -372,6 +372,14 @@ class Plan:
         _check(self.lib.ehyb_plan_stats(self.h, C.byref(st)), "ehyb_plan_stats")
         return st.as_dict()
 
+    @property
+    def resident_bytes(self):
+        """ehyb_plan_resident_bytes: bytes of the window kernel's value stream read with plain loads (kept in the Infinity Cache)"""
+        b = int(self.lib.ehyb_plan_resident_bytes(self.h))
+        if b < 0:
+            raise EhybError(b, "ehyb_plan_resident_bytes")
+        return b
+
     def array(self, name):
         which, dtype = ARRAYS[name]
         p = C.c_void_p()

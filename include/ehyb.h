@@ -195,7 +195,9 @@ typedef struct ehyb_config {
                               launch starts with what the one before it left in the 256 MB Infinity Cache (a solver multiplies with
                               the same matrix again and again): 0 = where the plan's stream is larger than that cache and at most
                               8 GB (a smaller one stays resident anyway, of a far larger one the cache holds too little to pay for
-                              the walk from the short slabs up), 1 = always, 2 = never (always first to last).  With more work items
+                              the walk from the short slabs up) and cfg.ell_nt is 1, 2 or 3 -- the fixed set of ell_nt = 4 / 5 is the
+                              same for both directions, and such a plan measured 1-1.5 us faster first to last --, 1 = always,
+                              2 = never (always first to last).  With more work items
                               than resident workgroups the items are taken from the far end as well.  Pass 1 of the panel
                               residual alternates the same way                                                        */
     int32_t row_split;     /* panel form, multi-GPU: a row block of pass 2 never straddles this row (0 = none).  The rows from it on
@@ -208,11 +210,17 @@ typedef struct ehyb_config {
                               the same array for array                                                                  */
     int32_t er_nt;         /* panel form, pass 2: the partial sums and their row words are read with the non-temporal hint (past the caches):
                               0 = where they are more than half the 256 MB Infinity Cache (10 B per partial sum), 1 = always, 2 = never (A/B) */
-    int32_t ell_nt;        /* the window kernel reads its value stream (read once per multiply) with the non-temporal hint, past the caches:
-                              0/3 = every slab but the END of an alternating walk (the share of the stream the Infinity Cache can hold
-                              is read with plain loads, to be found there by the next launch; every slab where the walk does not
-                              alternate; none where the whole stream fits that cache), 1 = every slab, 2 = never (rounds 1-3)      */
-    int32_t reserved[21];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
+    int32_t ell_nt;        /* the window kernel reads its value stream (read once per multiply) with the non-temporal hint, past the caches,
+                              all but a share that the 256 MB Infinity Cache is to keep for the next multiply (none where the whole stream
+                              fits that cache: plain loads throughout).  0/4 = all but a FIXED set of slabs, the same in every launch
+                              whatever its walk direction, spread evenly over the slabs of every partition: after the first launch the set
+                              is resident and nothing evicts it; 5 = the same with the set at the start of every partition (A/B);
+                              3 = all but the END of an alternating walk, which the next launch reads first (round 4; every slab where
+                              the walk does not alternate); 1 = every slab, 2 = never (rounds 1-3).  The result never depends on it   */
+    int32_t ell_keep;      /* ell_nt = 4 / 5: the share of a partition's slabs in that set, per mille (1..1000).  0 = automatic: what the
+                              256 MiB cache holds beside the bytes the launch re-reads and writes with plain accesses (column words,
+                              lane maps, slab records, x, y), times a safety factor; all of a stream that fits whole       */
+    int32_t reserved[20];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
 } ehyb_config;
 
 void ehyb_config_default(ehyb_config* cfg);
@@ -349,6 +357,14 @@ typedef struct ehyb_stats {
                                and read by its second, per multiply                                    */
 } ehyb_stats;
 int ehyb_plan_stats(const ehyb_plan* plan, ehyb_stats* out);
+/* Bytes of the window kernel's value stream that the plan reads with plain loads, i.e. leaves in the Infinity Cache (cfg.ell_nt,
+ * cfg.ell_keep; for ell_nt = 3 the walk first to last); -1 = null plan.  Host arithmetic over EHYB_ARR_SLAB_META. */
+int64_t ehyb_plan_resident_bytes(const ehyb_plan* plan);
+/* The rule behind it, as the kernel applies it: is slab `pos` of a segment of `n` slabs in the set, for a share of
+ * keep1024 / 1024 and shape 1 = spread (cfg.ell_nt = 4), 2 = block (5); 0 = the end of a walk (3), pos = the walk position. */
+int ehyb_ell_slab_resident(int pos, int n, int keep1024, int shape);
+/* The automatic share (cfg.ell_keep = 0) in 1/1024 for a value stream of value_bytes beside plain_bytes of other traffic. */
+int ehyb_ell_auto_keep1024(int64_t value_bytes, int64_t plain_bytes);
 
 /* Read-only views of the host layout, for invariant tests (i-iv). */
 enum {
@@ -462,8 +478,10 @@ int ehyb_spmv_walk(ehyb_plan* plan, const double* x_dev, double* y_dev, void* st
 /*
  * `multiplies` back-to-back multiplies y = A x captured into a hipGraph with the directions alternating explicitly inside the run;
  * for an odd count (1: the solver that launches one multiply per iteration) TWO executables are captured, beginning first-to-last
- * and last-to-first, and ehyb_graph_launch replays them in turn -- the alternation survives the capture.  x and y are bound at
- * capture.  One launch at a time per graph object.
+ * and last-to-first, and ehyb_graph_launch replays them in turn -- the alternation survives the capture.  A plan that multiplies in
+ * window launches alone and keeps a fixed set of slabs in the Infinity Cache (cfg.ell_nt = 0/4/5, cfg.ell_alternate != 1) gains nothing
+ * from a direction: every captured multiply walks first to last and one executable serves.  x and y are bound at capture.  One launch
+ * at a time per graph object.
  */
 typedef struct ehyb_graph ehyb_graph;
 int ehyb_spmv_graph_create(ehyb_plan* plan, const double* x_dev, double* y_dev, int multiplies, ehyb_graph** graph);
