@@ -646,7 +646,7 @@ int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y,
                         unsigned long long* stamps, double* xy_out)
 {
     const HostLayout& H = P->host;
-    const int n_items = (int)(H.items.size() / 8);
+    const int n_items = (int)(H.items.size() / kItemWords);
     if (n_items == 0 || H.direct) return EHYB_OK;  // direct shape: the row-segment kernel does everything
     if (H.pb_assign && H.segs.empty()) return EHYB_OK;  // no partition kept its window: pass 2 of the panel residual assigns every row
     // cfg.ell_variant: 0/1 = LDS slab counter (default), 3 = static round-robin (A/B arm, tools/sweep.py --variants; one vector only)
@@ -682,7 +682,7 @@ static int launch_ell(ehyb_plan* P, const double* x, double* y, hipStream_t st, 
 int ehyb::spmv_xy_partials(const ehyb_plan* P)
 {
     const HostLayout& H = P->host;
-    const int n_items = (int)(H.items.size() / 8);
+    const int n_items = (int)(H.items.size() / kItemWords);
     if (!P->uploaded || H.direct || n_items == 0 || H.pb_assign || P->cfg.window_mode != EHYB_WINDOW_HALO) return 0;
     if (H.stats.nnz_er > 0 && !H.inline_er) return 0;
     return n_items;
@@ -796,14 +796,6 @@ static int launch_er(ehyb_plan* P, const double* x, double* y, hipStream_t st)
         return launch_panel(P, x, y, st, 0, 3);  // (probe arms only through ehyb_debug_panel_times)
     return launch_er_csr(P, x, 0, y, 0, 1, st);
 }
-
-// Where the residual runs (decided by the layout builder, HostLayout::inline_er).  Its own launch
-// costs a second ~8 us kernel boundary but gives the residual thousands of independent blocks;
-// inline -- every ELL lane adds its row's few residual entries before writing y -- costs nothing
-// when the residual is tiny and would serialise a divergent per-lane loop when it is not.
-// fuse_er: 1 = always inline, 2 = never, 0 = automatic: inline iff the residual holds < 0.2 % of
-// the entries.  Multi-GPU plans keep the phases apart (phase 1 reads only the rank's x segment).
-static bool fuse_residual(const ehyb_plan* P) { return P->host.inline_er; }
 
 template <class T, class A>
 static int upload(T** dst, const std::vector<T, A>& src)
@@ -958,7 +950,7 @@ int ehyb_debug_ell_stamps_probe(ehyb_plan* P, const double* x, double* y, unsign
 int ehyb_debug_ell_stamps(ehyb_plan* P, const double* x, double* y, unsigned long long* out_host)
 {
     if (!P || !P->uploaded || !out_host) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_ell_stamps: bad arguments");
-    const int n_items = (int)(P->host.items.size() / 8);
+    const int n_items = (int)(P->host.items.size() / kItemWords);
     unsigned long long* d = nullptr;
     HIP_TRY(hipMalloc((void**)&d, (size_t)n_items * 32));
     HIP_TRY(hipMemset(d, 0, (size_t)n_items * 32));
@@ -994,7 +986,7 @@ int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* s
     if (span_before_us) *span_before_us = 0;
     if (span_after_us) *span_after_us = 0;
     const HostLayout& H = P->host;
-    const int n_items = (int)(H.items.size() / 8);
+    const int n_items = (int)(H.items.size() / kItemWords);
     const int resident = kNumCU * std::max(1, P->cfg.items_per_cu);
     // one resident round only: with more items than slots the later ones start wherever a CU falls free
     if (H.direct || n_items < 16 || n_items > resident || (H.pb_assign && H.segs.empty())) return EHYB_OK;
@@ -1005,13 +997,16 @@ int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* s
     // cost of an item: the bytes its slabs stream (values 16 B per lane and pair + column words) + its windows
     std::vector<double> cost((size_t)n_items, 0.0);
     for (int i = 0; i < n_items; ++i) {
-        const int32_t* rec = &H.items[(size_t)i * 8];
+        const int32_t* rec = &H.items[(size_t)i * kItemWords];
         double c = 0;
-        for (int s = rec[2]; s < rec[3]; ++s) {
-            const uint32_t w = H.slab_meta[(size_t)s * 4 + 3];
-            c += (double)(w >> 16) * (1024.0 + 4.0 * ((w & 0x3Fu) + 1));
+        for (int s = rec[ITEM_SLAB_BEGIN]; s < rec[ITEM_SLAB_END]; ++s) {
+            const SlabShape shape = unpack_slab_shape(H.slab_meta[(size_t)s * kSlabWords + SLAB_SHAPE]);
+            c += (double)shape.pairs * (1024.0 + 4.0 * shape.groups);
         }
-        for (int g = rec[0]; g < rec[1]; ++g) c += 8.0 * (H.segs[(size_t)g * 8 + 6] + H.segs[(size_t)g * 8 + 3]) + 16.0 * (H.segs[(size_t)g * 8 + 5] - H.segs[(size_t)g * 8 + 4]);
+        for (int g = rec[ITEM_SEG_BEGIN]; g < rec[ITEM_SEG_END]; ++g) {
+            const int32_t* seg = &H.segs[(size_t)g * kSegWords];
+            c += 8.0 * (seg[SEG_WIN_LEN] + seg[SEG_HALO_COUNT]) + 16.0 * (seg[SEG_ROW_END] - seg[SEG_ROW_BEGIN]);
+        }
         cost[(size_t)i] = c + 1.0;
     }
     auto measure = [&](std::vector<double>* dur, std::vector<int>* xcc, double* span_us) -> int {
@@ -1211,7 +1206,7 @@ int ehyb_spmv_phase(ehyb_plan* P, const double* x, double* y, void* stream, int 
     if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv: plan not uploaded (no CPU fallback exists)");
     hipStream_t st = (hipStream_t)stream;
     int rc = EHYB_OK;
-    if (phase == 0 && fuse_residual(P)) return launch_ell(P, x, y, st, true);  // one launch
+    if (phase == 0 && P->host.inline_er) return launch_ell(P, x, y, st, true);  // one launch
     if (P->host.direct && phase != 0) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_phase: a plan in the direct shape (small matrix) has no phases");
     if (phase == 0 || phase == 1) rc = launch_ell(P, x, y, st, false);
     if (rc == EHYB_OK && (phase == 0 || phase == 2)) rc = launch_er(P, x, y, st);
@@ -1245,10 +1240,11 @@ int64_t ehyb_plan_resident_bytes(const ehyb_plan* P)
     int keep1024 = 0, shape = 0;
     ell_keep_rule(P, ell_alternates(P), &keep1024, &shape);
     int64_t bytes = 0;
-    for (size_t sg = 0; sg < H.segs.size(); sg += 8) {
-        const int sb = H.segs[sg + 1], se = H.segs[sg + 2];
+    for (size_t sg = 0; sg < H.segs.size(); sg += kSegWords) {
+        const int sb = H.segs[sg + SEG_SLAB_BEGIN], se = H.segs[sg + SEG_SLAB_END];
         for (int s = sb; s < se; ++s)   // (WALK_END: the walk first to last)
-            if (ell_slab_resident(s - sb, se - sb, keep1024, shape)) bytes += (int64_t)(H.slab_meta[(size_t)s * 4 + 3] >> 16) * kSlabRows * 16;
+            if (ell_slab_resident(s - sb, se - sb, keep1024, shape))
+                bytes += (int64_t)unpack_slab_shape(H.slab_meta[(size_t)s * kSlabWords + SLAB_SHAPE]).pairs * kSlabRows * 16;
     }
     return bytes;
 }
@@ -1327,7 +1323,7 @@ int ehyb_spmv_part(ehyb_plan* P, const double* x, double* y, void* stream, int s
     int n_segs = 1;
     (void)ehyb_plan_col_segs(P, &n_segs);
     if (seg_begin < 0 || seg_end > n_segs || seg_begin > seg_end) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_spmv_part: column segments [%d, %d) of %d", seg_begin, seg_end, n_segs);
-    if (H.direct || fuse_residual(P)) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: this plan multiplies in one launch (direct shape or inline residual): it has no parts");
+    if (H.direct || H.inline_er) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: this plan multiplies in one launch (direct shape or inline residual): it has no parts");
     hipStream_t st = (hipStream_t)stream;
     int rc = EHYB_OK;
     if (flags & EHYB_PART_FIRST) rc = launch_ell(P, x, y, st, false);
@@ -1499,7 +1495,7 @@ int ehyb_spmv_bench(ehyb_plan* P, const double* x, double* y, void* stream, int 
         std::vector<hipEvent_t>& ev = evs.v;
         for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
         for (int i = 0; i < n; ++i) {
-            const bool fused = fuse_residual(P);
+            const bool fused = P->host.inline_er;
             HIP_TRY(hipEventRecord(ev[3 * i + 0], st));
             if ((rc = launch_ell(P, x, y, st, fused)) != EHYB_OK) return rc;
             HIP_TRY(hipEventRecord(ev[3 * i + 1], st));

@@ -150,12 +150,12 @@ struct HostLayout {
     BigVec<uint32_t> ell_col;
     std::vector<uint32_t> slab_col_ptr;  // [n_slabs+1] prefix of pairs*groups
     std::vector<uint8_t> lane_group;     // [n_slabs*64]
-    std::vector<uint32_t> slab_meta;     // [n_slabs*4] {pair_ptr, col_ptr, first row, pairs<<16 | er_pairs<<8 | groups-1}
+    std::vector<uint32_t> slab_meta;     // [n_slabs*kSlabWords] slab records (SlabField, SlabShape below)
 
-    // work items {seg_begin, seg_end, slab_begin, slab_end, er_begin, er_b64, er_b16, er_end}: a run of
-    // slabs of (nearly) equal cost; it is cut into segments where it crosses a partition boundary
+    // work items (kItemWords each, ItemField below): a run of slabs of (nearly) equal cost; it is cut into
+    // segments where it crosses a partition boundary
     std::vector<int32_t> items;
-    // segments {partition, slab_begin, slab_end, halo_count, first row, end row, win_len, halo_begin}
+    // segments (kSegWords each, SegField below): the slabs of an item that share one partition's window
     std::vector<int32_t> segs;
 
     // residual (CSR segments sorted by length, descending)
@@ -234,6 +234,28 @@ struct HostLayout {
     ehyb_stats stats{};
 };
 
+// Named views of the packed records above, host side (the kernels decode the same words in ell_device.h).
+// The 16-byte slab record the window kernel reads:
+constexpr int kSlabWords = 4;
+enum SlabField { SLAB_PAIR_PTR, SLAB_COL_PTR, SLAB_ROW, SLAB_SHAPE };
+// its word SLAB_SHAPE = pairs << 16 | er_pairs << 8 | relative << 7 | groups - 1
+struct SlabShape {
+    uint32_t pairs;     // ELL pairs per lane (the slab's width / 2)
+    uint32_t er_pairs;  // inline residual pairs per lane behind them (HostLayout::inline_er)
+    uint32_t groups;    // groups of lanes that share their column words, 1..64
+    bool relative;      // the columns are stored relative to the lane's own row
+};
+inline uint32_t pack_slab_shape(uint32_t pairs, uint32_t er_pairs, bool relative, uint32_t groups)
+{
+    return (pairs << 16) | (er_pairs << 8) | (relative ? 0x80u : 0u) | (groups - 1);
+}
+inline SlabShape unpack_slab_shape(uint32_t w) { return {w >> 16, (w >> 8) & 0xFF, (w & 0x3F) + 1, (w & 0x80u) != 0}; }
+// work item: its segments, its slabs, and its residual segments by length bin (64 lanes per segment for >= 128 entries, 16 for 17..127, 4 below)
+constexpr int kItemWords = 8;
+enum ItemField { ITEM_SEG_BEGIN, ITEM_SEG_END, ITEM_SLAB_BEGIN, ITEM_SLAB_END, ITEM_ER_BEGIN, ITEM_ER_B64, ITEM_ER_B16, ITEM_ER_END };
+constexpr int kSegWords = 8;
+enum SegField { SEG_PART, SEG_SLAB_BEGIN, SEG_SLAB_END, SEG_HALO_COUNT, SEG_ROW_BEGIN, SEG_ROW_END, SEG_WIN_LEN, SEG_HALO_BEGIN };
+
 // The host's share of the panel builder (er_panel.cpp), common to the host and the device route
 struct PanelGeometry {
     int W = 0;
@@ -248,11 +270,19 @@ int64_t panel_pass1_items(const Config& cfg, const PanelGeometry& G, const std::
 void panel_finish(const PanelGeometry& G, const std::vector<int64_t>& rb_count, int64_t staged, int64_t padded, int64_t n_pieces, int64_t n_jumps,
                   HostLayout* L);
 
-// defer_panel: a panel form that is certain (cfg.er_mode = 2, or partitions given up) is left to the device --
-// out->deferred.pending, no CSR segments either; the views of out->deferred may point into *m
-int build_layout(const matrixCOO* m, int row_begin, int row_end, const Config& cfg, HostLayout* out,
-                 const std::vector<uint8_t>* part_to_er = nullptr, int local_lo = -1, int local_hi = -1, bool defer_panel = false,
-                 bool stats_only = false);  // stats_only: stop after the windows and slab widths (plan.cpp's sample)
+// What a caller of build_layout may ask for beyond the plain layout of the rows
+struct LayoutOptions {
+    // partitions (by their index in the layout's own partition list) whose rows go to the residual whole (plan.cpp decides)
+    const std::vector<uint8_t>* part_to_er = nullptr;
+    // multi-GPU: the rank's own columns, where the rows laid out are only a sample of the rank's (-1: the rows themselves)
+    int local_lo = -1, local_hi = -1;
+    // a panel form that is certain (cfg.er_mode = 2, or partitions given up) is left to the device --
+    // out->deferred.pending, no CSR segments either; the views of out->deferred may point into *m
+    bool defer_panel = false;
+    // stop after the windows and slab widths (plan.cpp's sample): out->stats holds the entry counts, nothing is filled
+    bool stats_only = false;
+};
+int build_layout(const matrixCOO* m, int row_begin, int row_end, const Config& cfg, HostLayout* out, const LayoutOptions& opt = LayoutOptions());
 int create_host_plan(const matrixCOO* m, int row_begin, int row_end, const ehyb_config* cfg, int n_col_segs, const int* col_seg_first,
                      bool defer_panel, ehyb_plan** plan);                         // plan.cpp
 int spmv_xy_partials(const ehyb_plan* P);            // ehyb_hip.hip: y = A x with x . y on the side -- partials it leaves, 0 = not this plan

@@ -30,8 +30,9 @@ int windows_that_do_not_pay(const HostLayout& H, int pct, std::vector<uint8_t>* 
     to_er->assign((size_t)np, 0);
     std::vector<int64_t> stored((size_t)np, 0), words((size_t)np, 0);
     for (size_t s = 0; s < H.slab_part.size(); ++s) {
-        stored[H.slab_part[s]] += (int64_t)(H.slab_meta[4 * s + 3] >> 16) * 2 * kSlabRows;
-        words[H.slab_part[s]] += (int64_t)(H.slab_meta[4 * s + 3] >> 16) * ((H.slab_meta[4 * s + 3] & 0x3F) + 1);
+        const SlabShape shape = unpack_slab_shape(H.slab_meta[kSlabWords * s + SLAB_SHAPE]);
+        stored[H.slab_part[s]] += (int64_t)shape.pairs * 2 * kSlabRows;
+        words[H.slab_part[s]] += (int64_t)shape.pairs * shape.groups;
     }
     int count = 0;
     *entries_moved = 0;
@@ -95,6 +96,9 @@ static bool windows_will_not_pay(const matrixCOO* m, int row_begin, int row_end,
     std::vector<int64_t> s_nnz(pick.size(), 0), s_kept(pick.size(), 0);
     bool failed = false;
     quiet.host_threads = 1;
+    LayoutOptions sample;  // one partition of the plan's rows: the windows and their cost, nothing filled
+    sample.local_lo = row_begin, sample.local_hi = row_end;
+    sample.stats_only = true;
     {
         OmpScope omp_scope(cfg.host_threads);
 #pragma omp parallel for schedule(dynamic, 1)
@@ -103,7 +107,7 @@ static bool windows_will_not_pay(const matrixCOO* m, int row_begin, int row_end,
             HostLayout S;
             int rc;
             try {
-                rc = build_layout(m, m->partBoundary[p], m->partBoundary[p + 1], quiet, &S, nullptr, row_begin, row_end, false, true);
+                rc = build_layout(m, m->partBoundary[p], m->partBoundary[p + 1], quiet, &S, sample);
             } catch (const std::bad_alloc&) {
                 rc = EHYB_ERR_ALLOC;
             }
@@ -209,6 +213,8 @@ int ehyb::create_host_plan(const matrixCOO* m, int row_begin, int row_end, const
     P->cfg = resolve_config(cfg);
     if (n_col_segs > 0) P->host.col_seg_first.assign(col_seg_first, col_seg_first + n_col_segs + 1);
     int rc;
+    LayoutOptions plain, given_up;  // the layout of the rows as they are / with the partitions of given_up.part_to_er in the residual
+    plain.defer_panel = given_up.defer_panel = defer_panel;
     try {
         bool decided = false;
         if (windows_will_not_pay(m, row_begin, row_end, P->cfg)) {
@@ -219,7 +225,8 @@ int ehyb::create_host_plan(const matrixCOO* m, int row_begin, int row_end, const
             // (the layout's own partition list may be longer than the caller's -- partitions cut down to the window --
             // so the flags cover any index: every partition goes)
             all.assign((size_t)(row_end - row_begin) / kSlabRows + (size_t)m->nParts + 64, 1);
-            const int rc0 = build_layout(m, row_begin, row_end, P->cfg, &direct_to, &all, -1, -1, defer_panel);
+            given_up.part_to_er = &all;
+            const int rc0 = build_layout(m, row_begin, row_end, P->cfg, &direct_to, given_up);
             if (rc0 == EHYB_OK && (direct_to.er_panel || direct_to.deferred.pending)) {
                 P->host = std::move(direct_to);
                 decided = true;
@@ -228,7 +235,7 @@ int ehyb::create_host_plan(const matrixCOO* m, int row_begin, int row_end, const
             }
         }
         // (the first build of the two-build route needs no panel form to judge the windows: deferred as well when certain)
-        rc = decided ? EHYB_OK : build_layout(m, row_begin, row_end, P->cfg, &P->host, nullptr, -1, -1, defer_panel);
+        rc = decided ? EHYB_OK : build_layout(m, row_begin, row_end, P->cfg, &P->host, plain);
         // Where the residual runs in panel form (a large residual without locality: R-MAT), a partition
         // whose window does not pay is better off in the residual whole: built a second time with those.
         if (!decided && rc == EHYB_OK && (P->host.er_panel || P->host.deferred.pending) && !P->host.sym && P->cfg.er_mode != 1 && P->cfg.ell_prune != 2) {
@@ -253,7 +260,8 @@ int ehyb::create_host_plan(const matrixCOO* m, int row_begin, int row_end, const
                 again.col_seg_first = P->host.col_seg_first;
                 int rc2;
                 try {
-                    rc2 = build_layout(m, row_begin, row_end, P->cfg, &again, &to_er, -1, -1, defer_panel);
+                    given_up.part_to_er = &to_er;
+                    rc2 = build_layout(m, row_begin, row_end, P->cfg, &again, given_up);
                 } catch (const std::bad_alloc&) {
                     rc2 = EHYB_ERR_ALLOC;
                 }

@@ -220,9 +220,9 @@ int ehyb_plan_load(const char* path, uint64_t expect_key, ehyb_plan** plan, int*
         H.part_boundary.size() == (size_t)H.n_parts + 1 && H.win_len.size() == (size_t)H.n_parts &&
         H.halo_ptr.size() == (size_t)H.n_parts + 1 && H.halo_cols.size() == (size_t)H.halo_ptr.back() &&
         H.slab_pair_ptr.size() == nslab + 1 && H.slab_col_ptr.size() == nslab + 1 && H.slab_part.size() == nslab &&
-        H.slab_meta.size() == nslab * 4 && H.lane_group.size() == nslab * kSlabRows &&
+        H.slab_meta.size() == nslab * kSlabWords && H.lane_group.size() == nslab * kSlabRows &&
         H.ell_val.size() == (size_t)H.slab_pair_ptr.back() * 2 * kSlabRows && H.ell_col.size() == (size_t)H.slab_col_ptr.back() &&
-        H.items.size() % 8 == 0 && H.segs.size() % 8 == 0 && H.er_seg_ptr.size() == nseg + 1 &&
+        H.items.size() % kItemWords == 0 && H.segs.size() % kSegWords == 0 && H.er_seg_ptr.size() == nseg + 1 &&
         H.er_col.size() == (size_t)H.er_seg_ptr.back() && H.er_val.size() == H.er_col.size() && H.er_blocks.size() % 4 == 0 && (H.sym ? H.slab_lrow.size() == nslab * kSlabRows : H.slab_lrow.empty()) &&
         H.lds_doubles > 0 && H.lds_doubles <= EHYB_LDS_MAX_DOUBLES && (perm.empty() || perm.size() == (size_t)H.n_cols) &&
         panel_consistent(H);
