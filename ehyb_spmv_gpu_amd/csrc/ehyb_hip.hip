@@ -30,7 +30,9 @@
 //                    not carried inline (the reference skips it after the first launch: SURVEY 8
 //                    a-10 item 1); it is also phase 2 of the multi-GPU multiply (all remote columns).
 //                    ehyb_er_k_kernel: the same for K = 2, 3, 4 columns.
-//   launch_window / launch_er_csr  the one launch path of each family, for every K.
+//   ehyb_pb_scale_kernel / ehyb_pb_reduce_kernel  the two passes of the panel-form residual (below); ehyb_pb_scale_k_kernel /
+//                    ehyb_pb_reduce_k_kernel: the same bodies for K = 2, 3, 4 columns.
+//   launch_window / launch_er_csr / launch_panel  the one launch path of each family, for every K.
 // No MFMA: 2 flops per 5.8-10 streamed bytes, HBM-bound.
 //
 // Arms tried and dropped (measurements in DESIGN.md 3.1): software-pipelined slab walk with ping-pong
@@ -151,6 +153,112 @@ __device__ __forceinline__ double piece_sums(double prod, unsigned long long hea
     return v;
 }
 
+// ---- the same for NV columns per entry (ehyb_spmm on a panel-form plan): the flags, and with them every branch, belong to the
+// chunk and are worked out once; only the sums are per column.
+template <int CTRL, int ROW_MASK, int NV>
+__device__ __forceinline__ void seg_scan_step_n(double (&v)[NV], uint32_t& f)
+{
+    const uint32_t fp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, CTRL, ROW_MASK, 0xf, true);
+#pragma unroll
+    for (int n = 0; n < NV; ++n) {
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v[n]), CTRL, ROW_MASK, 0xf, true);
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v[n]), CTRL, ROW_MASK, 0xf, true);
+        v[n] += f ? 0.0 : __hiloint2double(hi, lo);
+    }
+    f |= fp;
+}
+
+template <int CTRL, int ROW_MASK, int NV>
+__device__ __forceinline__ void wave_sum_step_n(double (&v)[NV])
+{
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+        v[n] += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v[n]), CTRL, ROW_MASK, 0xf, true),
+                                 __builtin_amdgcn_update_dpp(0, __double2loint(v[n]), CTRL, ROW_MASK, 0xf, true));
+}
+
+template <int NV>
+__device__ __forceinline__ void piece_sums_n(double (&v)[NV], unsigned long long heads, bool head)
+{
+    const unsigned long long nh = ~heads;
+    if (nh == 0ull) return;
+    if (heads == 1ull) {  // one piece: plain sums over the wave, lane 63 holds them
+        wave_sum_step_n<0x111, 0xf>(v);
+        wave_sum_step_n<0x112, 0xf>(v);
+        wave_sum_step_n<0x114, 0xf>(v);
+        wave_sum_step_n<0x118, 0xf>(v);
+        wave_sum_step_n<0x142, 0xa>(v);
+        wave_sum_step_n<0x143, 0xc>(v);
+        return;
+    }
+    uint32_t f = head ? 1u : 0u;
+    seg_scan_step_n<0x111, 0xf>(v, f);
+    const unsigned long long r2 = nh & (nh >> 1);
+    if (r2 != 0ull) {
+        seg_scan_step_n<0x112, 0xf>(v, f);
+        const unsigned long long r4 = r2 & (r2 >> 2);
+        if (r4 != 0ull) {
+            seg_scan_step_n<0x114, 0xf>(v, f);
+            const unsigned long long r8 = r4 & (r4 >> 4);
+            if (r8 != 0ull) seg_scan_step_n<0x118, 0xf>(v, f);
+        }
+    }
+    if (nh & 0x0001000100010000ull) {
+        seg_scan_step_n<0x142, 0xa>(v, f);
+        seg_scan_step_n<0x143, 0xc>(v, f);
+    }
+}
+
+// NV doubles that lie side by side -- the NV values of one column in the interleaved panel image, the NV partial sums of one
+// slot, the NV accumulators of one row: 16-byte accesses where the address allows (NV = 2, 4: base 16-byte aligned, index a
+// multiple of 2), plain doubles for NV = 3.
+template <int NV>
+__device__ __forceinline__ void get_n(const double* p, double (&o)[NV])
+{
+    if constexpr (NV == 2 || NV == 4) {
+#pragma unroll
+        for (int h = 0; h < NV / 2; ++h) {
+            const double2 t = reinterpret_cast<const double2*>(p)[h];
+            o[2 * h] = t.x, o[2 * h + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) o[n] = p[n];
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void put_n(double* p, const double (&v)[NV])
+{
+    if constexpr (NV == 2 || NV == 4) {
+        typedef double dbl2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int h = 0; h < NV / 2; ++h) {
+            const dbl2 t = {v[2 * h], v[2 * h + 1]};
+            reinterpret_cast<dbl2*>(p)[h] = t;
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) p[n] = v[n];
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void get_n_nt(const double* p, double (&o)[NV])
+{
+    if constexpr (NV == 2 || NV == 4) {
+        typedef double dbl2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int h = 0; h < NV / 2; ++h) {
+            const dbl2 t = __builtin_nontemporal_load(reinterpret_cast<const dbl2*>(p) + h);
+            o[2 * h] = t.x, o[2 * h + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) o[n] = __builtin_nontemporal_load(p + n);
+    }
+}
+
 // SUMS_DPP (cfg.er_sums, the default): the products of a piece are added by the register scan above and the piece's
 // LAST lane stores the partial; false = round 2's way: ds_add_f64 into 64 LDS words per wave, the FIRST lane reads the
 // sum back and stores it (kept as the A/B arm: the LDS pipe of a CU was what bound pass 1 -- DESIGN.md 3.2).
@@ -162,7 +270,9 @@ __device__ __forceinline__ double piece_sums(double prod, unsigned long long hea
 // (Round 4 measured an instantiation for TWO 1024-thread workgroups per CU -- 9,728-column panels, KCH = 6, 59 VGPRs, 8 waves per SIMD, one
 // workgroup staging while the other streams: R-MAT 2^22 140 against 132 us, 2^24 665 against 574 us, profiles/r04_d_panel_two_ab.jsonl -- the
 // narrower panels' extra partial sums cost more than the occupancy gives; pass 1 alone ran level.  Removed again.)
-template <int THREADS, bool SUMS_DPP, bool PROBE, int KCH>
+// NV = columns of X per pass (ehyb_spmm): the panel image is interleaved, win[c NV + j] = X[first + c + j ldx], and so are the
+// partial sums, partial[slot NV + j]; the decode of a chunk is done once for the NV products.  NV = 1 is the one-vector kernel.
+template <int THREADS, bool SUMS_DPP, bool PROBE, int KCH, int NV = 1>
 __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, const int4* __restrict__ units,
                                                                 const double* __restrict__ val,
                                                                 const uint16_t* __restrict__ colf,
@@ -170,8 +280,9 @@ __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, co
                                                                 const uint32_t* __restrict__ jump,
                                                                 const double* __restrict__ x,
                                                                 double* __restrict__ partial, int panel_cols, int probe_arg, int xcd_map,
-                                                                int* __restrict__ queue, int n_items, int reverse)
+                                                                int* __restrict__ queue, int n_items, int reverse, long long ldx = 0)
 {
+    static_assert(NV == 1 || (SUMS_DPP && !PROBE), "the K-wide pass 1 has register-scan sums and no probes");
     const int probe = PROBE ? probe_arg : 0;
     // probe (tools/panel_sweep.py, timing diagnostics only, results wrong): 1 no lane sums, 2 no stores,
     // 4 no LDS gather, 8 no panel staging
@@ -189,7 +300,7 @@ __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, co
     // one to leave (queue[128] = workgroups gone) zeroes the counts for the next launch.
     // (the item handed from thread 0 to the workgroup: one word behind the panel and the piece accumulators, in the dynamic
     // allocation -- a static __shared__ word on top of a 160 KiB dynamic limit is refused by hipFuncSetAttribute)
-    int& s_item = *reinterpret_cast<int*>(win + panel_cols + (SUMS_DPP ? 0 : THREADS));
+    int& s_item = *reinterpret_cast<int*>(win + NV * panel_cols + (SUMS_DPP ? 0 : THREADS));
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double* scr = win + panel_cols + 64 * wave;  // this wave's 64 piece accumulators, behind the panel (!SUMS_DPP only)
@@ -245,6 +356,28 @@ __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, co
     staged_x = u.x, staged_n = u.y;
     // stage the panel: all of a thread's loads in flight before the first store (a 64 KiB panel is 16
     // double2 loads per thread; one load per loop trip would pay the memory latency 16 times)
+    if constexpr (NV > 1) {
+        // NV columns of X, interleaved: a thread takes the NV values of a column (each load coalesced along its own column of X,
+        // which may start on an odd double: plain 8-byte loads) and stores them side by side
+        if (!staged_already) {
+            constexpr int UN = NV == 2 ? 8 : 4;  // columns per thread and trip: 16 / 12 / 16 loads in flight
+            const double* __restrict__ xp = x + u.x;
+            for (int i0 = 0; i0 < u.y; i0 += UN * THREADS) {
+                double t[UN][NV];
+#pragma unroll
+                for (int j = 0; j < UN; ++j) {
+                    const int i = i0 + j * THREADS + (int)threadIdx.x;
+#pragma unroll
+                    for (int n = 0; n < NV; ++n) t[j][n] = i < u.y ? xp[i + n * ldx] : 0.0;
+                }
+#pragma unroll
+                for (int j = 0; j < UN; ++j) {
+                    const int i = i0 + j * THREADS + (int)threadIdx.x;
+                    if (i < u.y) put_n<NV>(win + (size_t)i * NV, t[j]);
+                }
+            }
+        }
+    } else
     if (!(probe & 8) && !staged_already) {
         const double2* __restrict__ xp2 = reinterpret_cast<const double2*>(x + u.x);  // panels start on even columns
         double2* win2 = reinterpret_cast<double2*>(win);
@@ -305,7 +438,7 @@ __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, co
         }
         uint32_t slot[K], piece[K];
         unsigned long long hd[K];
-        double xw[K];
+        double xw[K][NV];
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             const bool head = (cw[j] & 0x8000u) != 0, jmp = (cw[j] & 0x4000u) != 0;
@@ -322,13 +455,25 @@ __device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, co
             slot[j] = stores ? base + hc - 1u : 0xFFFFFFFFu;
             hd[j] = heads;
             const uint32_t cl = cw[j] & 0x3FFFu;
-            xw[j] = (probe & 4) ? (double)cl : win[cl];
+            if constexpr (NV == 1)
+                xw[j][0] = (probe & 4) ? (double)cl : win[cl];
+            else
+                get_n<NV>(win + cl * NV, xw[j]);
             cw[j] = (heads == ~0ull ? 1u : 0u) | (head ? 2u : 0u);  // bit 0: every lane its own piece, no sums needed
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) {
+            if constexpr (NV > 1) {
+                if (c + j < c1) {  // wave-uniform
+                    double sum[NV];
+#pragma unroll
+                    for (int n = 0; n < NV; ++n) sum[n] = v[j] * xw[j][n];
+                    piece_sums_n<NV>(sum, hd[j], (cw[j] & 2u) != 0);
+                    if (slot[j] != 0xFFFFFFFFu) put_n<NV>(partial + (size_t)slot[j] * NV, sum);
+                }
+            } else
             if (c + j < c1) {  // wave-uniform
-                const double prod = v[j] * xw[j];
+                const double prod = v[j] * xw[j][0];
                 double sum = prod;
                 if (SUMS_DPP) {
                     if (!(probe & 1)) sum = piece_sums(prod, hd[j], (cw[j] & 2u) != 0);
@@ -370,6 +515,19 @@ __global__ __launch_bounds__(THREADS) void ehyb_pb_scale_kernel(const int2* __re
     pb_scale_body<THREADS, SUMS_DPP, PROBE, 8>(items, units, val, colf, chunk, jump, x, partial, panel_cols, probe_arg, xcd_map, queue, n_items, reverse);
 }
 
+// Pass 1 for NV = 2, 3, 4 columns (ehyb_spmm).  At most 128 VGPRs: four waves per SIMD are one 1024-thread workgroup or two of
+// 512 threads per CU, as for one vector.  Chunks per wave and step: 8 (NV = 2), 6, 4 -- the NV gathered x values per chunk are
+// what the registers go to: 87 / 85 / 76 VGPRs, no scratch.
+template <int THREADS, int NV>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void ehyb_pb_scale_k_kernel(
+    const int2* __restrict__ items, const int4* __restrict__ units, const double* __restrict__ val, const uint16_t* __restrict__ colf,
+    const uint32_t* __restrict__ chunk, const uint32_t* __restrict__ jump, const double* __restrict__ x, const long long ldx, double* __restrict__ partial,
+    int panel_cols, int xcd_map, int* __restrict__ queue, int n_items, int reverse)
+{
+    pb_scale_body<THREADS, true, false, (NV == 2 ? 8 : NV == 3 ? 6 : 4), NV>(items, units, val, colf, chunk, jump, x, partial, panel_cols, 0, xcd_map, queue, n_items,
+                                                                            reverse, ldx);
+}
+
 // Pass 2: one workgroup per unit {first partial, end partial, first row, rows}.  The row block's
 // accumulators live in LDS; (partial, 16-bit local row) are streamed and added (ds_add_f64); finally
 // y[row] += accumulator for the rows that received something (the ELL launch has written y before) -- or,
@@ -378,58 +536,23 @@ __global__ __launch_bounds__(THREADS) void ehyb_pb_scale_kernel(const int2* __re
 // NT: the partial sums and their row words are streamed past the caches -- where they are more than the Infinity Cache can hold between the
 // passes anyway (R-MAT 2^24: 460 MB; 520 -> 487 us with it, because the next multiply then finds more of the entry stream's tail there);
 // where they fit (2^22: 89 MB) pass 2 reads them from that cache and the hint costs 3 us.
-template <int THREADS, bool NT>
-__global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_kernel(const int4* __restrict__ units,
-                                                                 const double* __restrict__ partial,
-                                                                 const uint16_t* __restrict__ row,
-                                                                 double* __restrict__ y, int probe)
+// The write-back of pass 2 for one column: the accumulators of the block's rows, NV doubles apart in LDS.
+template <int THREADS, int NV>
+__device__ __forceinline__ void pb_write_back(double* __restrict__ yp, const double* yacc, int rows, bool assign, int probe)
 {
-    // probe (timing diagnostics only): 16 no lane sums, 32 no LDS adds, 64 no write-back, 128 no zeroing
-    extern __shared__ __attribute__((aligned(16))) double yacc[];
-    int4 u = units[blockIdx.x];
-    const bool assign = u.w < 0;  // the block is the only writer of its rows (partitions without a window): y = sum, zeros included
-    u.w = assign ? -u.w : u.w;
-    if (!(probe & 128))
-        for (int i = threadIdx.x; i < u.w; i += THREADS) yacc[i] = 0.0;
-    __syncthreads();
-    constexpr int K = 8;  // partials per thread and step: 16 independent loads in flight
-    // every wave runs the same number of steps (the shuffles need all 64 lanes)
-    for (int base = u.x; base < u.y; base += K * THREADS) {
-        double v[K];
-        uint32_t r[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int i = base + j * THREADS + (int)threadIdx.x;
-            const bool in = i < u.y;
-            if (NT) {
-                v[j] = in ? __builtin_nontemporal_load(&partial[i]) : 0.0;
-                r[j] = in ? (uint32_t)__builtin_nontemporal_load(&row[i]) : 0xFFFFFFFFu;
-            } else {
-                v[j] = in ? partial[i] : 0.0;
-                r[j] = in ? (uint32_t)row[i] : 0xFFFFFFFFu;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            // (summing equal neighbouring rows across lanes first was measured: 17 us of an 80 us launch
-            // for nothing -- the LDS adds serialise the few same-row neighbours by themselves)
-            if (r[j] != 0xFFFFFFFFu && (!(probe & 32) || v[j] == 123.456)) unsafeAtomicAdd(&yacc[r[j]], v[j]);  // ds_add_f64
-        }
-    }
-    __syncthreads();
+    constexpr int K = 8;
     // y[row] += accumulator for the rows that received something: the loads of a batch first, then the stores
-    double* __restrict__ yp = y + u.z;
     if (probe & 64) return;
     if (assign) {
-        for (int i = threadIdx.x; i < u.w; i += THREADS) yp[i] = yacc[i];
+        for (int i = threadIdx.x; i < rows; i += THREADS) yp[i] = yacc[i * NV];
         return;
     }
-    for (int i0 = 0; i0 < u.w; i0 += K * THREADS) {
+    for (int i0 = 0; i0 < rows; i0 += K * THREADS) {
         double a[K], yo[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             const int i = i0 + j * THREADS + (int)threadIdx.x;
-            a[j] = i < u.w ? yacc[i] : 0.0;
+            a[j] = i < rows ? yacc[i * NV] : 0.0;
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) {
@@ -442,6 +565,85 @@ __global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_kernel(const int4* __r
             if (a[j] != 0.0) yp[i] = yo[j] + a[j];
         }
     }
+}
+
+// NV columns (ehyb_spmm): partial[slot NV + j], accumulators yacc[row NV + j], one row word per slot for the NV adds; NV = 1 is the
+// one-vector kernel.
+template <int THREADS, bool NT, int NV>
+__device__ __forceinline__ void pb_reduce_body(const int4* __restrict__ units, const double* __restrict__ partial, const uint16_t* __restrict__ row,
+                                               double* __restrict__ y, long long ldy, int probe)
+{
+    // probe (timing diagnostics only): 16 no lane sums, 32 no LDS adds, 64 no write-back, 128 no zeroing
+    extern __shared__ __attribute__((aligned(16))) double yacc[];
+    int4 u = units[blockIdx.x];
+    const bool assign = u.w < 0;  // the block is the only writer of its rows (partitions without a window): y = sum, zeros included
+    u.w = assign ? -u.w : u.w;
+    if (!(probe & 128))
+        for (int i = threadIdx.x; i < u.w * NV; i += THREADS) yacc[i] = 0.0;
+    __syncthreads();
+    constexpr int KP = NV == 1 ? 8 : NV == 2 ? 4 : 2;  // partials per thread and step: 16 (12 for three columns) independent loads in flight
+    // every wave runs the same number of steps (the shuffles need all 64 lanes)
+    for (int base = u.x; base < u.y; base += KP * THREADS) {
+        double v[KP][NV];
+        uint32_t r[KP];
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const int i = base + j * THREADS + (int)threadIdx.x;
+            const bool in = i < u.y;
+            if constexpr (NV == 1) {
+                if (NT) {
+                    v[j][0] = in ? __builtin_nontemporal_load(&partial[i]) : 0.0;
+                    r[j] = in ? (uint32_t)__builtin_nontemporal_load(&row[i]) : 0xFFFFFFFFu;
+                } else {
+                    v[j][0] = in ? partial[i] : 0.0;
+                    r[j] = in ? (uint32_t)row[i] : 0xFFFFFFFFu;
+                }
+            } else {
+                const int ic = in ? i : u.x;  // (in range: u.x < u.y inside the loop)
+                if (NT) {
+                    get_n_nt<NV>(partial + (size_t)ic * NV, v[j]);
+                    r[j] = in ? (uint32_t)__builtin_nontemporal_load(&row[i]) : 0xFFFFFFFFu;
+                } else {
+                    get_n<NV>(partial + (size_t)ic * NV, v[j]);
+                    r[j] = in ? (uint32_t)row[i] : 0xFFFFFFFFu;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            // (summing equal neighbouring rows across lanes first was measured: 17 us of an 80 us launch
+            // for nothing -- the LDS adds serialise the few same-row neighbours by themselves)
+            if constexpr (NV == 1) {
+                if (r[j] != 0xFFFFFFFFu && (!(probe & 32) || v[j][0] == 123.456)) unsafeAtomicAdd(&yacc[r[j]], v[j][0]);  // ds_add_f64
+            } else if (r[j] != 0xFFFFFFFFu) {
+#pragma unroll
+                for (int n = 0; n < NV; ++n) unsafeAtomicAdd(&yacc[r[j] * NV + n], v[j][n]);
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (NV == 1) {
+        pb_write_back<THREADS, 1>(y + u.z, yacc, u.w, assign, probe);
+    } else {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) pb_write_back<THREADS, NV>(y + u.z + n * ldy, yacc + n, u.w, assign, 0);
+    }
+}
+
+template <int THREADS, bool NT>
+__global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_kernel(const int4* __restrict__ units,
+                                                                 const double* __restrict__ partial,
+                                                                 const uint16_t* __restrict__ row,
+                                                                 double* __restrict__ y, int probe)
+{
+    pb_reduce_body<THREADS, NT, 1>(units, partial, row, y, 0, probe);
+}
+
+template <int THREADS, bool NT, int NV>
+__global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_k_kernel(const int4* __restrict__ units, const double* __restrict__ partial,
+                                                                   const uint16_t* __restrict__ row, double* __restrict__ y, const long long ldy)
+{
+    pb_reduce_body<THREADS, NT, NV>(units, partial, row, y, ldy, 0);
 }
 
 // dst[i] = src[idx[i]]: the send list of a halo exchange (multi-GPU), four gathers per thread in flight
@@ -710,9 +912,13 @@ static int pass2_split(const ehyb_plan* P)
 }
 
 // u2_part (pass 2): 0 = every row block, 1 = the blocks in front of cfg.row_split, 2 = the blocks from it on
-static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st, int probe, int which, int unit_begin = 0, int unit_end = -1, int u2_part = 0)
+// k = 2..spmm_width(H) columns ldx / ldy doubles apart (ehyb_spmm): both passes k wide; no probes there.
+static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st, int probe, int which, int unit_begin = 0, int unit_end = -1, int u2_part = 0,
+                        long long ldx = 0, long long ldy = 0, int k = 1)
 {
     const HostLayout& H = P->host;
+    // (k > 1: register-scan sums whatever cfg.er_sums says -- the LDS-sum A/B arm is one vector wide -- and no probes)
+    if (k < 1 || k > spmm_width(H) || (k > 1 && probe)) EHYB_FAIL(EHYB_ERR_ARG, "launch_panel: %d columns on a plan whose panel passes serve %d", k, spmm_width(H));
     const int u_all = (int)(H.pb_items1.size() / 2), u2_all = (int)(H.pb_units2.size() / 4);
     const int u2_cut = u2_part ? pass2_split(P) : 0;
     const int u2_first = u2_part == 2 ? u2_cut : 0, u2 = (u2_part == 1 ? u2_cut : u2_all) - u2_first;
@@ -722,7 +928,8 @@ static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st
     if ((which & 1) && u1 > 0) {
         // panels of up to 9,728 columns: two 512-thread workgroups per CU (one stages while the other streams); wider
         // panels leave room for one workgroup only, which then gets the CU's 16 waves
-        const bool wide = P->cfg.er_panel_threads ? P->cfg.er_panel_threads == 1024 : H.pb_panel_cols > 9728;
+        // (on the LDS the launch really takes: k interleaved panel images)
+        const bool wide = P->cfg.er_panel_threads ? P->cfg.er_panel_threads == 1024 : (int64_t)k * H.pb_panel_cols > 9728;
         const bool dpp = P->cfg.er_sums != 2;
         const int xcd = P->cfg.xcd_map != 2 ? 1 : 0;
         // cfg.er_queue: one resident round of workgroups taking items from per-XCD queues (with stealing) instead of one
@@ -749,26 +956,53 @@ static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st
 #define PB_SCALE(T, D)                  \
     if (probe) PB_SCALE_P(T, D, true);  \
     else PB_SCALE_P(T, D, false)
-        if (wide) {
+#define PB_SCALE_K(T, NV)                                                                                                                                   \
+    hipLaunchKernelGGL((ehyb_pb_scale_k_kernel<T, NV>), dim3(grid), dim3(T), ((size_t)(NV) * H.pb_panel_cols + 1) * 8, st, (const int2*)P->d_pb_items1 + unit_begin, \
+                       (const int4*)P->d_pb_units1, P->d_pb_val, P->d_pb_colf, P->d_pb_chunk, P->d_pb_jump, x, ldx, P->d_pb_partial, H.pb_panel_cols, xcd, queue, u1, rev)
+        if (k > 1) {
+            if (wide) {
+                if (k == 2) PB_SCALE_K(1024, 2); else if (k == 3) PB_SCALE_K(1024, 3); else PB_SCALE_K(1024, 4);
+            } else {
+                if (k == 2) PB_SCALE_K(512, 2); else if (k == 3) PB_SCALE_K(512, 3); else PB_SCALE_K(512, 4);
+            }
+        } else if (wide) {
             if (dpp) { PB_SCALE(1024, true); } else { PB_SCALE(1024, false); }
         } else {
             if (dpp) { PB_SCALE(512, true); } else { PB_SCALE(512, false); }
         }
+#undef PB_SCALE_K
 #undef PB_SCALE
 #undef PB_SCALE_P
     }
     if ((which & 2) && u2 > 0) {
-        // (cfg.er_nt: 0 = by the size of what pass 2 reads -- 10 B per partial sum -- against half the 256 MB Infinity Cache, 1 / 2 = always / never)
-        const bool nt = P->cfg.er_nt == 1 || (P->cfg.er_nt == 0 && H.pb_partials * 10 > (128ll << 20));
-        if (nt)
+        // (cfg.er_nt: 0 = by the size of what pass 2 reads -- 8 B per column and 2 B of row word per partial sum -- against half the 256 MB
+        // Infinity Cache, 1 / 2 = always / never)
+        const bool nt = P->cfg.er_nt == 1 || (P->cfg.er_nt == 0 && H.pb_partials * (8 * k + 2) > (128ll << 20));
+#define PB_REDUCE_K(NT, NV)                                                                                                                                       \
+    hipLaunchKernelGGL((ehyb_pb_reduce_k_kernel<512, NT, NV>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * (NV) * 8, st, (const int4*)P->d_pb_units2 + u2_first, \
+                       P->d_pb_partial, P->d_pb_row, y, ldy)
+        if (k > 1) {
+            if (nt) {
+                if (k == 2) PB_REDUCE_K(true, 2); else if (k == 3) PB_REDUCE_K(true, 3); else PB_REDUCE_K(true, 4);
+            } else {
+                if (k == 2) PB_REDUCE_K(false, 2); else if (k == 3) PB_REDUCE_K(false, 3); else PB_REDUCE_K(false, 4);
+            }
+        } else if (nt)
             hipLaunchKernelGGL((ehyb_pb_reduce_kernel<512, true>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * 8, st, (const int4*)P->d_pb_units2 + u2_first,
                                P->d_pb_partial, P->d_pb_row, y, probe);
         else
             hipLaunchKernelGGL((ehyb_pb_reduce_kernel<512, false>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * 8, st, (const int4*)P->d_pb_units2 + u2_first,
                                P->d_pb_partial, P->d_pb_row, y, probe);
     }
+#undef PB_REDUCE_K
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
+}
+
+int ehyb::launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, int walk)
+{
+    WalkScope w(walk);  // reaches pass 1 the way ehyb_spmv_walk's does
+    return launch_panel(P, x, y, st, 0, 3, 0, -1, 0, ldx, ldy, k);
 }
 
 int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st)
@@ -1159,7 +1393,8 @@ int ehyb_plan_upload(ehyb_plan* P)
             free_device(P);
             EHYB_FAIL(EHYB_ERR_HIP, "ehyb_plan_upload: no device memory for the work queues");
         }
-        if (hipMalloc((void**)&P->d_pb_partial, (size_t)std::max<int64_t>(H.pb_partials, 1) * 8) != hipSuccess) {
+        // (one slot per partial sum and column of the widest pass)
+        if (hipMalloc((void**)&P->d_pb_partial, (size_t)std::max<int64_t>(H.pb_partials, 1) * spmm_width(H) * 8) != hipSuccess) {
             free_device(P);
             EHYB_FAIL(EHYB_ERR_HIP, "ehyb_plan_upload: no device memory for %lld partial sums", (long long)H.pb_partials);
         }
@@ -1188,6 +1423,15 @@ int ehyb_plan_upload(ehyb_plan* P)
     LDS_ATTR((ehyb_pb_scale_kernel<1024, false, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, true>))
     LDS_ATTR((ehyb_pb_reduce_kernel<512, false>))
+#define LDS_ATTR_K(NV)                                   \
+    LDS_ATTR((ehyb_pb_scale_k_kernel<512, NV>))          \
+    LDS_ATTR((ehyb_pb_scale_k_kernel<1024, NV>))         \
+    LDS_ATTR((ehyb_pb_reduce_k_kernel<512, true, NV>))   \
+    LDS_ATTR((ehyb_pb_reduce_k_kernel<512, false, NV>))
+    LDS_ATTR_K(2)
+    LDS_ATTR_K(3)
+    LDS_ATTR_K(4)
+#undef LDS_ATTR_K
 #undef LDS_ATTR
     P->uploaded = true;
     return EHYB_OK;

@@ -1,7 +1,8 @@
 // Y = A X for k columns per pass over the matrix (ehyb_spmm, include/ehyb.h).  The value stream, the column words, the lane maps
 // and the slab records are read ONCE per pass for up to k_max columns; a multiply moves about matrix + k (x + y) bytes instead of
 // k (matrix + x + y).  A pass of width 2..4 is one launch of the window kernel and, unless the residual rides inline, one of the
-// CSR-segment residual, both K columns wide (ell_device.h, launched by ehyb_hip.hip); a pass of width 1 is ehyb_spmv_walk itself.
+// CSR-segment residual, both K columns wide (ell_device.h, launched by ehyb_hip.hip); on a plan whose residual is in panel form,
+// the window launch (if the plan kept windows) and the two panel passes, K wide; a pass of width 1 is ehyb_spmv_walk itself.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,16 +11,6 @@
 #include "ell_device.h"
 
 using namespace ehyb;
-
-// Widest pass of a plan: the K window images and the slab counter must fit the 160 KiB of LDS.
-static int spmm_width(const HostLayout& H)
-{
-    if (H.er_panel || H.deferred.pending) return 1;  // a panel-form residual multiplies one vector per pass
-    if (H.direct) return kSpmmMaxK;                   // no window
-    const int64_t cap = ell_win_cap(H);
-    if (cap <= 0) return kSpmmMaxK;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(kSpmmMaxK, ((int64_t)EHYB_LDS_MAX_DOUBLES * 8 - 16) / (8 * cap)));
-}
 
 int ehyb_spmm_max_k(const ehyb_plan* P, int* k_max)
 {
@@ -52,7 +43,8 @@ int ehyb_spmm(ehyb_plan* P, const double* X, int64_t ldx, double* Y, int64_t ldy
             rc = ehyb_spmv_walk(P, Xp, Yp, stream, walk);  // the one-vector launch sequence
         } else {
             rc = launch_window(P, Xp, ldx, Yp, ldy, w, st, H.inline_er, walk);
-            if (rc == EHYB_OK && !H.inline_er) rc = launch_er_csr(P, Xp, ldx, Yp, ldy, w, st);
+            if (rc == EHYB_OK && H.er_panel) rc = launch_panel_k(P, Xp, ldx, Yp, ldy, w, st, walk);  // (never inline; no window launch where no partition kept one)
+            else if (rc == EHYB_OK && !H.inline_er) rc = launch_er_csr(P, Xp, ldx, Yp, ldy, w, st);
         }
         if (rc != EHYB_OK) return rc;
         j0 += w;

@@ -524,6 +524,22 @@ inline size_t ell_lds_bytes(const HostLayout& H, int k) { return (size_t)k * ell
 // alternation.  k = 1 only: stamps (diagnostic; no walk of its own) and xy_out (x . y on the side).
 int launch_window(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, bool inl, int walk,
                   unsigned long long* stamps = nullptr, double* xy_out = nullptr);
+// Widest pass of ehyb_spmm on a plan (ehyb_spmm_max_k; the rule is stated in include/ehyb.h): what fits the 160 KiB of LDS -- k
+// window images and the slab counter; for a panel-form residual also k panel images and the hand-over word of pass 1, and k
+// accumulators per row of the largest row block of pass 2.
+inline int spmm_width(const HostLayout& H)
+{
+    if (H.deferred.pending) return 1;  // (the panel form is not built yet: nothing can be multiplied)
+    int64_t k = kSpmmMaxK;
+    if (H.er_panel && H.pb_panel_cols > 0 && H.pb_rows_max > 0)
+        k = std::min<int64_t>(k, std::min<int64_t>((EHYB_LDS_MAX_DOUBLES - 1) / H.pb_panel_cols, EHYB_LDS_MAX_DOUBLES / H.pb_rows_max));
+    const int64_t cap = ell_win_cap(H);
+    if (!H.direct && cap > 0) k = std::min<int64_t>(k, ((int64_t)EHYB_LDS_MAX_DOUBLES * 8 - 16) / (8 * cap));
+    return (int)std::max<int64_t>(1, k);
+}
+
+// Both passes of the panel-form residual for k = 2..spmm_width columns (k = 1: the one-vector launch of ehyb_spmv)
+int launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, int walk);
 // The CSR-segment residual launch for k columns (none where the plan has no CSR segments)
 int launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st);
 }  // namespace ehyb

@@ -401,14 +401,17 @@ class Plan:
 
     def spmm(self, x_dev, y_dev, k, ldx=None, ldy=None, stream=0, walk=None):
         """Asynchronous Y[:, j] = A X[:, j], j < k, on device pointers (ints; column j at X + j*ldx, Y + j*ldy; None = n) --
-        ehyb_spmm: ceil(k / spmm_max_k) passes over the matrix.  walk: None = the plan's own alternation, 0 / 1 explicit."""
+        ehyb_spmm: ceil(k / spmm_max_k) passes over the matrix, a panel-form residual's two passes as wide as the window launch.
+        walk: None = the plan's own alternation, 0 / 1 explicit."""
         _check(self.lib.ehyb_spmm(self.h, C.c_void_p(x_dev), self.n if ldx is None else int(ldx), C.c_void_p(y_dev),
                                   self.n if ldy is None else int(ldy), int(k), C.c_void_p(stream), -1 if walk is None else int(walk)),
                "ehyb_spmm")
 
     @property
     def spmm_max_k(self):
-        """ehyb_spmm_max_k: the widest k one pass over the matrix serves (1..4; build with lds_doubles = 20480 // k for k)."""
+        """ehyb_spmm_max_k: the widest k one pass over the matrix serves (1..4; build with lds_doubles = 20480 // k for k; a plan
+        whose residual is in panel form -- stats["er_partials"] > 0 -- with er_panel_cols = 16384 // k, and lds_doubles as well
+        where it keeps windows)."""
         k = C.c_int(0)
         _check(self.lib.ehyb_spmm_max_k(self.h, C.byref(k)), "ehyb_spmm_max_k")
         return k.value
@@ -478,7 +481,8 @@ class Plan:
     def cg_multi(self, B, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_cg_multi / ehyb_pcg_multi: k independent (Jacobi-preconditioned if inv_diag is given) CG solves that share every
         multiply; B, X0 (k, n) in the permuted numbering, column j solved as cg(B[j]) would.  -> (X (k, n), iterations (k,),
-        relative residuals (k,)).  A breakdown raises EhybError, unless allow_breakdown: then the broken columns report NaN."""
+        relative residuals (k,)).  A breakdown raises EhybError, unless allow_breakdown: then the broken columns report NaN.
+        The multiplies are as wide as spmm_max_k allows -- on a panel-form plan too, when it was built with er_panel_cols = 16384 // k."""
         B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
         k, n = B.shape
         assert n == self.n, (n, self.n)

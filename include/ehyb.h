@@ -498,6 +498,17 @@ void ehyb_graph_destroy(ehyb_graph* graph);
  * matrix's streams once for all of them.  Column j of a plain-storage multiply equals ehyb_spmv of X[:, j] bit for bit, but for
  * rows the residual splits into several segments (fp64 atomics); with symmetric pair storage the LDS adds' order is free, as
  * between any two launches.  The non-finite contract of ehyb_spmv holds per column: a non-finite X[c, j] reaches column j only.
+ * A residual in PANEL FORM (stats.er_partials > 0) is multiplied K wide too: the window launch K wide where the plan kept windows,
+ * then both panel passes -- pass 1 stages K interleaved images of every x panel and reads the entry stream (values, column words,
+ * chunk records, jump lists) once for the K products; pass 2 reads one row word per partial sum for its K adds.
+ *   Exactness: pass 2 adds the partial sums with LDS atomics, in any order, at every width (as between two one-vector launches
+ *   of such a plan).  A column of a K-wide panel multiply equals the one-vector multiply up to the order of summation, and bit
+ *   for bit wherever every product and sum is exact (integer data).
+ *   Non-finite values, per column: the padding of the panel form reads nothing (a padding slot stores nothing), so a non-finite
+ *   X[c, j] reaches column j only, and in it only the rows that store column c -- plus, through windows the plan kept, what the
+ *   window contract allows.
+ *   One multiply at a time per plan (the partial-sum buffer, k_max * stats.er_partials doubles), as for ehyb_spmv.
+ *   The multiply in parts (ehyb_spmv_part, ehyb_halo_*) stays one vector wide.
  * EHYB_ERR_ARG for a null pointer, k < 1, an ld too small or a bad walk; EHYB_ERR_STATE on a plan never uploaded.
  */
 int ehyb_spmm(ehyb_plan* plan, const double* X_dev, int64_t ldx, double* Y_dev, int64_t ldy, int k, void* stream, int walk);
@@ -509,7 +520,18 @@ int ehyb_spmm(ehyb_plan* plan, const double* X_dev, int64_t ldx, double* Y_dev, 
  *                 default window has k_max = 1: to get a wide plan, build it with cfg.lds_doubles = EHYB_LDS_MAX_DOUBLES / k
  *                 (the partitions are then sized for k vectors; the one-vector multiply of such a plan still works);
  *   the direct shape (no window): 4;
- *   a residual in panel form (stats.er_partials > 0): 1 -- such a plan multiplies one vector per pass.
+ *   a residual in panel form (stats.er_partials > 0): min(k_panel, k_window) with
+ *                 k_panel  = min(4, (EHYB_LDS_MAX_DOUBLES - 1) / panel columns, EHYB_LDS_MAX_DOUBLES / rows of the largest row block)
+ *                 -- K panel images and the one hand-over word behind them in pass 1, K accumulators per row of the largest
+ *                 row block in pass 2 -- and k_window = the window rule above where the plan still makes a window launch (4
+ *                 where no partition kept its window: stats.lds_bytes == 0).  Integer division throughout.  The panel columns
+ *                 are the CONFIGURED width (cfg.er_panel_cols, default 16,384), not the widest panel the matrix fills, so a
+ *                 default plan has k_max = 1: build with cfg.er_panel_cols = 16384 / k (4096 for k = 4, 5120 for 3, 8192 for
+ *                 2) and, where windows are kept, cfg.lds_doubles = EHYB_LDS_MAX_DOUBLES / k as well.  A window that holds no
+ *                 entry still counts (cfg.er_mode = 2 keeps the windows).  Host- and device-built plans of one matrix report
+ *                 one width.  Narrower panels mean more partial sums per vector (R-MAT 2^22: 8.9 M at 16,384 columns, 13.3 M
+ *                 at 4,096), and the partial sums scale with K: see DESIGN.md 10 for what each width measured before
+ *                 choosing one -- k_max says what FITS, not what pays.
  */
 int ehyb_spmm_max_k(const ehyb_plan* plan, int* k_max);
 
