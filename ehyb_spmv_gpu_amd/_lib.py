@@ -101,6 +101,20 @@ class Stats(C.Structure):
         return {n: int(getattr(self, n)) for n in _STAT_NAMES}
 
 
+_BICGSTAB_SLOT_NAMES = [
+    "slots", "slot_doubles", "slot_bb", "slot_rv", "slot_ss", "slot_ts", "slot_tt", "slot_rho0", "slot_rr",
+    "flag_status", "flag_iters", "flag_count", "status_running", "status_converged", "status_breakdown",
+]
+
+
+class BicgstabSlots(C.Structure):
+    """ehyb_bicgstab_slots (include/ehyb.h): the slot layout behind the ehyb_bicgstab_*_step building blocks"""
+    _fields_ = [(n, C.c_int32) for n in _BICGSTAB_SLOT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in _BICGSTAB_SLOT_NAMES}
+
+
 # every symbol include/*.h declares with C linkage: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -196,6 +210,13 @@ SIGNATURES = {
     "ehyb_cg_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_cg_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_cg_direction_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_bicgstab_layout": (C.c_int, [_P(BicgstabSlots)]),
+    "ehyb_bicgstab_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ehyb_bicgstab_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_bicgstab_s_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_bicgstab_dot2_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_bicgstab_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
+    "ehyb_bicgstab_direction_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

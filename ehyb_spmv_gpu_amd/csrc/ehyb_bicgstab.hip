@@ -342,3 +342,106 @@ extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, 
         EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab: breakdown after %d iterations (a zero or non-finite rho, r^.v, t.t or omega)", done);
     return EHYB_OK;
 }
+
+// ------------------------------------------------------------------ building blocks for a caller that owns the loop
+// The six vector kernels above, one launch each, for a caller that issues the multiplies itself (and for tests that look at
+// one kernel at a time) -- the analogue of ehyb_cg_*_step.  s: `slots` slots of `slot_doubles` doubles and one more double
+// behind them, whose two ints are the status word and the iteration counter (ehyb_bicgstab_layout); every launch uses
+// slot_doubles / 2 workgroups.  Asynchronous on `stream`.
+extern "C" int ehyb_bicgstab_layout(ehyb_bicgstab_slots* out)
+{
+    if (!out) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab_layout: null argument");
+    out->slots = B_COUNT;
+    out->slot_doubles = kMaxGrid;
+    out->slot_bb = B_BB;
+    out->slot_rv = B_RV;
+    out->slot_ss = B_SS;
+    out->slot_ts = B_TS;
+    out->slot_tt = B_TT;
+    out->slot_rho0 = B_RHO0;
+    out->slot_rr = B_RR;
+    out->flag_status = F_STATUS;
+    out->flag_iters = F_ITERS;
+    out->flag_count = F_COUNT;
+    out->status_running = ST_RUNNING;
+    out->status_converged = ST_CONVERGED;
+    out->status_breakdown = ST_BREAKDOWN;
+    return EHYB_OK;
+}
+
+namespace {
+
+constexpr int kStepGrid = kMaxGrid / 2;
+
+inline int check_step(const char* who, int n, std::initializer_list<const void*> pointers)
+{
+    bool ok = n >= 0;
+    for (const void* a : pointers) ok = ok && a;
+    if (!ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: bad arguments", who);
+    return EHYB_OK;
+}
+
+inline int* flags_of(double* s) { return (int*)(s + (size_t)B_COUNT * kMaxGrid); }
+
+}  // namespace
+
+extern "C" int ehyb_bicgstab_init_step(int n, const double* b, const double* q, const double* dinv, double* r, double* rh, double* p,
+                                       double* s, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_init_step", n, {b, q, r, rh, p, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_init_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, b, q, dinv, r, rh, p, s);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_bicgstab_dot_step(int n, const double* rh, const double* v, double* s, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_dot_step", n, {rh, v, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_dot_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, rh, v, s, flags_of(s));
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_bicgstab_s_step(int n, const double* r, const double* v, const double* dinv, double* sv, double* sh, double* s,
+                                    int cur, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_s_step", n, {r, v, sv, sh, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_s_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v, dinv, sv, sh, s, flags_of(s),
+                       cur & 1);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_bicgstab_dot2_step(int n, const double* t, const double* sv, double* s, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_dot2_step", n, {t, sv, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_dot2_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, t, sv, s, flags_of(s));
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_bicgstab_update_step(int n, const double* p, const double* sh, const double* sv, const double* t,
+                                         const double* rh, double* x, double* r, double* s, int cur, double thr, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_update_step", n, {p, sh, sv, t, rh, x, r, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_update_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, p, sh, sv, t, rh, x, r, s,
+                       flags_of(s), cur & 1, thr);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_bicgstab_direction_step(int n, const double* r, const double* v, const double* dinv, double* p, double* s, int cur,
+                                            double thr, void* stream)
+{
+    int rc = check_step("ehyb_bicgstab_direction_step", n, {r, v, p, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(bicg_direction_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v, dinv, p, s, flags_of(s),
+                       cur & 1, thr);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}

@@ -818,6 +818,46 @@ int ehyb_cg_update_step(int n, const double* p_dev, const double* q_dev, const d
 int ehyb_cg_direction_step(int n, const double* r_dev, const double* inv_diag_dev, double* p_dev, const double* s_dev, int cur,
                            void* stream);
 
+/*
+ * The six vector kernels of ehyb_bicgstab as building blocks, one launch each with slot_doubles / 2 workgroups, for a caller
+ * that issues the multiplies itself -- and the seam through which the tests look at one kernel at a time.  s_dev: `slots`
+ * slots of `slot_doubles` doubles and one more double behind them whose ints are the flags: the status word at int
+ * flag_status and the iteration counter at int flag_iters of (int*)(s_dev + slots * slot_doubles).  rho = rh.r number c (0/1)
+ * lives in slot rho0 + 2 c, r.r in the slot between the two; cur (0/1, masked with & 1) says which holds the current rho.
+ * thr = rtol^2.  Every step but init returns at once, writing nothing, when the status is not status_running on entry; a
+ * step that sets the status writes nothing else.
+ *   init       r = b - q, rh = r, p^ = M^-1 r; partials of rho (slot rho0), r.r, b.b.  Takes no flags: the caller zeroes them.
+ *   dot        partials of rh.v
+ *   s          alpha = rho[cur] / rh.v; a non-finite rho or alpha, a zero or non-finite rh.v: breakdown.  Else s = r - alpha v,
+ *              s^ = M^-1 s, partials of s.s
+ *   dot2       partials of t.s and t.t
+ *   update     s.s <= thr b.b (b.b = 0: 1): the half step x += alpha p^, r = s, partials of r.r, counter + 1; the status stays.
+ *              Else omega = t.s / t.t; a zero or non-finite t.t or a non-finite omega: breakdown.  Else x += alpha p^ + omega s^,
+ *              r = s - omega t, partials of rho[cur ^ 1] and r.r, counter + 1
+ *   direction  s.s <= thr b.b or r.r <= thr b.b: converged.  Else beta = (rho[cur ^ 1] / rho[cur]) (alpha / omega); a zero or
+ *              non-finite rho[cur] or omega, a non-finite rho[cur ^ 1] or beta: breakdown.  Else
+ *              p^ = M^-1 r + beta (p^ - omega M^-1 v)
+ * Every scalar is recomputed from the partials in their slots: a kernel adds the first slot_doubles / 2 entries of a slot
+ * and never looks at the rest.  All asynchronous on `stream`.
+ */
+typedef struct ehyb_bicgstab_slots {
+    int32_t slots, slot_doubles;
+    int32_t slot_bb, slot_rv, slot_ss, slot_ts, slot_tt, slot_rho0, slot_rr;
+    int32_t flag_status, flag_iters, flag_count;
+    int32_t status_running, status_converged, status_breakdown;
+} ehyb_bicgstab_slots;
+int ehyb_bicgstab_layout(ehyb_bicgstab_slots* out);
+int ehyb_bicgstab_init_step(int n, const double* b_dev, const double* q_dev, const double* inv_diag_dev, double* r_dev, double* rh_dev,
+                            double* p_dev, double* s_dev, void* stream);
+int ehyb_bicgstab_dot_step(int n, const double* rh_dev, const double* v_dev, double* s_dev, void* stream);
+int ehyb_bicgstab_s_step(int n, const double* r_dev, const double* v_dev, const double* inv_diag_dev, double* s_vec_dev,
+                         double* sh_dev, double* s_dev, int cur, void* stream);
+int ehyb_bicgstab_dot2_step(int n, const double* t_dev, const double* s_vec_dev, double* s_dev, void* stream);
+int ehyb_bicgstab_update_step(int n, const double* p_dev, const double* sh_dev, const double* s_vec_dev, const double* t_dev,
+                              const double* rh_dev, double* x_dev, double* r_dev, double* s_dev, int cur, double thr, void* stream);
+int ehyb_bicgstab_direction_step(int n, const double* r_dev, const double* v_dev, const double* inv_diag_dev, double* p_dev,
+                                 double* s_dev, int cur, double thr, void* stream);
+
 /* -------------------------------------------- harness pieces (solver_test.c) */
 
 /*
