@@ -458,6 +458,14 @@ int ehyb_plan_host_array(const ehyb_plan* plan, int which, const void** ptr, int
  * padding does (convert.c), and the padding of an inline residual (stats.er_inline) reads x[0] -- and 0 * inf, 0 * NaN are
  * NaN.  (A NaN in x[0] alone turns most rows of an inline-residual plan NaN.)  The padding of the panel form and the direct
  * shape reads nothing.  With every x finite no padding slot changes a result.
+ * Range.  Subnormal matrix values, x entries, products and partial sums are kept on every path, never flushed to zero: the
+ * window, halo and direct kernels, the CSR and inline residual, both passes of the panel form, and the fp64 atomic adds --
+ * ds_add_f64 for symmetric pairs and for the panel form's piece sums, global_atomic_add_f64 for split rows -- which were observed
+ * to keep subnormal operands and results on gfx950 (tests/test_gpu_range.py; every kernel is built with both denormal modes of
+ * its descriptor at "keep", tests/test_range_layout.py).  Every value and x travels with all 53 bits of its mantissa (ehyb_plan_
+ * set_values and the plan cache included; the refill compares a stored pair a_ij == a_ji as fp64 numbers, so two different
+ * subnormals differ).  No row's arithmetic touches another row's: rows hundreds of binades apart do not disturb each other.  A
+ * product is finite whenever every ordering of its partial sums is: no path meets an infinity before the end of a finite sum.
  */
 int ehyb_spmv(ehyb_plan* plan, const double* x_dev, double* y_dev, void* stream);
 /*
@@ -498,6 +506,9 @@ void ehyb_graph_destroy(ehyb_graph* graph);
  * matrix's streams once for all of them.  Column j of a plain-storage multiply equals ehyb_spmv of X[:, j] bit for bit, but for
  * rows the residual splits into several segments (fp64 atomics); with symmetric pair storage the LDS adds' order is free, as
  * between any two launches.  The non-finite contract of ehyb_spmv holds per column: a non-finite X[c, j] reaches column j only.
+ * So does its range contract: subnormal values, X entries, products and partial sums are kept at every width and in both panel
+ * passes (LDS atomics included, as observed on gfx950), a column is finite whenever every ordering of its partial sums is, and a
+ * subnormal column beside one near 2^1023 in the same call do not reach each other (tests/test_gpu_range.py).
  * A residual in PANEL FORM (stats.er_partials > 0) is multiplied K wide too: the window launch K wide where the plan kept windows,
  * then both panel passes -- pass 1 stages K interleaved images of every x panel and reads the entry stream (values, column words,
  * chunk records, jump lists) once for the K products; pass 2 reads one row word per partial sum for its K adds.

@@ -202,13 +202,17 @@ def _device_set_values(plan, values, order):
         lib.ehyb_dev_free(dv), lib.ehyb_dev_free(do)
 
 
-@pytest.mark.parametrize("name,gen,kw,sym", [
+# (id, matrix, config, symmetric values): the plans a refill is tested on (test_gpu_range.py refills them too)
+REFILL_PLANS = [
     ("plain", FEM, dict(lds_doubles=4096, direct=2), True),
     ("sym-pairs", FEM, dict(lds_doubles=4096, sym_pairs=1), True),
     ("csr-split", RMAT11, dict(window_mode=1, lds_doubles=256, er_seg_len=16, er_mode=1, fuse_er=2), False),
     ("panel", RMAT14, dict(er_mode=2, fuse_er=2, lds_doubles=512, er_panel_cols=512, er_block_rows=300), False),
     ("direct", ("rmat", (13, 1 << 18, 3)), dict(), False),
-], ids=lambda v: v if isinstance(v, str) else None)
+]
+
+
+@pytest.mark.parametrize("name,gen,kw,sym", REFILL_PLANS, ids=lambda v: v if isinstance(v, str) else None)
 @pytest.mark.parametrize("how", ["host", "device"])
 def test_exact_refill(E, O, gpu, name, gen, kw, sym, how):
     """set_values with new integer values, from the host (reordered order) or the device (caller's order + entry_order):
