@@ -187,7 +187,7 @@ Config resolve_config(const ehyb_config* in)
     c.er_nt = (z.er_nt == 1 || z.er_nt == 2) ? z.er_nt : 0;
     c.ell_nt = (z.ell_nt >= 1 && z.ell_nt <= 5) ? z.ell_nt : 4;  // 4: a fixed set of slabs stays in the Infinity Cache (ell_keep_rule)
     c.ell_keep = std::min(1000, std::max(0, z.ell_keep));  // 0: by the size of the Infinity Cache (ell_keep_rule)
-    c.er_queue = (z.er_queue == 1 || z.er_queue == 2) ? z.er_queue : 0;  // 0: by the number of items per resident workgroup (launch_panel)
+    c.er_queue = (z.er_queue == 1 || z.er_queue == 2) ? z.er_queue : 0;  // 0: by the number of items per resident workgroup (launch_panel_scale)
     // the automatic choice of the direct shape is for callers that left the window sizing alone: a caller
     // that names a window (lds_doubles / part_rows other than the defaults) gets that window
     if (c.direct == 0 && (c.lds_doubles != EHYB_LDS_MAX_DOUBLES || c.part_rows != round_down(EHYB_LDS_MAX_DOUBLES * 11 / 20, kSlabRows) ||

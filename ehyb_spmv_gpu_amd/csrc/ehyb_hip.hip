@@ -1,6 +1,7 @@
 // HIP kernels for gfx950 (MI355X, CDNA4) and the device half of the C-ABI.
 //
-// Kernels (replace reference kernel.cu:43-284; the bodies of the first two are in ell_device.h, written once for K columns):
+// Kernels (replace reference kernel.cu:43-284; this file holds their thin entry points, the bodies are in ell_device.h and
+// panel_device.h):
 //   ehyb_ell_kernel  one workgroup per work item = a run of 64-row slabs of (nearly) equal byte
 //                    count, cut into segments at partition boundaries.  Per segment:
 //                      1. stage the partition's x-window into LDS -- contiguous own segment
@@ -30,9 +31,10 @@
 //                    not carried inline (the reference skips it after the first launch: SURVEY 8
 //                    a-10 item 1); it is also phase 2 of the multi-GPU multiply (all remote columns).
 //                    ehyb_er_k_kernel: the same for K = 2, 3, 4 columns.
-//   ehyb_pb_scale_kernel / ehyb_pb_reduce_kernel  the two passes of the panel-form residual (below); ehyb_pb_scale_k_kernel /
-//                    ehyb_pb_reduce_k_kernel: the same bodies for K = 2, 3, 4 columns.
-//   launch_window / launch_er_csr / launch_panel  the one launch path of each family, for every K.
+//   ehyb_pb_scale_kernel / ehyb_pb_reduce_kernel  the two passes of the panel-form residual (bodies in panel_device.h, written
+//                    once for K columns); ehyb_pb_scale_k_kernel / ehyb_pb_reduce_k_kernel: the same for K = 2, 3, 4 columns.
+//   launch_window / launch_er_csr / launch_panel_scale + launch_panel_reduce  the one launch path of each family (of each pass
+//                    of the panel family), for every K; each looks its kernel up in a table of the family's instantiations.
 // No MFMA: 2 flops per 5.8-10 streamed bytes, HBM-bound.
 //
 // Arms tried and dropped (measurements in DESIGN.md 3.1): software-pipelined slab walk with ping-pong
@@ -47,6 +49,7 @@
 #include "ehyb_internal.h"
 #include "hip_try.h"
 #include "ell_device.h"
+#include "panel_device.h"
 
 using namespace ehyb;
 
@@ -92,420 +95,9 @@ __global__ __launch_bounds__(THREADS) void ehyb_er_k_kernel(const int4* __restri
     er_blocks<THREADS, ASSIGN, K>(blocks, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
 }
 
-// ------------------------------------------------------------------ panel residual (er_panel.cpp)
-// Pass 1: one workgroup per unit {first column, columns, first entry, end entry}.  The unit's panel of
-// x is staged in LDS; (value, 16-bit column word) are streamed, eight 64-entry chunks per wave and step.
-// The column word carries two flags from which a lane works out the slot of its partial (er_panel.cpp,
-// encode_panel_slots): bit 15 = first entry of a piece (entries of one row that are neighbours in the
-// chunk), bit 14 = the piece's slot is not the previous piece's + 1: a "jump", with an entry in the jump list
-// from which every lane behind it (up to the next jump) gets its slot by adding the pieces begun before its own.
-// The products of a piece are summed in the wave's LDS words and its first lane stores the partial.
-// One step of a segmented inclusive scan over the 64 lanes of a wave, in registers (DPP moves, no LDS): every lane takes
-// (sum, flag) of the lane CTRL names -- row_shr:d inside the rows of 16 lanes, row_bcast15 / row_bcast31 across them --
-// and adds the sum unless a piece has begun between that lane and itself (flag).  Lanes without a source read zeros.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void seg_scan_step(double& v, uint32_t& f)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-    const uint32_t fp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, CTRL, ROW_MASK, 0xf, true);
-    v += f ? 0.0 : __hiloint2double(hi, lo);
-    f |= fp;
-}
-
-// Sums of the pieces of one 64-entry chunk: afterwards the LAST lane of every piece holds the piece's sum.  `heads` =
-// ballot of the first lanes of the pieces (bit 0 always set).  Only the steps the chunk needs are run (wave-uniform
-// branches on the ballot): none when every lane is its own piece -- most chunks of the sparse panels --, row_shr:1 alone
-// when no piece is longer than two lanes, and so on; a hub row's 64-lane piece takes all six.
-__device__ __forceinline__ double piece_sums(double prod, unsigned long long heads, bool head)
-{
-    const unsigned long long nh = ~heads;  // lanes that continue a piece
-    if (nh == 0ull) return prod;
-    if (heads == 1ull) {
-        // the whole chunk is one piece -- a hub row in a hub panel, a third of the entries of a degree-ordered R-MAT: a
-        // plain sum over the wave, no flags to carry (half the instructions of the segmented steps)
-        double v = prod;
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x111, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x111, 0xf, 0xf, true));
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x112, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x112, 0xf, 0xf, true));
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x114, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x114, 0xf, 0xf, true));
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x118, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x118, 0xf, 0xf, true));
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x142, 0xa, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x142, 0xa, 0xf, true));
-        v += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x143, 0xc, 0xf, true), __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x143, 0xc, 0xf, true));
-        return v;  // lane 63 holds the sum
-    }
-    double v = prod;
-    uint32_t f = head ? 1u : 0u;
-    seg_scan_step<0x111, 0xf>(v, f);  // row_shr:1
-    const unsigned long long r2 = nh & (nh >> 1);
-    if (r2 != 0ull) {  // a piece of three lanes or more
-        seg_scan_step<0x112, 0xf>(v, f);  // row_shr:2
-        const unsigned long long r4 = r2 & (r2 >> 2);
-        if (r4 != 0ull) {  // five or more
-            seg_scan_step<0x114, 0xf>(v, f);  // row_shr:4
-            const unsigned long long r8 = r4 & (r4 >> 4);
-            if (r8 != 0ull) seg_scan_step<0x118, 0xf>(v, f);  // nine or more: row_shr:8
-        }
-    }
-    if (nh & 0x0001000100010000ull) {  // a piece crosses from one row of 16 lanes into the next
-        seg_scan_step<0x142, 0xa>(v, f);  // row_bcast15: lane 15 -> row 1, lane 47 -> row 3
-        seg_scan_step<0x143, 0xc>(v, f);  // row_bcast31: lane 31 -> rows 2 and 3
-    }
-    return v;
-}
-
-// ---- the same for NV columns per entry (ehyb_spmm on a panel-form plan): the flags, and with them every branch, belong to the
-// chunk and are worked out once; only the sums are per column.
-template <int CTRL, int ROW_MASK, int NV>
-__device__ __forceinline__ void seg_scan_step_n(double (&v)[NV], uint32_t& f)
-{
-    const uint32_t fp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, CTRL, ROW_MASK, 0xf, true);
-#pragma unroll
-    for (int n = 0; n < NV; ++n) {
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v[n]), CTRL, ROW_MASK, 0xf, true);
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v[n]), CTRL, ROW_MASK, 0xf, true);
-        v[n] += f ? 0.0 : __hiloint2double(hi, lo);
-    }
-    f |= fp;
-}
-
-template <int CTRL, int ROW_MASK, int NV>
-__device__ __forceinline__ void wave_sum_step_n(double (&v)[NV])
-{
-#pragma unroll
-    for (int n = 0; n < NV; ++n)
-        v[n] += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v[n]), CTRL, ROW_MASK, 0xf, true),
-                                 __builtin_amdgcn_update_dpp(0, __double2loint(v[n]), CTRL, ROW_MASK, 0xf, true));
-}
-
-template <int NV>
-__device__ __forceinline__ void piece_sums_n(double (&v)[NV], unsigned long long heads, bool head)
-{
-    const unsigned long long nh = ~heads;
-    if (nh == 0ull) return;
-    if (heads == 1ull) {  // one piece: plain sums over the wave, lane 63 holds them
-        wave_sum_step_n<0x111, 0xf>(v);
-        wave_sum_step_n<0x112, 0xf>(v);
-        wave_sum_step_n<0x114, 0xf>(v);
-        wave_sum_step_n<0x118, 0xf>(v);
-        wave_sum_step_n<0x142, 0xa>(v);
-        wave_sum_step_n<0x143, 0xc>(v);
-        return;
-    }
-    uint32_t f = head ? 1u : 0u;
-    seg_scan_step_n<0x111, 0xf>(v, f);
-    const unsigned long long r2 = nh & (nh >> 1);
-    if (r2 != 0ull) {
-        seg_scan_step_n<0x112, 0xf>(v, f);
-        const unsigned long long r4 = r2 & (r2 >> 2);
-        if (r4 != 0ull) {
-            seg_scan_step_n<0x114, 0xf>(v, f);
-            const unsigned long long r8 = r4 & (r4 >> 4);
-            if (r8 != 0ull) seg_scan_step_n<0x118, 0xf>(v, f);
-        }
-    }
-    if (nh & 0x0001000100010000ull) {
-        seg_scan_step_n<0x142, 0xa>(v, f);
-        seg_scan_step_n<0x143, 0xc>(v, f);
-    }
-}
-
-// NV doubles that lie side by side -- the NV values of one column in the interleaved panel image, the NV partial sums of one
-// slot, the NV accumulators of one row: 16-byte accesses where the address allows (NV = 2, 4: base 16-byte aligned, index a
-// multiple of 2), plain doubles for NV = 3.
-template <int NV>
-__device__ __forceinline__ void get_n(const double* p, double (&o)[NV])
-{
-    if constexpr (NV == 2 || NV == 4) {
-#pragma unroll
-        for (int h = 0; h < NV / 2; ++h) {
-            const double2 t = reinterpret_cast<const double2*>(p)[h];
-            o[2 * h] = t.x, o[2 * h + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int n = 0; n < NV; ++n) o[n] = p[n];
-    }
-}
-
-template <int NV>
-__device__ __forceinline__ void put_n(double* p, const double (&v)[NV])
-{
-    if constexpr (NV == 2 || NV == 4) {
-        typedef double dbl2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int h = 0; h < NV / 2; ++h) {
-            const dbl2 t = {v[2 * h], v[2 * h + 1]};
-            reinterpret_cast<dbl2*>(p)[h] = t;
-        }
-    } else {
-#pragma unroll
-        for (int n = 0; n < NV; ++n) p[n] = v[n];
-    }
-}
-
-template <int NV>
-__device__ __forceinline__ void get_n_nt(const double* p, double (&o)[NV])
-{
-    if constexpr (NV == 2 || NV == 4) {
-        typedef double dbl2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int h = 0; h < NV / 2; ++h) {
-            const dbl2 t = __builtin_nontemporal_load(reinterpret_cast<const dbl2*>(p) + h);
-            o[2 * h] = t.x, o[2 * h + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int n = 0; n < NV; ++n) o[n] = __builtin_nontemporal_load(p + n);
-    }
-}
-
-// SUMS_DPP (cfg.er_sums, the default): the products of a piece are added by the register scan above and the piece's
-// LAST lane stores the partial; false = round 2's way: ds_add_f64 into 64 LDS words per wave, the FIRST lane reads the
-// sum back and stores it (kept as the A/B arm: the LDS pipe of a CU was what bound pass 1 -- DESIGN.md 3.2).
-// xcd_map: workgroup b takes unit xcd_item(b): the units of one panel (neighbours in the unit list) then run on ONE XCD at
-// about the same time and stage their panel from its L2 instead of each from the fabric.
-// PROBE: the timing-diagnostics instantiation (ehyb_debug_panel_times only); the product's own launches run PROBE = false,
-// where every probe test folds away (they cost six vector instructions of ~70 per chunk).
-// KCH = chunks per wave and step (8: 24 independent vector loads in flight per lane at 4 waves per SIMD).
-// (Round 4 measured an instantiation for TWO 1024-thread workgroups per CU -- 9,728-column panels, KCH = 6, 59 VGPRs, 8 waves per SIMD, one
-// workgroup staging while the other streams: R-MAT 2^22 140 against 132 us, 2^24 665 against 574 us, profiles/r04_d_panel_two_ab.jsonl -- the
-// narrower panels' extra partial sums cost more than the occupancy gives; pass 1 alone ran level.  Removed again.)
-// NV = columns of X per pass (ehyb_spmm): the panel image is interleaved, win[c NV + j] = X[first + c + j ldx], and so are the
-// partial sums, partial[slot NV + j]; the decode of a chunk is done once for the NV products.  NV = 1 is the one-vector kernel.
-template <int THREADS, bool SUMS_DPP, bool PROBE, int KCH, int NV = 1>
-__device__ __forceinline__ void pb_scale_body(const int2* __restrict__ items, const int4* __restrict__ units,
-                                                                const double* __restrict__ val,
-                                                                const uint16_t* __restrict__ colf,
-                                                                const uint32_t* __restrict__ chunk,
-                                                                const uint32_t* __restrict__ jump,
-                                                                const double* __restrict__ x,
-                                                                double* __restrict__ partial, int panel_cols, int probe_arg, int xcd_map,
-                                                                int* __restrict__ queue, int n_items, int reverse, long long ldx = 0)
-{
-    static_assert(NV == 1 || (SUMS_DPP && !PROBE), "the K-wide pass 1 has register-scan sums and no probes");
-    const int probe = PROBE ? probe_arg : 0;
-    // probe (tools/panel_sweep.py, timing diagnostics only, results wrong): 1 no lane sums, 2 no stores,
-    // 4 no LDS gather, 8 no panel staging
-    extern __shared__ __attribute__((aligned(16))) double win[];
-    constexpr int WAVES = THREADS / 64;
-    // An ITEM = a run of units of (nearly) equal total cost, cut by the host (er_panel.cpp); every unit is a stretch of one
-    // panel's entries and stages that panel once.
-    // queue == null: one workgroup per item (workgroup b takes item xcd_item(b) / b).
-    // queue != null (cfg.er_queue = 1, an A/B arm -- see DESIGN.md 3.2): one RESIDENT round of workgroups, each taking items until none is left.  The
-    // hardware deals workgroups to the 8 XCDs round robin, so with one item per workgroup every XCD gets an eighth of the
-    // work whatever its speed -- and two of the eight XCDs of every box measured stream 8-12 % slower than the fastest, which
-    // the whole launch then waits for.  Here XCD k's workgroups take the items of the k-th contiguous eighth (queue[16 k] =
-    // items taken: the units of one panel still meet in one L2), and a workgroup whose own eighth is used up takes from the
-    // eighth with the most items left.  Exit: every workgroup leaves when every queue is empty (counts only grow); the last
-    // one to leave (queue[128] = workgroups gone) zeroes the counts for the next launch.
-    // (the item handed from thread 0 to the workgroup: one word behind the panel and the piece accumulators, in the dynamic
-    // allocation -- a static __shared__ word on top of a 160 KiB dynamic limit is refused by hipFuncSetAttribute)
-    int& s_item = *reinterpret_cast<int*>(win + NV * panel_cols + (SUMS_DPP ? 0 : THREADS));
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* scr = win + panel_cols + 64 * wave;  // this wave's 64 piece accumulators, behind the panel (!SUMS_DPP only)
-    if (!SUMS_DPP) scr[lane] = 0.0;
-    int staged_x = -1, staged_n = -1;  // the panel in this workgroup's LDS (first column, columns): wave-uniform
-    int my_q = 0;
-    if (queue != nullptr && threadIdx.x == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        my_q = (int)(xcc & 7u);
-    }
-  for (;;) {
-    int2 it;
-    if (queue != nullptr) {
-        __syncthreads();  // every wave is done with the previous item's panel, and with s_item
-        if (threadIdx.x == 0) {
-            int item = -1;
-            for (;;) {
-                const int first = (int)((long long)n_items * my_q / 8), len = (int)((long long)n_items * (my_q + 1) / 8) - first;
-                const int idx = len > 0 ? atomicAdd(&queue[16 * my_q], 1) : len;
-                if (idx < len) {
-                    item = reverse ? first + len - 1 - idx : first + idx;   // (alternating walk: every eighth from its far end)
-                    break;
-                }
-                int best = -1, most = 0;  // own eighth used up: the one with the most items left
-                for (int k = 0; k < 8; ++k) {
-                    const int lk = (int)((long long)n_items * (k + 1) / 8) - (int)((long long)n_items * k / 8);
-                    const int left = lk - __hip_atomic_load(&queue[16 * k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (left > most) most = left, best = k;
-                }
-                if (best < 0) break;  // nothing left anywhere
-                my_q = best;
-            }
-            s_item = item;
-        }
-        __syncthreads();
-        const int item = s_item;
-        if (item < 0) break;
-        it = items[item];
-    } else {
-        // reverse (successive launches alternate, as the ELL launch does): the items last to first, the units of an item last to
-        // first, a unit's chunks last to first -- this launch starts with what the one before it left in the Infinity Cache
-        const int idx = xcd_map ? xcd_item(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-        it = items[reverse ? (int)gridDim.x - 1 - idx : idx];
-    }
-  for (int ui = it.x; ui < it.y; ++ui) {
-    const int un = reverse ? it.y - 1 - (ui - it.x) : ui;
-    const int4 u = units[un];
-    // the panel this workgroup staged last is still in its LDS: a unit of the same panel (the next stretch of a hub panel's
-    // entries -- with the work queues a workgroup takes neighbouring items) streams straight away
-    const bool staged_already = u.x == staged_x && u.y == staged_n;
-    if (!staged_already && (ui != it.x || staged_n >= 0)) __syncthreads();  // every wave is done with the previous panel
-    staged_x = u.x, staged_n = u.y;
-    // stage the panel: all of a thread's loads in flight before the first store (a 64 KiB panel is 16
-    // double2 loads per thread; one load per loop trip would pay the memory latency 16 times)
-    if constexpr (NV > 1) {
-        // NV columns of X, interleaved: a thread takes the NV values of a column (each load coalesced along its own column of X,
-        // which may start on an odd double: plain 8-byte loads) and stores them side by side
-        if (!staged_already) {
-            constexpr int UN = NV == 2 ? 8 : 4;  // columns per thread and trip: 16 / 12 / 16 loads in flight
-            const double* __restrict__ xp = x + u.x;
-            for (int i0 = 0; i0 < u.y; i0 += UN * THREADS) {
-                double t[UN][NV];
-#pragma unroll
-                for (int j = 0; j < UN; ++j) {
-                    const int i = i0 + j * THREADS + (int)threadIdx.x;
-#pragma unroll
-                    for (int n = 0; n < NV; ++n) t[j][n] = i < u.y ? xp[i + n * ldx] : 0.0;
-                }
-#pragma unroll
-                for (int j = 0; j < UN; ++j) {
-                    const int i = i0 + j * THREADS + (int)threadIdx.x;
-                    if (i < u.y) put_n<NV>(win + (size_t)i * NV, t[j]);
-                }
-            }
-        }
-    } else
-    if (!(probe & 8) && !staged_already) {
-        const double2* __restrict__ xp2 = reinterpret_cast<const double2*>(x + u.x);  // panels start on even columns
-        double2* win2 = reinterpret_cast<double2*>(win);
-        const int n2 = u.y >> 1;
-        for (int i0 = 0; i0 < n2; i0 += 8 * THREADS) {
-            double2 t[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = i0 + j * THREADS + (int)threadIdx.x;
-                t[j] = i < n2 ? xp2[i] : double2{0.0, 0.0};
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = i0 + j * THREADS + (int)threadIdx.x;
-                if (i < n2) win2[i] = t[j];
-            }
-        }
-        if ((u.y & 1) && threadIdx.x == 0) win[u.y - 1] = x[u.x + u.y - 1];
-    }
-    if (!staged_already) __syncthreads();
-    const int c0 = u.z >> 6, c1 = u.w >> 6;  // chunks of 64 entries
-    constexpr int K = KCH;  // chunks per wave and step: 24 independent vector loads in flight per lane at K = 8
-    // The jump-list range of a chunk is known from the chunk records alone (wave-uniform, scalar loads): they are
-    // fetched one step ahead, so that the jump entries travel together with the values and column words instead
-    // of behind them (a gather that waits for the flags doubled the latency per step: 345 -> 470 us on R-MAT 2^24).
-    uint32_t f0[K], fn[K];
-    // the wave's steps: chunks c0 + K (wave + t WAVES) .., t = 0 .. steps - 1, walked up or down
-    const int first = c0 + K * wave;
-    const int steps = first < c1 ? (c1 - first + K * WAVES - 1) / (K * WAVES) : 0;
-    const int dc = reverse ? -K * WAVES : K * WAVES;
-    const int cstart = reverse ? first + (steps - 1) * K * WAVES : first;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const int cj = max(c0, min(cstart + j, c1 - 1));
-        f0[j] = chunk[cj];
-        fn[j] = chunk[cj + 1] - f0[j];
-    }
-    int c = cstart;
-    for (int t = 0; t < steps; ++t, c += dc) {
-        double v[K];
-        uint32_t cw[K], jv[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int cj = c + j < c1 ? c + j : c;  // wave-uniform
-            const size_t pos = (size_t)cj * 64 + lane;
-            // (streamed past the caches: every entry is read once per multiply, and what the caches hold instead -- the x panels the units of a
-            // hub panel stage again and again, the partial sums pass 2 is about to read -- is read again.  R-MAT 2^22: 128.0 -> 124.0 us)
-            v[j] = __builtin_nontemporal_load(&val[pos]);
-            cw[j] = __builtin_nontemporal_load(&colf[pos]);
-            jv[j] = (uint32_t)lane < fn[j] ? jump[f0[j] + lane] : 0u;  // lane l: the chunk's l-th jump entry
-        }
-        uint32_t g0[K], gn[K];  // the records of the next step
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int cj = max(c0, min(c + dc + j, c1 - 1));
-            g0[j] = chunk[cj];
-            gn[j] = chunk[cj + 1] - g0[j];
-        }
-        uint32_t slot[K], piece[K];
-        unsigned long long hd[K];
-        double xw[K][NV];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const bool head = (cw[j] & 0x8000u) != 0, jmp = (cw[j] & 0x4000u) != 0;
-            const unsigned long long heads = __ballot(head), jumps = __ballot(jmp);
-            // pieces / jumps begun in the lanes below this one (v_mbcnt), plus its own
-            const uint32_t hc = __builtin_amdgcn_mbcnt_hi((uint32_t)(heads >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)heads, 0u)) + (head ? 1u : 0u);
-            const uint32_t jc = __builtin_amdgcn_mbcnt_hi((uint32_t)(jumps >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)jumps, 0u)) + (jmp ? 1u : 0u);
-            // the entry of the last jump at or below this lane sits in lane jc - 1 (lane 0 is always a jump)
-            const uint32_t base = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((jc - 1u) << 2), (int)jv[j]);
-            piece[j] = hc - 1u;
-            // who stores the partial: the piece's last lane (register scan) or its first (LDS sums); every lane of a piece
-            // computes the same slot.  0xFFFFFFFF: nothing to store (also what the padding piece yields)
-            const bool stores = SUMS_DPP ? (lane == 63 || ((heads >> (lane + 1)) & 1ull)) : head;
-            slot[j] = stores ? base + hc - 1u : 0xFFFFFFFFu;
-            hd[j] = heads;
-            const uint32_t cl = cw[j] & 0x3FFFu;
-            if constexpr (NV == 1)
-                xw[j][0] = (probe & 4) ? (double)cl : win[cl];
-            else
-                get_n<NV>(win + cl * NV, xw[j]);
-            cw[j] = (heads == ~0ull ? 1u : 0u) | (head ? 2u : 0u);  // bit 0: every lane its own piece, no sums needed
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if constexpr (NV > 1) {
-                if (c + j < c1) {  // wave-uniform
-                    double sum[NV];
-#pragma unroll
-                    for (int n = 0; n < NV; ++n) sum[n] = v[j] * xw[j][n];
-                    piece_sums_n<NV>(sum, hd[j], (cw[j] & 2u) != 0);
-                    if (slot[j] != 0xFFFFFFFFu) put_n<NV>(partial + (size_t)slot[j] * NV, sum);
-                }
-            } else
-            if (c + j < c1) {  // wave-uniform
-                const double prod = v[j] * xw[j][0];
-                double sum = prod;
-                if (SUMS_DPP) {
-                    if (!(probe & 1)) sum = piece_sums(prod, hd[j], (cw[j] & 2u) != 0);
-                } else if (!(cw[j] & 1u) && !(probe & 1)) {
-                    // Some lanes share a slot: the piece sums are formed in this wave's 64 LDS words (zero between
-                    // uses), one ds_add_f64 per lane, one read + one store of zero per piece.  (Shuffle trees --
-                    // six ds_bpermute rounds per chunk -- cost 17 us of a 127 us launch here and 17 of 80 in pass 2.)
-                    unsafeAtomicAdd(&scr[piece[j]], prod);
-                    if (slot[j] != 0xFFFFFFFFu) sum = scr[piece[j]];
-                    __builtin_amdgcn_wave_barrier();
-                    scr[piece[j]] = 0.0;
-                }
-                if (slot[j] != 0xFFFFFFFFu && (!(probe & 2) || sum == 123.456)) {
-                    if (probe & 256)
-                        __builtin_nontemporal_store(sum, &partial[slot[j]]);
-                    else
-                        partial[slot[j]] = sum;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) f0[j] = g0[j], fn[j] = gn[j];
-    }
-  }
-    if (queue == nullptr) break;
-  }
-    if (queue != nullptr && threadIdx.x == 0 && atomicAdd(&queue[128], 1) == (int)gridDim.x - 1) {
-        for (int k = 0; k < 8; ++k) __hip_atomic_store(&queue[16 * k], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&queue[128], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
+// ------------------------------------------------------------------ panel residual (bodies: panel_device.h)
+// Pass 1, one vector: SUMS_DPP = the register scan (false: the LDS-sum A/B arm), PROBE = the timing-diagnostics instantiation;
+// eight chunks per wave and step.
 template <int THREADS, bool SUMS_DPP, bool PROBE>
 __global__ __launch_bounds__(THREADS) void ehyb_pb_scale_kernel(const int2* __restrict__ items, const int4* __restrict__ units, const double* __restrict__ val,
                                                                 const uint16_t* __restrict__ colf, const uint32_t* __restrict__ chunk,
@@ -528,113 +120,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
                                                                             reverse, ldx);
 }
 
-// Pass 2: one workgroup per unit {first partial, end partial, first row, rows}.  The row block's
-// accumulators live in LDS; (partial, 16-bit local row) are streamed and added (ds_add_f64); finally
-// y[row] += accumulator for the rows that received something (the ELL launch has written y before) -- or,
-// for a block of rows whose partitions have no window (rows < 0 in the unit), y[row] = accumulator for
-// every row: the ELL launch leaves those rows alone.
-// NT: the partial sums and their row words are streamed past the caches -- where they are more than the Infinity Cache can hold between the
-// passes anyway (R-MAT 2^24: 460 MB; 520 -> 487 us with it, because the next multiply then finds more of the entry stream's tail there);
-// where they fit (2^22: 89 MB) pass 2 reads them from that cache and the hint costs 3 us.
-// The write-back of pass 2 for one column: the accumulators of the block's rows, NV doubles apart in LDS.
-template <int THREADS, int NV>
-__device__ __forceinline__ void pb_write_back(double* __restrict__ yp, const double* yacc, int rows, bool assign, int probe)
-{
-    constexpr int K = 8;
-    // y[row] += accumulator for the rows that received something: the loads of a batch first, then the stores
-    if (probe & 64) return;
-    if (assign) {
-        for (int i = threadIdx.x; i < rows; i += THREADS) yp[i] = yacc[i * NV];
-        return;
-    }
-    for (int i0 = 0; i0 < rows; i0 += K * THREADS) {
-        double a[K], yo[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int i = i0 + j * THREADS + (int)threadIdx.x;
-            a[j] = i < rows ? yacc[i * NV] : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int i = i0 + j * THREADS + (int)threadIdx.x;
-            yo[j] = a[j] != 0.0 ? yp[i] : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const int i = i0 + j * THREADS + (int)threadIdx.x;
-            if (a[j] != 0.0) yp[i] = yo[j] + a[j];
-        }
-    }
-}
-
-// NV columns (ehyb_spmm): partial[slot NV + j], accumulators yacc[row NV + j], one row word per slot for the NV adds; NV = 1 is the
-// one-vector kernel.
-template <int THREADS, bool NT, int NV>
-__device__ __forceinline__ void pb_reduce_body(const int4* __restrict__ units, const double* __restrict__ partial, const uint16_t* __restrict__ row,
-                                               double* __restrict__ y, long long ldy, int probe)
-{
-    // probe (timing diagnostics only): 16 no lane sums, 32 no LDS adds, 64 no write-back, 128 no zeroing
-    extern __shared__ __attribute__((aligned(16))) double yacc[];
-    int4 u = units[blockIdx.x];
-    const bool assign = u.w < 0;  // the block is the only writer of its rows (partitions without a window): y = sum, zeros included
-    u.w = assign ? -u.w : u.w;
-    if (!(probe & 128))
-        for (int i = threadIdx.x; i < u.w * NV; i += THREADS) yacc[i] = 0.0;
-    __syncthreads();
-    constexpr int KP = NV == 1 ? 8 : NV == 2 ? 4 : 2;  // partials per thread and step: 16 (12 for three columns) independent loads in flight
-    // every wave runs the same number of steps (the shuffles need all 64 lanes)
-    for (int base = u.x; base < u.y; base += KP * THREADS) {
-        double v[KP][NV];
-        uint32_t r[KP];
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const int i = base + j * THREADS + (int)threadIdx.x;
-            const bool in = i < u.y;
-            if constexpr (NV == 1) {
-                if (NT) {
-                    v[j][0] = in ? __builtin_nontemporal_load(&partial[i]) : 0.0;
-                    r[j] = in ? (uint32_t)__builtin_nontemporal_load(&row[i]) : 0xFFFFFFFFu;
-                } else {
-                    v[j][0] = in ? partial[i] : 0.0;
-                    r[j] = in ? (uint32_t)row[i] : 0xFFFFFFFFu;
-                }
-            } else {
-                const int ic = in ? i : u.x;  // (in range: u.x < u.y inside the loop)
-                if (NT) {
-                    get_n_nt<NV>(partial + (size_t)ic * NV, v[j]);
-                    r[j] = in ? (uint32_t)__builtin_nontemporal_load(&row[i]) : 0xFFFFFFFFu;
-                } else {
-                    get_n<NV>(partial + (size_t)ic * NV, v[j]);
-                    r[j] = in ? (uint32_t)row[i] : 0xFFFFFFFFu;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            // (summing equal neighbouring rows across lanes first was measured: 17 us of an 80 us launch
-            // for nothing -- the LDS adds serialise the few same-row neighbours by themselves)
-            if constexpr (NV == 1) {
-                if (r[j] != 0xFFFFFFFFu && (!(probe & 32) || v[j][0] == 123.456)) unsafeAtomicAdd(&yacc[r[j]], v[j][0]);  // ds_add_f64
-            } else if (r[j] != 0xFFFFFFFFu) {
-#pragma unroll
-                for (int n = 0; n < NV; ++n) unsafeAtomicAdd(&yacc[r[j] * NV + n], v[j][n]);
-            }
-        }
-    }
-    __syncthreads();
-    if constexpr (NV == 1) {
-        pb_write_back<THREADS, 1>(y + u.z, yacc, u.w, assign, probe);
-    } else {
-#pragma unroll
-        for (int n = 0; n < NV; ++n) pb_write_back<THREADS, NV>(y + u.z + n * ldy, yacc + n, u.w, assign, 0);
-    }
-}
-
+// Pass 2 (NT: partial sums and row words streamed past the caches)
 template <int THREADS, bool NT>
-__global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_kernel(const int4* __restrict__ units,
-                                                                 const double* __restrict__ partial,
-                                                                 const uint16_t* __restrict__ row,
-                                                                 double* __restrict__ y, int probe)
+__global__ __launch_bounds__(THREADS) void ehyb_pb_reduce_kernel(const int4* __restrict__ units, const double* __restrict__ partial,
+                                                                 const uint16_t* __restrict__ row, double* __restrict__ y, int probe)
 {
     pb_reduce_body<THREADS, NT, 1>(units, partial, row, y, 0, probe);
 }
@@ -895,7 +384,105 @@ int ehyb::spmv_xy(ehyb_plan* P, const double* x, double* y, void* stream, double
     return launch_window(P, x, 0, y, 0, 1, (hipStream_t)stream, P->host.inline_er, t_walk, nullptr, xy_partials);
 }
 
-// which: 1 = pass 1 (scale), 2 = pass 2 (reduce), 3 = both; pass 1 over the items [unit_begin, unit_end) (-1: all)
+// ---- panel residual
+// Every instantiation of the two passes: pass 1 in both workgroup sizes -- one vector with register-scan or LDS sums (dpp), plain
+// and with the timing probes; k = 2..kSpmmMaxK with register-scan sums only --, pass 2 with and without the streaming hint (nt)
+// for every k.  Behind both launches and the LDS opt-in of ehyb_plan_upload.  (A field its pass does not have holds one value.)
+struct PanelKernel { int pass, threads, k; bool dpp, probe, nt; const void* fn; };
+
+template <int T>
+static void add_panel_scale_kernels(std::vector<PanelKernel>* v)
+{
+    v->insert(v->end(), {{1, T, 1, true, false, false, (const void*)ehyb_pb_scale_kernel<T, true, false>}, {1, T, 1, false, false, false, (const void*)ehyb_pb_scale_kernel<T, false, false>},
+                         {1, T, 1, true, true, false, (const void*)ehyb_pb_scale_kernel<T, true, true>}, {1, T, 1, false, true, false, (const void*)ehyb_pb_scale_kernel<T, false, true>},
+                         {1, T, 2, true, false, false, (const void*)ehyb_pb_scale_k_kernel<T, 2>}, {1, T, 3, true, false, false, (const void*)ehyb_pb_scale_k_kernel<T, 3>},
+                         {1, T, 4, true, false, false, (const void*)ehyb_pb_scale_k_kernel<T, 4>}});
+}
+template <bool NT>
+static void add_panel_reduce_kernels(std::vector<PanelKernel>* v)
+{
+    v->insert(v->end(), {{2, 512, 1, true, false, NT, (const void*)ehyb_pb_reduce_kernel<512, NT>}, {2, 512, 2, true, false, NT, (const void*)ehyb_pb_reduce_k_kernel<512, NT, 2>},
+                         {2, 512, 3, true, false, NT, (const void*)ehyb_pb_reduce_k_kernel<512, NT, 3>}, {2, 512, 4, true, false, NT, (const void*)ehyb_pb_reduce_k_kernel<512, NT, 4>}});
+}
+
+static const std::vector<PanelKernel>& panel_kernels()
+{
+    static const std::vector<PanelKernel> all = [] {
+        std::vector<PanelKernel> v;
+        add_panel_scale_kernels<512>(&v), add_panel_scale_kernels<1024>(&v);
+        add_panel_reduce_kernels<false>(&v), add_panel_reduce_kernels<true>(&v);
+        return v;
+    }();
+    return all;
+}
+
+// (each pass is looked up by the fields it has)
+static const void* panel_scale_kernel(int threads, int k, bool dpp, bool probe)
+{
+    for (const PanelKernel& e : panel_kernels())
+        if (e.pass == 1 && e.threads == threads && e.k == k && e.dpp == dpp && e.probe == probe) return e.fn;
+    return nullptr;
+}
+static const void* panel_reduce_kernel(int k, bool nt)
+{
+    for (const PanelKernel& e : panel_kernels())
+        if (e.pass == 2 && e.k == k && e.nt == nt) return e.fn;
+    return nullptr;
+}
+
+// Dynamic LDS of a pass-1 launch: k interleaved panel images, the waves' piece accumulators (LDS sums only) and the word in which
+// thread 0 hands over the item; of a pass-2 launch: k accumulators per row of the largest row block.
+static size_t panel_scale_lds_bytes(const HostLayout& H, int k, bool dpp, int threads) { return ((size_t)k * H.pb_panel_cols + (dpp ? 0 : threads) + 1) * 8; }
+static size_t panel_reduce_lds_bytes(const HostLayout& H, int k) { return (size_t)H.pb_rows_max * k * 8; }
+
+static int panel_items(const HostLayout& H) { return (int)(H.pb_items1.size() / 2); }
+
+// Pass 1 (scale) over the items [item_begin, item_end) for k columns of x, ldx doubles apart; probe: ehyb_debug_panel_times only.
+// (k > 1, ehyb_spmm: register-scan sums whatever cfg.er_sums says -- the LDS-sum A/B arm is one vector wide -- and no probes)
+static int launch_panel_scale(ehyb_plan* P, const double* x, long long ldx, int k, hipStream_t st, int probe, int item_begin, int item_end)
+{
+    const HostLayout& H = P->host;
+    if (item_begin < 0 || item_end > panel_items(H) || item_begin > item_end) EHYB_FAIL(EHYB_ERR_ARG, "panel launch: items [%d, %d) of %d", item_begin, item_end, panel_items(H));
+    int n_items = item_end - item_begin;
+    if (n_items > 0) {
+        // panels of up to 9,728 columns: two 512-thread workgroups per CU (one stages while the other streams); wider
+        // panels leave room for one workgroup only, which then gets the CU's 16 waves
+        // (on the LDS the launch really takes: k interleaved panel images)
+        const bool wide = P->cfg.er_panel_threads ? P->cfg.er_panel_threads == 1024 : (int64_t)k * H.pb_panel_cols > 9728;
+        const int threads = wide ? 1024 : 512;
+        const bool dpp = k > 1 || P->cfg.er_sums != 2;
+        int xcd = P->cfg.xcd_map != 2 ? 1 : 0;
+        // cfg.er_queue: one resident round of workgroups taking items from per-XCD queues (with stealing) instead of one
+        // workgroup per item; needs the XCD map's contiguous eighths, and more items than workgroups to be worth it
+        const int resident = kNumCU * (wide ? 1 : 2);
+        // (automatic, cfg.er_queue = 0: from six items per resident workgroup up -- a workgroup that takes neighbouring items finds the panel
+        // of the previous one still staged, and the XCDs even out: R-MAT 2^24 574 -> 544 us; with three or four items per workgroup the two
+        // barriers and the atomic round trip per item cost more than that: 2^22 132 -> 138 us.  profiles/r04_d_panel_two_ab.jsonl)
+        const bool want_queue = P->cfg.er_queue == 1 || (P->cfg.er_queue == 0 && n_items >= 6 * resident);
+        int* queue = (want_queue && xcd && n_items > resident) ? P->d_pb_queue : nullptr;
+        const int grid = queue ? resident : n_items;
+        // successive launches walk the entry stream in alternating directions (cfg.ell_alternate) where it does not fit the cache
+        int rev = 0;
+        if (!probe && (t_walk >= 0 || P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.pb_bytes > kInfinityCache))) {
+            // one direction per MULTIPLY: a multiply in parts (ehyb_spmv_part: one pass-1 launch per column segment) turns around
+            // with its first part
+            if (t_walk >= 0) rev = t_walk & 1;
+            else if (item_begin == 0) rev = (P->panel_parity.fetch_xor(1, std::memory_order_relaxed) ^ 1) & 1;
+            else rev = P->panel_parity.load(std::memory_order_relaxed) & 1;
+        }
+        const void* fn = panel_scale_kernel(threads, k, dpp, probe != 0);
+        if (!fn) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 1 not built for %d threads, %d columns%s", threads, k, probe ? " with probes" : "");
+        const int2* items = (const int2*)P->d_pb_items1 + item_begin;
+        const int4* units = (const int4*)P->d_pb_units1;
+        int panel_cols = H.pb_panel_cols;
+        void* args1[] = {&items, &units, &P->d_pb_val, &P->d_pb_colf, &P->d_pb_chunk, &P->d_pb_jump, &x, &P->d_pb_partial, &panel_cols, &probe, &xcd, &queue, &n_items, &rev};
+        void* argsk[] = {&items, &units, &P->d_pb_val, &P->d_pb_colf, &P->d_pb_chunk, &P->d_pb_jump, &x, &ldx, &P->d_pb_partial, &panel_cols, &xcd, &queue, &n_items, &rev};
+        (void)hipLaunchKernel(fn, dim3(grid), dim3(threads), k == 1 ? args1 : argsk, panel_scale_lds_bytes(H, k, dpp, threads), st);
+    }
+    HIP_TRY(hipGetLastError());  // (as <<< >>>: a failed launch is the last error)
+    return EHYB_OK;
+}
+
 // first pass-2 unit whose rows lie at or behind cfg.row_split (= number of units: no split)
 static int pass2_split(const ehyb_plan* P)
 {
@@ -911,98 +498,38 @@ static int pass2_split(const ehyb_plan* P)
     return lo;
 }
 
-// u2_part (pass 2): 0 = every row block, 1 = the blocks in front of cfg.row_split, 2 = the blocks from it on
-// k = 2..spmm_width(H) columns ldx / ldy doubles apart (ehyb_spmm): both passes k wide; no probes there.
-static int launch_panel(ehyb_plan* P, const double* x, double* y, hipStream_t st, int probe, int which, int unit_begin = 0, int unit_end = -1, int u2_part = 0,
-                        long long ldx = 0, long long ldy = 0, int k = 1)
+// the row blocks a pass-2 launch covers: all, those in front of cfg.row_split, those from it on
+enum PanelRows { PANEL_ROWS_ALL = 0, PANEL_ROWS_BEFORE_SPLIT = 1, PANEL_ROWS_FROM_SPLIT = 2 };
+
+// Pass 2 (reduce) into k columns of y, ldy doubles apart; probe: ehyb_debug_panel_times only.
+static int launch_panel_reduce(ehyb_plan* P, double* y, long long ldy, int k, hipStream_t st, int probe, PanelRows part)
 {
     const HostLayout& H = P->host;
-    // (k > 1: register-scan sums whatever cfg.er_sums says -- the LDS-sum A/B arm is one vector wide -- and no probes)
-    if (k < 1 || k > spmm_width(H) || (k > 1 && probe)) EHYB_FAIL(EHYB_ERR_ARG, "launch_panel: %d columns on a plan whose panel passes serve %d", k, spmm_width(H));
-    const int u_all = (int)(H.pb_items1.size() / 2), u2_all = (int)(H.pb_units2.size() / 4);
-    const int u2_cut = u2_part ? pass2_split(P) : 0;
-    const int u2_first = u2_part == 2 ? u2_cut : 0, u2 = (u2_part == 1 ? u2_cut : u2_all) - u2_first;
-    if (unit_end < 0) unit_end = u_all;
-    if (unit_begin < 0 || unit_end > u_all || unit_begin > unit_end) EHYB_FAIL(EHYB_ERR_ARG, "launch_panel: items [%d, %d) of %d", unit_begin, unit_end, u_all);
-    const int u1 = unit_end - unit_begin;
-    if ((which & 1) && u1 > 0) {
-        // panels of up to 9,728 columns: two 512-thread workgroups per CU (one stages while the other streams); wider
-        // panels leave room for one workgroup only, which then gets the CU's 16 waves
-        // (on the LDS the launch really takes: k interleaved panel images)
-        const bool wide = P->cfg.er_panel_threads ? P->cfg.er_panel_threads == 1024 : (int64_t)k * H.pb_panel_cols > 9728;
-        const bool dpp = P->cfg.er_sums != 2;
-        const int xcd = P->cfg.xcd_map != 2 ? 1 : 0;
-        // cfg.er_queue: one resident round of workgroups taking items from per-XCD queues (with stealing) instead of one
-        // workgroup per item; needs the XCD map's contiguous eighths, and more items than workgroups to be worth it
-        const int resident = kNumCU * (wide ? 1 : 2);
-        // (automatic, cfg.er_queue = 0: from six items per resident workgroup up -- a workgroup that takes neighbouring items finds the panel
-        // of the previous one still staged, and the XCDs even out: R-MAT 2^24 574 -> 544 us; with three or four items per workgroup the two
-        // barriers and the atomic round trip per item cost more than that: 2^22 132 -> 138 us.  profiles/r04_d_panel_two_ab.jsonl)
-        const bool want_queue = P->cfg.er_queue == 1 || (P->cfg.er_queue == 0 && u1 >= 6 * resident);
-        int* queue = (want_queue && xcd && u1 > resident) ? P->d_pb_queue : nullptr;
-        const int grid = queue ? resident : u1;
-        // successive launches walk the entry stream in alternating directions (cfg.ell_alternate) where it does not fit the cache
-        int rev = 0;
-        if (!probe && (t_walk >= 0 || P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && H.pb_bytes > (256ll << 20)))) {
-            // one direction per MULTIPLY: a multiply in parts (ehyb_spmv_part: one pass-1 launch per column segment) turns around
-            // with its first part
-            if (t_walk >= 0) rev = t_walk & 1;
-            else if (unit_begin == 0) rev = (P->panel_parity.fetch_xor(1, std::memory_order_relaxed) ^ 1) & 1;
-            else rev = P->panel_parity.load(std::memory_order_relaxed) & 1;
-        }
-#define PB_SCALE_P(T, D, PR)                                                                                                    \
-    hipLaunchKernelGGL((ehyb_pb_scale_kernel<T, D, PR>), dim3(grid), dim3(T), (size_t)(H.pb_panel_cols + ((D) ? 0 : (T)) + 1) * 8, st, (const int2*)P->d_pb_items1 + unit_begin, (const int4*)P->d_pb_units1, \
-                       P->d_pb_val, P->d_pb_colf, P->d_pb_chunk, P->d_pb_jump, x, P->d_pb_partial, H.pb_panel_cols, probe, xcd, queue, u1, rev)
-#define PB_SCALE(T, D)                  \
-    if (probe) PB_SCALE_P(T, D, true);  \
-    else PB_SCALE_P(T, D, false)
-#define PB_SCALE_K(T, NV)                                                                                                                                   \
-    hipLaunchKernelGGL((ehyb_pb_scale_k_kernel<T, NV>), dim3(grid), dim3(T), ((size_t)(NV) * H.pb_panel_cols + 1) * 8, st, (const int2*)P->d_pb_items1 + unit_begin, \
-                       (const int4*)P->d_pb_units1, P->d_pb_val, P->d_pb_colf, P->d_pb_chunk, P->d_pb_jump, x, ldx, P->d_pb_partial, H.pb_panel_cols, xcd, queue, u1, rev)
-        if (k > 1) {
-            if (wide) {
-                if (k == 2) PB_SCALE_K(1024, 2); else if (k == 3) PB_SCALE_K(1024, 3); else PB_SCALE_K(1024, 4);
-            } else {
-                if (k == 2) PB_SCALE_K(512, 2); else if (k == 3) PB_SCALE_K(512, 3); else PB_SCALE_K(512, 4);
-            }
-        } else if (wide) {
-            if (dpp) { PB_SCALE(1024, true); } else { PB_SCALE(1024, false); }
-        } else {
-            if (dpp) { PB_SCALE(512, true); } else { PB_SCALE(512, false); }
-        }
-#undef PB_SCALE_K
-#undef PB_SCALE
-#undef PB_SCALE_P
-    }
-    if ((which & 2) && u2 > 0) {
-        // (cfg.er_nt: 0 = by the size of what pass 2 reads -- 8 B per column and 2 B of row word per partial sum -- against half the 256 MB
+    const int cut = part != PANEL_ROWS_ALL ? pass2_split(P) : 0;
+    const int first = part == PANEL_ROWS_FROM_SPLIT ? cut : 0;
+    const int n_units = (part == PANEL_ROWS_BEFORE_SPLIT ? cut : (int)(H.pb_units2.size() / 4)) - first;
+    if (n_units > 0) {
+        // (cfg.er_nt: 0 = by the size of what pass 2 reads -- 8 B per column and 2 B of row word per partial sum -- against half the
         // Infinity Cache, 1 / 2 = always / never)
-        const bool nt = P->cfg.er_nt == 1 || (P->cfg.er_nt == 0 && H.pb_partials * (8 * k + 2) > (128ll << 20));
-#define PB_REDUCE_K(NT, NV)                                                                                                                                       \
-    hipLaunchKernelGGL((ehyb_pb_reduce_k_kernel<512, NT, NV>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * (NV) * 8, st, (const int4*)P->d_pb_units2 + u2_first, \
-                       P->d_pb_partial, P->d_pb_row, y, ldy)
-        if (k > 1) {
-            if (nt) {
-                if (k == 2) PB_REDUCE_K(true, 2); else if (k == 3) PB_REDUCE_K(true, 3); else PB_REDUCE_K(true, 4);
-            } else {
-                if (k == 2) PB_REDUCE_K(false, 2); else if (k == 3) PB_REDUCE_K(false, 3); else PB_REDUCE_K(false, 4);
-            }
-        } else if (nt)
-            hipLaunchKernelGGL((ehyb_pb_reduce_kernel<512, true>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * 8, st, (const int4*)P->d_pb_units2 + u2_first,
-                               P->d_pb_partial, P->d_pb_row, y, probe);
-        else
-            hipLaunchKernelGGL((ehyb_pb_reduce_kernel<512, false>), dim3(u2), dim3(512), (size_t)H.pb_rows_max * 8, st, (const int4*)P->d_pb_units2 + u2_first,
-                               P->d_pb_partial, P->d_pb_row, y, probe);
+        const bool nt = P->cfg.er_nt == 1 || (P->cfg.er_nt == 0 && H.pb_partials * (8 * k + 2) > kInfinityCache / 2);
+        const void* fn = panel_reduce_kernel(k, nt);
+        if (!fn || (k > 1 && probe)) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 2 not built for %d columns%s", k, probe ? " with probes" : "");
+        const int4* units = (const int4*)P->d_pb_units2 + first;
+        void* args1[] = {&units, &P->d_pb_partial, &P->d_pb_row, &y, &probe};
+        void* argsk[] = {&units, &P->d_pb_partial, &P->d_pb_row, &y, &ldy};
+        (void)hipLaunchKernel(fn, dim3(n_units), dim3(512), k == 1 ? args1 : argsk, panel_reduce_lds_bytes(H, k), st);
     }
-#undef PB_REDUCE_K
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
 
 int ehyb::launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, int walk)
 {
+    const int width = spmm_width(P->host);
+    if (k < 1 || k > width) EHYB_FAIL(EHYB_ERR_ARG, "launch_panel_k: %d columns on a plan whose panel passes serve %d", k, width);
     WalkScope w(walk);  // reaches pass 1 the way ehyb_spmv_walk's does
-    return launch_panel(P, x, y, st, 0, 3, 0, -1, 0, ldx, ldy, k);
+    const int rc = launch_panel_scale(P, x, ldx, k, st, 0, 0, panel_items(P->host));
+    return rc != EHYB_OK ? rc : launch_panel_reduce(P, y, ldy, k, st, 0, PANEL_ROWS_ALL);
 }
 
 int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st)
@@ -1027,7 +554,7 @@ int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y,
 static int launch_er(ehyb_plan* P, const double* x, double* y, hipStream_t st)
 {
     if (P->host.er_panel)  // panel form: scale (x panels in LDS) then reduce (y blocks in LDS)
-        return launch_panel(P, x, y, st, 0, 3);  // (probe arms only through ehyb_debug_panel_times)
+        return launch_panel_k(P, x, 0, y, 0, 1, st, t_walk);  // (t_walk: the scope it opens changes nothing -- the caller's walk stays)
     return launch_er_csr(P, x, 0, y, 0, 1, st);
 }
 
@@ -1337,10 +864,11 @@ int ehyb_debug_panel_times(ehyb_plan* P, const double* x, double* y, int iters, 
     HIP_TRY(hipEventCreate(&b));
     double* out[2] = {ms_scale, ms_reduce};
     int rc = EHYB_OK;
+    const auto launch = [&](int pass) { return pass == 1 ? launch_panel_scale(P, x, 0, 1, nullptr, probe, 0, panel_items(P->host)) : launch_panel_reduce(P, y, 0, 1, nullptr, probe, PANEL_ROWS_ALL); };
     for (int which = 1; which <= 2 && rc == EHYB_OK; ++which) {
-        for (int i = 0; i < 3 && rc == EHYB_OK; ++i) rc = launch_panel(P, x, y, nullptr, probe, which);
+        for (int i = 0; i < 3 && rc == EHYB_OK; ++i) rc = launch(which);
         (void)hipEventRecord(a, nullptr);
-        for (int i = 0; i < iters && rc == EHYB_OK; ++i) rc = launch_panel(P, x, y, nullptr, probe, which);
+        for (int i = 0; i < iters && rc == EHYB_OK; ++i) rc = launch(which);
         (void)hipEventRecord(b, nullptr);
         (void)hipEventSynchronize(b);
         float ms = 0;
@@ -1410,29 +938,9 @@ int ehyb_plan_upload(ehyb_plan* P)
     // attribute belongs to the kernel, not to a plan: it is set to the device maximum, so plans with
     // windows of different sizes can live side by side in one process.
     const int lds = EHYB_LDS_MAX_DOUBLES * 8;
-#define LDS_ATTR(K) HIP_TRY(hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     for (const EllKernel& e : ell_kernels())
-        if (!e.stamp) LDS_ATTR(e.fn)  // (a stamped launch opts in itself)
-    LDS_ATTR((ehyb_pb_scale_kernel<512, true, false>))
-    LDS_ATTR((ehyb_pb_scale_kernel<512, false, false>))
-    LDS_ATTR((ehyb_pb_scale_kernel<1024, true, false>))
-    LDS_ATTR((ehyb_pb_scale_kernel<1024, false, false>))
-    LDS_ATTR((ehyb_pb_scale_kernel<512, true, true>))
-    LDS_ATTR((ehyb_pb_scale_kernel<512, false, true>))
-    LDS_ATTR((ehyb_pb_scale_kernel<1024, true, true>))
-    LDS_ATTR((ehyb_pb_scale_kernel<1024, false, true>))
-    LDS_ATTR((ehyb_pb_reduce_kernel<512, true>))
-    LDS_ATTR((ehyb_pb_reduce_kernel<512, false>))
-#define LDS_ATTR_K(NV)                                   \
-    LDS_ATTR((ehyb_pb_scale_k_kernel<512, NV>))          \
-    LDS_ATTR((ehyb_pb_scale_k_kernel<1024, NV>))         \
-    LDS_ATTR((ehyb_pb_reduce_k_kernel<512, true, NV>))   \
-    LDS_ATTR((ehyb_pb_reduce_k_kernel<512, false, NV>))
-    LDS_ATTR_K(2)
-    LDS_ATTR_K(3)
-    LDS_ATTR_K(4)
-#undef LDS_ATTR_K
-#undef LDS_ATTR
+        if (!e.stamp) HIP_TRY(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));  // (a stamped launch opts in itself)
+    for (const PanelKernel& e : panel_kernels()) HIP_TRY(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     P->uploaded = true;
     return EHYB_OK;
 }
@@ -1574,18 +1082,18 @@ int ehyb_spmv_part(ehyb_plan* P, const double* x, double* y, void* stream, int s
     if (rc != EHYB_OK || (H.er_bins[3] == 0 && !H.er_panel)) return rc;
     if (!H.er_panel) return (flags & EHYB_PART_LAST) ? launch_er(P, x, y, st) : EHYB_OK;  // CSR residual: one launch, needs all of x
     if (seg_end > seg_begin) {
-        const int ub = H.pb_seg_item.empty() ? 0 : H.pb_seg_item[(size_t)seg_begin];
-        const int ue = H.pb_seg_item.empty() ? -1 : H.pb_seg_item[(size_t)seg_end];
-        rc = launch_panel(P, x, y, st, 0, 1, ub, ue);
+        const int ib = H.pb_seg_item.empty() ? 0 : H.pb_seg_item[(size_t)seg_begin];
+        const int ie = H.pb_seg_item.empty() ? panel_items(H) : H.pb_seg_item[(size_t)seg_end];
+        rc = launch_panel_scale(P, x, 0, 1, st, 0, ib, ie);
     }
     // the closing pass: all row blocks, or -- with cfg.row_split -- the foreign rows first (EHYB_PART_LAST_FOREIGN, as soon as
     // segment 0's pass 1 is enqueued) and the rows in front of the split at the end
     const bool split = P->cfg.row_split > 0;
     if (rc == EHYB_OK && (flags & EHYB_PART_LAST_FOREIGN)) {
         if (!split) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: EHYB_PART_LAST_FOREIGN needs a plan built with cfg.row_split");
-        rc = launch_panel(P, x, y, st, 0, 2, 0, -1, 2);
+        rc = launch_panel_reduce(P, y, 0, 1, st, 0, PANEL_ROWS_FROM_SPLIT);
     }
-    if (rc == EHYB_OK && (flags & EHYB_PART_LAST)) rc = launch_panel(P, x, y, st, 0, 2, 0, -1, split ? 1 : 0);
+    if (rc == EHYB_OK && (flags & EHYB_PART_LAST)) rc = launch_panel_reduce(P, y, 0, 1, st, 0, split ? PANEL_ROWS_BEFORE_SPLIT : PANEL_ROWS_ALL);
     return rc;
 }
 

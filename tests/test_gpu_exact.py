@@ -102,6 +102,25 @@ def _lane_codes(plan):
     return set(np.unique(plan.array("lane_group") >> 6).tolist())
 
 
+# The arms of the panel residual that one vector reaches through configuration only.  RMAT14 with 2,048-column panels cut into
+# seven items: 11 pass-1 units in 8 items (up to two units per item) of 1 to 298 64-entry chunks -- a 1024-thread workgroup takes
+# 128 chunks per step, so the longest unit walks three steps with a ragged last one, at 512 threads five -- whose 1,880 chunks
+# have longest pieces of 1, 2, 3-4, 5-8, 9-63 and 64 lanes: every early exit of the piece sums is taken, the plain wave sum
+# included.  No partition keeps a window, so every pass-2 unit assigns.
+PANEL_ARMS = dict(er_mode=2, fuse_er=2, direct=2, lds_doubles=512, er_panel_cols=2048, er_units1=7)
+
+
+def _panel_arms(p, n):
+    chunks = np.diff(p.array("pb_units1").reshape(-1, 4)[:, 2:4], axis=1) >> 6
+    return p.stats["er_partials"] > 0 and chunks.max() > 128 and p.stats["nnz_ell"] == 0
+
+
+def _panel_arms_two_blocks(p, n):
+    """pass 2 in units of several steps (512 threads x 8 partial sums = 4,096 per step) beside units of a single partial sum"""
+    sums = np.diff(p.array("pb_units2").reshape(-1, 4)[:, 0:2], axis=1)
+    return _panel_arms(p, n) and sums.max() > 3 * 4096 and sums.min() == 1
+
+
 # (id, matrix, config, symmetric values, what the stats must show)
 PATHS = [
     ("refwindow-t256-lds1024", FEM, dict(window_mode=1, threads=256, lds_doubles=1024), True,
@@ -140,6 +159,14 @@ PATHS = [
      lambda p, n: bool(np.any(p.array("slab_meta").reshape(-1, 4)[:, 3] & 0x80)) and p.stats["nnz_er"] == 0),
     ("symbolic-device-panel", ("rmat", (15, 1 << 18, 1)), dict(er_mode=2, fuse_er=2, direct=2, lds_doubles=2048, symbolic=2), False,
      lambda p, n: p.stats["er_partials"] > 0 and p.stats["er_segments"] == 0),
+    ("panel-scan-sums-t512", RMAT14, dict(er_sums=1, er_panel_threads=512, **PANEL_ARMS), False, _panel_arms),
+    ("panel-scan-sums-t1024", RMAT14, dict(er_sums=1, er_panel_threads=1024, **PANEL_ARMS), False, _panel_arms),
+    ("panel-lds-sums-t512", RMAT14, dict(er_sums=2, er_panel_threads=512, **PANEL_ARMS), False, _panel_arms),
+    ("panel-lds-sums-t1024", RMAT14, dict(er_sums=2, er_panel_threads=1024, **PANEL_ARMS), False, _panel_arms),
+    ("panel-pass2-streamed", RMAT14, dict(er_nt=1, **PANEL_ARMS), False, _panel_arms),
+    ("panel-pass2-cached", RMAT14, dict(er_nt=2, **PANEL_ARMS), False, _panel_arms),
+    ("panel-pass2-streamed-long-units", RMAT14, dict(er_nt=1, er_block_rows=16384, er_units2=2, **PANEL_ARMS), False, _panel_arms_two_blocks),
+    ("panel-pass2-cached-long-units", RMAT14, dict(er_nt=2, er_block_rows=16384, er_units2=2, **PANEL_ARMS), False, _panel_arms_two_blocks),
 ]
 
 
@@ -155,6 +182,35 @@ def test_exact_named_path(E, O, gpu, name, gen, kw, sym, taken):
         dx, dy = E.DeviceBuffer(c.n).upload(c.xp), E.DeviceBuffer(c.n)
         with pytest.raises(E.EhybError):
             plan.spmv(dx.ptr, dy.ptr, phase=1)
+
+
+@pytest.mark.parametrize("threads", [512, 1024])
+@pytest.mark.parametrize("er_sums", [1, 2])
+def test_panel_times_probes_launch_and_leave_the_product(E, O, gpu, er_sums, threads):
+    """ehyb_debug_panel_times (tools/panel_sweep.py) is the only caller of the PROBE instantiations of pass 1: with the probe values
+    the tool uses it launches both passes and returns 0 (a probed result is wrong by design: nothing is asserted about it), and a
+    call with probe 0 afterwards -- every row block of this plan assigns -- leaves y exactly the product.  The rows of no row block
+    (they have no entry; the window launch writes them) start with their value, every other row with NaN."""
+    cfg = E.make_config(er_sums=er_sums, er_panel_threads=threads, **PANEL_ARMS)
+    c = ExactCase(E, O, RMAT14, cfg, symmetric=False)
+    plan = E.Plan(c.m, cfg)
+    assert _panel_arms(plan, c.n), plan.stats
+    u2 = plan.array("pb_units2").reshape(-1, 4)
+    assert bool(np.all(u2[:, 3] < 0))
+    y0 = c.y_ref_p.copy()
+    for first, rows in zip(u2[:, 2], -u2[:, 3]):
+        y0[first:first + rows] = np.nan
+    assert np.isnan(y0).sum() == -u2[:, 3].sum() > c.n // 2 and not np.any(y0[~np.isnan(y0)])
+    lib = E.host._lib.load()
+    lib.ehyb_debug_panel_times.restype = C.c_int
+    lib.ehyb_debug_panel_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    dx, dy = E.DeviceBuffer(c.n).upload(c.xp), E.DeviceBuffer(c.n).upload(y0)
+    for probe in (0, 2, 0):                     # (panel_sweep.py --probes, then the product again)
+        a, b = C.c_double(), C.c_double()
+        assert lib.ehyb_debug_panel_times(plan.h, C.c_void_p(dx.ptr), C.c_void_p(dy.ptr), 1, probe, C.byref(a), C.byref(b)) == 0, probe
+    _sync(E)
+    assert_exact(dy.download(), c.y_ref_p, f"er_sums={er_sums} threads={threads} after the probes")
+    dx.free(), dy.free()
 
 
 @pytest.mark.parametrize("name,gen,kw,sym", [
