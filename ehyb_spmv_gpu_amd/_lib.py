@@ -82,7 +82,8 @@ class Config(C.Structure):
         ("er_nt", C.c_int32),
         ("ell_nt", C.c_int32),
         ("ell_keep", C.c_int32),
-        ("reserved", C.c_int32 * 20),
+        ("ell_triples", C.c_int32),
+        ("reserved", C.c_int32 * 19),
     ]
 
 
@@ -155,6 +156,8 @@ SIGNATURES = {
     "ehyb_ell_slab_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ehyb_ell_auto_keep1024": (C.c_int, [C.c_int64, C.c_int64]),
     "ehyb_plan_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
+    "ehyb_plan_device_col_words": (C.c_int64, [_vp]),
+    "ehyb_plan_device_cols": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32)]),
     "ehyb_spmv": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_spmv_phase": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
     "ehyb_spmv_walk": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),

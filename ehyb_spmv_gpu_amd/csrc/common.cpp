@@ -187,6 +187,7 @@ Config resolve_config(const ehyb_config* in)
     c.er_nt = (z.er_nt == 1 || z.er_nt == 2) ? z.er_nt : 0;
     c.ell_nt = (z.ell_nt >= 1 && z.ell_nt <= 5) ? z.ell_nt : 4;  // 4: a fixed set of slabs stays in the Infinity Cache (ell_keep_rule)
     c.ell_keep = std::min(1000, std::max(0, z.ell_keep));  // 0: by the size of the Infinity Cache (ell_keep_rule)
+    c.ell_triples = z.ell_triples == 2 ? 2 : 1;
     c.er_queue = (z.er_queue == 1 || z.er_queue == 2) ? z.er_queue : 0;  // 0: by the number of items per resident workgroup (launch_panel_scale)
     // the automatic choice of the direct shape is for callers that left the window sizing alone: a caller
     // that names a window (lds_doubles / part_rows other than the defaults) gets that window
@@ -265,6 +266,7 @@ void ehyb_config_resolve(const ehyb_config* in, ehyb_config* out)
     r.er_nt = c.er_nt;
     r.ell_nt = c.ell_nt;
     r.ell_keep = c.ell_keep;
+    r.ell_triples = c.ell_triples;
     *out = r;
 }
 

@@ -48,6 +48,7 @@
 
 #include "ehyb_internal.h"
 #include "hip_try.h"
+#include "col_triples.h"
 #include "ell_device.h"
 #include "panel_device.h"
 
@@ -60,8 +61,10 @@ using namespace ehyb;
 // a window of <= 80 KiB; at the default 160 KiB window one runs per CU (an 8-pair step with 128 VGPRs was
 // measured there too: no gain).  SYM always runs one workgroup per CU (its window holds x and the y
 // accumulators): 4 waves per SIMD, up to 128 VGPRs, no spills.
+// (The stamped instantiations, diagnostic, carry both forms of the column words like every other and the stamps on top: they
+// get the 128 VGPRs of SYM with plain storage too, rather than spill.)
 template <int THREADS, bool DYN, bool STAMP, bool INLINE_ER, bool SYM>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SYM ? 4 : 8, 8))) void ehyb_ell_kernel(const EllArgs A)
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu((SYM || STAMP) ? 4 : 8, 8))) void ehyb_ell_kernel(const EllArgs A)
 {
     ell_items<THREADS, 1, DYN, STAMP, INLINE_ER, SYM>(A, 0, 0);
 }
@@ -350,6 +353,8 @@ int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y,
         }
     }
     if (!fn) EHYB_FAIL(EHYB_ERR_ARG, "ELL workgroup size %d not built (256/512/1024)", P->cfg.threads);
+    if (P->d_triples && k >= kNoTripleArmK && inl && H.sym)  // (plan_keeps_pair_words keeps such a plan in the pair form)
+        EHYB_FAIL(EHYB_ERR_INTERNAL, "window launch: %d columns with symmetric pairs and an inline residual on triple-coded column words", k);
     const size_t lds = ell_lds_bytes(H, k);
     EllArgs A = ell_args(P, x, y, stamps, xy_out);
     if (stamps)
@@ -899,9 +904,23 @@ int ehyb_plan_upload(ehyb_plan* P)
     }
     UP(d_halo_cols, halo_cols)
     UP(d_ell_val, ell_val)
-    UP(d_ell_col, ell_col)
+    if (P->cfg.ell_triples == 1) {
+        // the device's own form of the column words and slab records (col_triples.h); the host arrays stay the definition
+        BigVec<uint32_t> words;
+        std::vector<uint32_t> meta;
+        {
+            OmpScope omp(P->cfg.host_threads);
+            P->d_triples = device_cols(H, true, &words, &meta) != (int64_t)H.ell_col.size() || meta != H.slab_meta;
+        }
+        if ((rc = upload(&P->d_ell_col, words)) != EHYB_OK || (rc = upload(&P->d_slab_meta, meta)) != EHYB_OK) {
+            free_device(P);
+            return rc;
+        }
+    } else {
+        UP(d_ell_col, ell_col)
+        UP(d_slab_meta, slab_meta)
+    }
     UP(d_lane_group, lane_group)
-    UP(d_slab_meta, slab_meta)
     UP(d_items, items)
     UP(d_segs, segs)
     UP(d_slab_lrow, slab_lrow)

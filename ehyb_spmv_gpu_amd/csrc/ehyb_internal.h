@@ -115,6 +115,7 @@ struct Config {
     int ell_nt;             // window kernel, value stream past the caches: 4 (default) / 5 all but a fixed set of slabs that stays in the Infinity
                             // Cache (spread over a segment / its first slabs), 3 all but the end of an alternating walk, 1 every slab, 2 never
     int ell_keep;           // ell_nt 4 / 5: the share of the slabs in that set, per mille; 0 = from the cache's size (ehyb_hip.hip)
+    int ell_triples;        // 1: the device holds one column base per node triple where a slab allows it (col_triples.h), 2: the host's words
 };
 Config resolve_config(const ehyb_config* cfg);
 
@@ -294,6 +295,36 @@ void encode_panel_slots(HostLayout* L);                      // er_panel.cpp; pb
 bool sym_storage_suits(const matrixCOO* m);  // spmvGPuEHYB's own choice of the storage (plan.cpp)
 int windows_that_do_not_pay(const HostLayout& H, int pct, std::vector<uint8_t>* to_er, int64_t* entries_moved);  // plan.cpp
 
+// ---------------------------------------------------------------- widths (host arithmetic; the launches and the transcoder of the column words share it)
+constexpr int kSpmmMaxK = 4;  // widest window / residual kernel built
+
+// Doubles of the LDS x image per vector (the window, with symmetric pair storage the y accumulators behind it); the kernel's
+// slab counter sits right behind the image(s).
+inline int ell_win_cap(const HostLayout& H) { return (H.lds_doubles + 1) / 2 * 2; }
+// Dynamic LDS of a window launch for k columns: k images and the slab counter
+inline size_t ell_lds_bytes(const HostLayout& H, int k) { return (size_t)k * ell_win_cap(H) * 8 + 16; }
+
+// Widest pass of ehyb_spmm on a plan (ehyb_spmm_max_k; the rule is stated in include/ehyb.h): what fits the 160 KiB of LDS -- k
+// window images and the slab counter; for a panel-form residual also k panel images and the hand-over word of pass 1, and k
+// accumulators per row of the largest row block of pass 2.
+inline int spmm_width(const HostLayout& H)
+{
+    if (H.deferred.pending) return 1;  // (the panel form is not built yet: nothing can be multiplied)
+    int64_t k = kSpmmMaxK;
+    if (H.er_panel && H.pb_panel_cols > 0 && H.pb_rows_max > 0)
+        k = std::min<int64_t>(k, std::min<int64_t>((EHYB_LDS_MAX_DOUBLES - 1) / H.pb_panel_cols, EHYB_LDS_MAX_DOUBLES / H.pb_rows_max));
+    const int64_t cap = ell_win_cap(H);
+    if (!H.direct && cap > 0) k = std::min<int64_t>(k, ((int64_t)EHYB_LDS_MAX_DOUBLES * 8 - 16) / (8 * cap));
+    return (int)std::max<int64_t>(1, k);
+}
+
+// One window kernel carries no triple arm (ell_device.h: it spilled with both forms of the column words in it): K columns from this
+// width up with symmetric pairs AND an inline residual.  A plan that can launch it keeps the host's column words on the device
+// (col_triples.cpp: plan_keeps_pair_words); launch_window refuses that kernel on a plan with coded slabs.
+constexpr int kNoTripleArmK = 4;
+static_assert(kNoTripleArmK <= kSpmmMaxK + 1, "a width no kernel is built for");
+inline bool plan_keeps_pair_words(const HostLayout& H) { return H.sym && H.inline_er && spmm_width(H) >= kNoTripleArmK; }
+
 // ---------------------------------------------------------------- partitioner
 // *by_degree (may be null) = true: the parts are blocks of the degree order (EHYB_PART_DEGREE, or EHYB_PART_AUTO on a
 // graph that does not coarsen) -- the caller should number the rows of a part in that order (degree_order)
@@ -357,6 +388,7 @@ struct ehyb_plan {
     ehyb::Config cfg;
     ehyb::HostLayout host;
     bool uploaded = false;
+    bool d_triples = false;  // the device's column words hold triple-coded slabs (col_triples.h)
     int device = -1;
     std::vector<int32_t> perm;  // reorderList a cached plan was saved with (ehyb_plan_load), else empty
     // device arrays (same names as HostLayout; what the kernels do not read stays on the host)

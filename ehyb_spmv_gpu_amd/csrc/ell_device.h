@@ -153,17 +153,16 @@ __device__ __forceinline__ void win_store(double* __restrict__ win, int idx, con
 // SAME accumulator.  Summed across the lanes first (`code`: this lane adds for itself and the next
 // 0/1/2 lanes, 3 = a lane before it adds for this one), a group of three costs one ds_add_f64
 // instead of three that the hardware has to serialise.
+// (ell_entry_at: the same with the column and its mirror flag apart, as the triple-coded slabs have them)
 template <int K, bool SYM>
-__device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double* __restrict__ win, double* yacc, const double (&xi)[K],
-                                          int code, double (&acc)[K])
+__device__ __forceinline__ void ell_entry_at(double v, uint32_t idx, bool mirror, const double* __restrict__ win, double* yacc, const double (&xi)[K],
+                                             int code, double (&acc)[K])
 {
     double w[K];
     if (SYM) {
-        const uint32_t idx = col16 & 0x7fffu;
         win_load<K>(win, idx, w);
 #pragma unroll
         for (int j = 0; j < K; ++j) acc[j] = fma(v, w[j], acc[j]);
-        const bool mirror = (col16 & 0x8000u) != 0;
         if constexpr (K == 1) {  // (written without the loop: even one trip of it costs the one-vector kernel a VGPR)
             const double mine = mirror ? v * xi[0] : 0.0;
             const double n1 = next_lane(mine), n2 = next_lane(n1);
@@ -179,10 +178,37 @@ __device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double
             }
         }
     } else {
-        win_load<K>(win, col16, w);
+        win_load<K>(win, idx, w);
 #pragma unroll
         for (int j = 0; j < K; ++j) acc[j] = fma(v, w[j], acc[j]);
     }
+}
+
+template <int K, bool SYM>
+__device__ __forceinline__ void ell_entry(double v, uint32_t col16, const double* __restrict__ win, double* yacc, const double (&xi)[K],
+                                          int code, double (&acc)[K])
+{
+    ell_entry_at<K, SYM>(v, SYM ? (col16 & 0x7fffu) : col16, SYM && (col16 & 0x8000u) != 0, win, yacc, xi, code, acc);
+}
+
+// The three value pairs of one column word (A, B) of a triple-coded slab: columns (A, A+1), (A+2, B), (B+1, B+2).  A base carries
+// the mirror flag of its triple in bit 15 (symmetric pairs).  No mask for lanes without a row (plain storage): the slab is not
+// relative, so the columns of any group of it lie in the window, and such a lane writes nothing.  `pairs` < 3: the first one or two.
+template <int K, bool SYM>
+__device__ __forceinline__ void ell_triple_word(const double2& v0, const double2& v1, const double2& v2, uint32_t w, int pairs,
+                                                const double* __restrict__ win, double* yacc, const double (&xi)[K], int code,
+                                                double (&acc0)[K], double (&acc1)[K])
+{
+    const uint32_t a = w & (SYM ? 0x7fffu : 0xffffu), b = SYM ? (w >> 16) & 0x7fffu : w >> 16;
+    const bool ma = SYM && (w & 0x8000u) != 0, mb = SYM && (w & 0x80000000u) != 0;
+    ell_entry_at<K, SYM>(v0.x, a, ma, win, yacc, xi, code, acc0);
+    ell_entry_at<K, SYM>(v0.y, a + 1, ma, win, yacc, xi, code, acc1);
+    if (pairs < 2) return;
+    ell_entry_at<K, SYM>(v1.x, a + 2, ma, win, yacc, xi, code, acc0);
+    ell_entry_at<K, SYM>(v1.y, b, mb, win, yacc, xi, code, acc1);
+    if (pairs < 3) return;
+    ell_entry_at<K, SYM>(v2.x, b + 1, mb, win, yacc, xi, code, acc0);
+    ell_entry_at<K, SYM>(v2.y, b + 2, mb, win, yacc, xi, code, acc1);
 }
 
 // One slab of 64 rows.  xy (K = 1, A.xy_out set): the lane's running sum of y[row] * x[row].
@@ -240,6 +266,86 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
     const uint32_t cmask = (SYM || has_row) ? 0xffffu : 0u;
 #define ELL_COL_LO(c) (SYM ? ((c) & 0xffffu) : ((((c) & 0xffffu) + radd) & cmask))
 #define ELL_COL_HI(c) (SYM ? ((c) >> 16) : ((((c) >> 16) + radd) & cmask))
+    // bit 6 of the record (device copy only, col_triples.h): the slab's column words hold one 16-bit base per node triple, two
+    // per word.  Wave-uniform.  The pairs come in the order, and on the accumulators, of the pair form below.
+    //   one vector, symmetric pairs (up to 128 VGPRs): six value pairs and two column words per step, then one step of three;
+    //   plain storage at K = 1 (64 VGPRs) and K = 2, 3: a word's three pairs per step -- six spill;
+    //   K = 4: a word's three pairs, the third loaded once the first has been multiplied;
+    // then one or two pairs from one more word.
+    // (K = 4 with symmetric pairs AND an inline residual spilled with both forms in it, 128 VGPRs: col_triples.cpp codes no slab
+    // of a plan that can take that kernel, and the arm is left out of it)
+    constexpr bool kTriples = !(K >= ehyb::kNoTripleArmK && SYM && INLINE_ER);
+    if (kTriples && (sm.w & 0x40u)) {
+        // Running pointers and a count.  The empty asm hides where the pointers come from: without it the compiler hoists this
+        // arm's lane addresses (ell_val + lane + a constant, ...) out of the walk over the slabs, next to the ones of the pair
+        // form, and the kernels built for 64 VGPRs have no registers for both -- they spilled.
+        const double2* vp = v;
+        const uint32_t* cp = c;
+        asm volatile("" : "+v"(vp), "+v"(cp));
+        int left = np;
+        if constexpr (K >= 4) {
+#pragma nounroll
+            for (; left >= 3; left -= 3, vp += 3 * 64, cp += G) {
+                // (one pair in flight: the barriers keep the next pair's load behind this pair's products -- registers)
+                const uint32_t w0 = cp[0];
+                const uint32_t a = w0 & (SYM ? 0x7fffu : 0xffffu), b = SYM ? (w0 >> 16) & 0x7fffu : w0 >> 16;
+                const bool ma = SYM && (w0 & 0x8000u) != 0, mb = SYM && (w0 & 0x80000000u) != 0;
+                const double2 v0 = ell_load_pair<NT>(vp);
+                ell_entry_at<K, SYM>(v0.x, a, ma, win, yacc, xi, code, acc0);
+                ell_entry_at<K, SYM>(v0.y, a + 1, ma, win, yacc, xi, code, acc1);
+                __builtin_amdgcn_sched_barrier(0);
+                const double2 v1 = ell_load_pair<NT>(vp + 64);
+                ell_entry_at<K, SYM>(v1.x, a + 2, ma, win, yacc, xi, code, acc0);
+                ell_entry_at<K, SYM>(v1.y, b, mb, win, yacc, xi, code, acc1);
+                __builtin_amdgcn_sched_barrier(0);
+                const double2 v2 = ell_load_pair<NT>(vp + 2 * 64);
+                ell_entry_at<K, SYM>(v2.x, b + 1, mb, win, yacc, xi, code, acc0);
+                ell_entry_at<K, SYM>(v2.y, b + 2, mb, win, yacc, xi, code, acc1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            if constexpr (SYM && K == 1) {
+                for (; left >= 6; left -= 6, vp += 6 * 64, cp += 2 * G) {
+                    double2 vv[6];
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) vv[q] = ell_load_pair<NT>(vp + q * 64);
+                    const uint32_t w0 = cp[0], w1 = cp[G];
+                    ell_triple_word<K, SYM>(vv[0], vv[1], vv[2], w0, 3, win, yacc, xi, code, acc0, acc1);
+                    ell_triple_word<K, SYM>(vv[3], vv[4], vv[5], w1, 3, win, yacc, xi, code, acc0, acc1);
+                }
+            }
+#pragma nounroll
+            for (; left >= 3; left -= 3, vp += 3 * 64, cp += G) {
+                double2 vv[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) vv[q] = ell_load_pair<NT>(vp + q * 64);
+                const uint32_t w0 = cp[0];
+                ell_triple_word<K, SYM>(vv[0], vv[1], vv[2], w0, 3, win, yacc, xi, code, acc0, acc1);
+            }
+        }
+        if constexpr (K >= 4) {
+            if (left > 0) {  // (wave-uniform, as `left > 1`)
+                const uint32_t w0 = cp[0];
+                const uint32_t a = w0 & (SYM ? 0x7fffu : 0xffffu), b = SYM ? (w0 >> 16) & 0x7fffu : w0 >> 16;
+                const bool ma = SYM && (w0 & 0x8000u) != 0, mb = SYM && (w0 & 0x80000000u) != 0;
+                const double2 v0 = ell_load_pair<NT>(vp);
+                ell_entry_at<K, SYM>(v0.x, a, ma, win, yacc, xi, code, acc0);
+                ell_entry_at<K, SYM>(v0.y, a + 1, ma, win, yacc, xi, code, acc1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (left > 1) {
+                    const double2 v1 = ell_load_pair<NT>(vp + 64);
+                    ell_entry_at<K, SYM>(v1.x, a + 2, ma, win, yacc, xi, code, acc0);
+                    ell_entry_at<K, SYM>(v1.y, b, mb, win, yacc, xi, code, acc1);
+                }
+            }
+        } else if (left > 0) {
+            const double2 v0 = ell_load_pair<NT>(vp);
+            double2 v1 = make_double2(0.0, 0.0);
+            if (left > 1) v1 = ell_load_pair<NT>(vp + 64);
+            const uint32_t w0 = cp[0];
+            ell_triple_word<K, SYM>(v0, v1, v1, w0, left, win, yacc, xi, code, acc0, acc1);
+        }
+    } else {
     // Four value pairs per step; symmetric pairs at K = 4 take two, which keeps them within 128 VGPRs.
     // (an 8-pair step for SYM, 128 VGPRs at 16 waves per CU, measured 1 % slower than four at K = 1)
     constexpr int STEP = (SYM && K >= 4) ? 2 : 4;
@@ -262,6 +368,7 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
         const uint32_t c0 = c[k * G];
         ell_entry<K, SYM>(v0.x, ELL_COL_LO(c0), win, yacc, xi, code, acc0);
         ell_entry<K, SYM>(v0.y, ELL_COL_HI(c0), win, yacc, xi, code, acc1);
+    }
     }
 #undef ELL_COL_LO
 #undef ELL_COL_HI
@@ -512,32 +619,11 @@ __device__ __forceinline__ void er_blocks(const int4* __restrict__ blocks, const
 
 // ------------------------------------------------------------------ host side (ehyb_hip.hip)
 namespace ehyb {
-constexpr int kSpmmMaxK = 4;  // widest window / residual kernel built
-
-// Doubles of the LDS x image per vector (the window, with symmetric pair storage the y accumulators behind it); the kernel's
-// slab counter sits right behind the image(s).
-inline int ell_win_cap(const HostLayout& H) { return (H.lds_doubles + 1) / 2 * 2; }
-// Dynamic LDS of a window launch for k columns: k images and the slab counter
-inline size_t ell_lds_bytes(const HostLayout& H, int k) { return (size_t)k * ell_win_cap(H) * 8 + 16; }
-
+// (kSpmmMaxK, ell_win_cap, ell_lds_bytes and spmm_width are in ehyb_internal.h: the transcoder of the column words uses them too)
 // The window launch of a multiply for k = 1..kSpmmMaxK columns ldx / ldy doubles apart.  walk: >= 0 explicit, -1 the plan's own
 // alternation.  k = 1 only: stamps (diagnostic; no walk of its own) and xy_out (x . y on the side).
 int launch_window(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, bool inl, int walk,
                   unsigned long long* stamps = nullptr, double* xy_out = nullptr);
-// Widest pass of ehyb_spmm on a plan (ehyb_spmm_max_k; the rule is stated in include/ehyb.h): what fits the 160 KiB of LDS -- k
-// window images and the slab counter; for a panel-form residual also k panel images and the hand-over word of pass 1, and k
-// accumulators per row of the largest row block of pass 2.
-inline int spmm_width(const HostLayout& H)
-{
-    if (H.deferred.pending) return 1;  // (the panel form is not built yet: nothing can be multiplied)
-    int64_t k = kSpmmMaxK;
-    if (H.er_panel && H.pb_panel_cols > 0 && H.pb_rows_max > 0)
-        k = std::min<int64_t>(k, std::min<int64_t>((EHYB_LDS_MAX_DOUBLES - 1) / H.pb_panel_cols, EHYB_LDS_MAX_DOUBLES / H.pb_rows_max));
-    const int64_t cap = ell_win_cap(H);
-    if (!H.direct && cap > 0) k = std::min<int64_t>(k, ((int64_t)EHYB_LDS_MAX_DOUBLES * 8 - 16) / (8 * cap));
-    return (int)std::max<int64_t>(1, k);
-}
-
 // Both passes of the panel-form residual for k = 2..spmm_width columns (k = 1: the one-vector launch of ehyb_spmv)
 int launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, int walk);
 // The CSR-segment residual launch for k columns (none where the plan has no CSR segments)

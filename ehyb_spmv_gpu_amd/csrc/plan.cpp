@@ -1,4 +1,5 @@
 // Host half of the plan object: layout construction and read-only views (no HIP calls).
+#include "col_triples.h"
 #include "ehyb_internal.h"
 
 #include <algorithm>
@@ -189,6 +190,26 @@ int ehyb_plan_create_host_segs(const matrixCOO* m, int row_begin, int row_end, c
                                int n_col_segs, const int* col_seg_first, ehyb_plan** plan)
 {
     return ehyb::create_host_plan(m, row_begin, row_end, cfg, n_col_segs, col_seg_first, false, plan);
+}
+
+// The column words ehyb_plan_upload sends for this plan (cfg.ell_triples; col_triples.h)
+int64_t ehyb_plan_device_col_words(const ehyb_plan* plan)
+{
+    if (!plan) return -1;
+    OmpScope omp(plan->cfg.host_threads);
+    return device_cols(plan->host, plan->cfg.ell_triples == 1, nullptr, nullptr);
+}
+
+int ehyb_plan_device_cols(const ehyb_plan* plan, uint32_t* words_out, uint32_t* meta_out)
+{
+    if (!plan || !words_out || !meta_out) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_device_cols: null argument");
+    OmpScope omp(plan->cfg.host_threads);
+    BigVec<uint32_t> words;
+    std::vector<uint32_t> meta;
+    device_cols(plan->host, plan->cfg.ell_triples == 1, &words, &meta);
+    std::copy(words.begin(), words.end(), words_out);
+    std::copy(meta.begin(), meta.end(), meta_out);
+    return EHYB_OK;
 }
 
 }  // extern "C"

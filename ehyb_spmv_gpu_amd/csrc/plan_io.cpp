@@ -40,14 +40,16 @@ bool get(FILE* f, T& v)
 {
     return fread(&v, sizeof(T), 1, f) == 1;
 }
-// The configuration as the files hold it: the fields up to ell_nt.  Knobs added since (ell_keep: how a launch reads, nothing of
-// the layout) stay out, so that files written before them remain valid; a loaded plan has them at 0 = automatic.
+// The configuration as the files hold it: the fields up to ell_nt.  Knobs added since (ell_keep: how a launch reads; ell_triples:
+// the form of the column words on the device; nothing of the host layout) stay out, so that files written before them remain
+// valid; a loaded plan has them at their defaults.
 constexpr size_t kCfgFileBytes = offsetof(Config, ell_keep);
-static_assert(kCfgFileBytes + sizeof(int) == sizeof(Config), "fields added to Config go behind ell_keep and stay out of plan files");
+static_assert(kCfgFileBytes + 2 * sizeof(int) == sizeof(Config), "fields added to Config go behind ell_keep and stay out of plan files");
 bool put_cfg(FILE* f, const Config& c) { return fwrite(&c, kCfgFileBytes, 1, f) == 1; }
 bool get_cfg(FILE* f, Config& c)
 {
     c.ell_keep = 0;
+    c.ell_triples = resolve_config(nullptr).ell_triples;
     return fread(&c, kCfgFileBytes, 1, f) == 1;
 }
 template <class T, class A>

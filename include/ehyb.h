@@ -220,7 +220,12 @@ typedef struct ehyb_config {
     int32_t ell_keep;      /* ell_nt = 4 / 5: the share of a partition's slabs in that set, per mille (1..1000).  0 = automatic: what the
                               256 MiB cache holds beside the bytes the launch re-reads and writes with plain accesses (column words,
                               lane maps, slab records, x, y), times a safety factor; all of a stream that fits whole       */
-    int32_t reserved[20];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
+    int32_t ell_triples;   /* the window kernel's column words ON THE DEVICE: 0/1 = a slab whose column lists are node triples c, c+1,
+                              c+2 (three unknowns per node) holds one 16-bit base per triple, two per word -- a third of the words
+                              of such a slab; ehyb_plan_upload transcodes, the host layout (EHYB_ARR_ELL_COL, EHYB_ARR_SLAB_META,
+                              stats, plan files) is the same either way; 2 = the host's words as they are (A/B).  With every x
+                              finite the result does not depend on it (ehyb_plan_device_cols)                       */
+    int32_t reserved[19];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
 } ehyb_config;
 
 void ehyb_config_default(ehyb_config* cfg);
@@ -433,6 +438,25 @@ enum {
     EHYB_ARR_PB_ITEMS1     = 36 /* int32  [2*items] {first unit, end unit}: the work of one pass-1 workgroup -- consecutive
                                    units of (nearly) equal total cost (entries streamed + panels staged)                */
 };
+/*
+ * The column words and slab records as ehyb_plan_upload sends them (cfg.ell_triples); host arithmetic, valid on a plan that was
+ * never uploaded.  A slab is TRIPLE-CODED iff it has no inline residual pairs, is not a relative slab, its window has at least 3
+ * slots, and for every group the 2 * pairs 16-bit entries, cut into threes from the front, are triples (b, b+1, b+2) with equal
+ * bits 15 or (0, 0, 0) (padding), a remainder of two entries being (b, b+1) or (0, 0).  Such a slab holds T = ceil(2 * pairs / 3)
+ * bases per group, two per 32-bit word (low half first), W = ceil(T / 2) words per group at [word][group] with stride G; a base
+ * carries bit 15 for its triple, a padding triple is base 0.  With (A, B) = word j, pair 3j reads the columns (A, A+1), pair 3j+1
+ * (A+2, B), pair 3j+2 (B+1, B+2).  Every other slab keeps its words.  In the records, word 1 is the slab's offset in the
+ * transcoded array and bit 6 of word 3 marks a triple-coded slab.
+ *   ONE EXCEPTION, by plan: a plan with symmetric pairs AND an inline residual (stats.er_inline > 0) whose window is small enough
+ *   for four columns per pass (ehyb_spmm_max_k = 4) keeps every slab in the host's form -- the window kernel of exactly that
+ *   combination carries no decoder (it would spill).  The rule is the one behind ehyb_spmm_max_k; ehyb_spmm refuses that
+ *   kernel on coded words (EHYB_ERR_INTERNAL), which the rule makes unreachable.
+ *   ehyb_plan_device_col_words  the number of words (-1: null plan); equals stats.col_words with cfg.ell_triples = 2.
+ *   ehyb_plan_device_cols       the arrays: words_out holds that many words, meta_out the 4 * n_slabs words of the records.
+ */
+int64_t ehyb_plan_device_col_words(const ehyb_plan* plan);
+int ehyb_plan_device_cols(const ehyb_plan* plan, uint32_t* words_out, uint32_t* meta_out);
+
 /* Read-only view of one array of the plan's host layout.  A plan whose panel form was built on the device (ehyb_plan_create,
  * cfg.symbolic) downloads the PB_* streams on the first call that asks for one; it has no CSR form of that residual
  * (ER_SEG_*, ER_COL, ER_VAL empty, er_segments = 0). */
@@ -454,8 +478,9 @@ int ehyb_plan_host_array(const ehyb_plan* plan, int which, const void** ptr, int
  * -inf or finite as the exact sum of its entries' products would (that class does not depend on the order of summation), and
  * no other row changes.  A NaN or an infinity in x makes every row that stores its column non-finite (a NaN is never lost;
  * an infinity may come out as NaN).  Rows that do NOT store that column may come out NaN as well: padding slots hold the
- * value 0.0 and still read a column -- ELL lanes without an entry read column 0 of their window, as the reference's ELL
- * padding does (convert.c), and the padding of an inline residual (stats.er_inline) reads x[0] -- and 0 * inf, 0 * NaN are
+ * value 0.0 and still read a column -- ELL lanes without an entry read columns 0 to 2 of their window (column 0, as the
+ * reference's ELL padding does, convert.c, in the host layout; in a triple-coded slab on the device, cfg.ell_triples, a padding
+ * triple reads columns 0, 1, 2), and the padding of an inline residual (stats.er_inline) reads x[0] -- and 0 * inf, 0 * NaN are
  * NaN.  (A NaN in x[0] alone turns most rows of an inline-residual plan NaN.)  The padding of the panel form and the direct
  * shape reads nothing.  With every x finite no padding slot changes a result.
  * Range.  Subnormal matrix values, x entries, products and partial sums are kept on every path, never flushed to zero: the

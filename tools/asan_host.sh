@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 make -C "$SRC" -j8 >/dev/null                      # the HIP objects (build/*.o of the *.hip files)
 HIP_OBJS=()
 for f in "$SRC"/*.hip; do HIP_OBJS+=("$SRC/build/$(basename "$f" .hip).o"); done
-for f in common partition reorder layout er_panel plan plan_io matrix_io; do
+for f in common partition reorder layout er_panel col_triples plan plan_io matrix_io; do
     g++ -O1 -g -fPIC -fopenmp -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
         -I"$ROOT/include" -I"$SRC" -c "$SRC/$f.cpp" -o "$TMP/$f.o"
 done

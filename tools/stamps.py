@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: per-workgroup timeline of the ELL kernel (stamped instantiation) and the
 streaming-read ceiling of the device.  Not part of the product path.
+The stamped plain-storage kernels are built for 4 waves per SIMD (80 VGPRs with both forms of the column words), the
+product's for 8: with --lds of 10240 or less and 1024 threads a plain-storage timeline is that of ONE workgroup per CU, not two.
 
 usage: python tools/stamps.py [--workload audikw_1-like] [--lds 10240] [--threads 1024] [--items 2]
 """
