@@ -208,6 +208,7 @@ SIGNATURES = {
     "ehyb_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cg_multi": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_bicgstab_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cg_layout": (C.c_int, [_ip, _ip, _ip, _ip, _ip, _ip]),
     "ehyb_cg_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_cg_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),

@@ -20,10 +20,15 @@
 // launch set does what it would have done anyway.  The half step is the exception -- it updates x and r -- so step 6 does
 // not set the status for it; step 7 sees the same s.s and sets it.  The host reads partials, status and counter at check
 // points only.
+//
+// k right-hand sides (ehyb_bicgstab_multi) are k such solves that share the two multiplies (ehyb_spmm): the vector kernels are
+// templated on K columns per launch, every column with its own slots, status word and counter, and K = 1 is the one-vector solve.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
+#include <vector>
 
 #include "ehyb_internal.h"
 #include "solve_loop.h"
@@ -32,257 +37,539 @@ using namespace ehyb;
 
 namespace {
 
-// partial slots, kMaxGrid doubles each; rho number c = r^.r of iterations of parity c lives in slot B_RHO0 + 2 c.  Behind
-// them two ints: the status word and the device's iteration counter.
+// partial slots, kMaxGrid doubles each; rho number c = r^.r of iterations of parity c lives in slot B_RHO0 + 2 c.  Column j's
+// set of slots starts at s + j * B_COUNT * kMaxGrid; behind the last set two ints per column: the status word and the device's
+// iteration counter.  One column is the layout of ehyb_bicgstab_layout.
 enum { B_BB = 0, B_RV = 1, B_SS = 2, B_TS = 3, B_TT = 4, B_RHO0 = 5, B_RR = 6, B_RHO1 = 7, B_COUNT = 8 };
 enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
 enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
 
-__device__ __forceinline__ double* slot(double* s, int which) { return s + (size_t)which * kMaxGrid; }
-__device__ __forceinline__ const double* slot(const double* s, int which) { return s + (size_t)which * kMaxGrid; }
+template <typename T>
+__device__ __forceinline__ T* slot(T* s, int col, int which)
+{
+    return s + ((size_t)col * B_COUNT + which) * kMaxGrid;
+}
 __device__ __forceinline__ bool usable_divisor(double d) { return d != 0.0 && isfinite(d); }
+// a decision every thread of the workgroup takes alike (it comes from the status words or from sums in the fixed order), as a
+// scalar: the branches on it are not divergent
+__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
 
-// the status as the workgroup saw it on entry, the same in every thread (a sibling workgroup of the launch may write it)
-__device__ __forceinline__ bool stopped(const int* __restrict__ flags)
+// on[c]: column c0 + c was running when the workgroup entered, the same in every thread (a sibling workgroup of the launch may
+// set a status).  -> any column running
+template <int K>
+__device__ __forceinline__ bool running(const int* __restrict__ flags, int c0, bool (&on)[K])
 {
-    __shared__ int st;
-    if (threadIdx.x == 0) st = __atomic_load_n(&flags[F_STATUS], __ATOMIC_RELAXED);
-    __syncthreads();
-    return st != ST_RUNNING;
-}
-
-__device__ __forceinline__ void set_status(int* __restrict__ flags, int status)
-{
-    if (threadIdx.x == 0) __atomic_store_n(&flags[F_STATUS], status, __ATOMIC_RELAXED);
-}
-
-// r = b - q (q = A x0), r^ = r, p^ = M^-1 r; partials of rho = r^.r, r.r, b.b
-__global__ __launch_bounds__(kThreads) void bicg_init_kernel(int n, const double* __restrict__ b, const double* __restrict__ q,
-                                                             const double* __restrict__ dinv, double* __restrict__ r,
-                                                             double* __restrict__ rh, double* __restrict__ p, double* __restrict__ s)
-{
-    double rr = 0.0, bb = 0.0;
-    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
-        const double bi = b[i], ri = bi - q[i];
-        r[i] = ri;
-        rh[i] = ri;
-        p[i] = dinv ? ri * dinv[i] : ri;
-        rr = fma(ri, ri, rr);
-        bb = fma(bi, bi, bb);
+    __shared__ int st[K];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) st[c] = __atomic_load_n(&flags[(c0 + c) * F_COUNT + F_STATUS], __ATOMIC_RELAXED);
     }
-    put_partial(rr, slot(s, B_RHO0));
-    put_partial(rr, slot(s, B_RR));
-    put_partial(bb, slot(s, B_BB));
+    __syncthreads();
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = uniform(st[c] == ST_RUNNING);
+        any = any || on[c];
+    }
+    return any;
+}
+
+__device__ __forceinline__ void set_status(int* __restrict__ flags, int col, int status)
+{
+    if (threadIdx.x == 0) __atomic_store_n(&flags[col * F_COUNT + F_STATUS], status, __ATOMIC_RELAXED);
+}
+
+// ------------------------------------------------------------------ the vector kernels, K columns per launch
+// Columns c0 .. c0 + K - 1 of vectors with leading dimension n (B: ldb, X: ldx); K <= 4 per launch, ceil(k / 4) launches for k
+// columns, K = 1 for the one-vector solve and the ehyb_bicgstab_*_step building blocks.  Every kernel walks the indices with the
+// grid and the per-thread order of the one-vector kernel and does the same arithmetic in the same order per column, so a
+// column's partials and scalars are the one-vector solve's bits.  One thread serves the K columns at one index: one inv_diag
+// load for all of them, and the loads of every column are issued before the first store.  U grid strides per trip: a thread
+// accumulates in rising index order whatever U is, so U is free per K and is chosen to keep the loads of a trip in registers.
+// A column whose status is set is skipped: its vectors and partials stay as they are.
+constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
+
+// r = b - q (q = A x0), r^ = r, p^ = M^-1 r; partials of rho = r^.r, r.r, b.b.  Takes no flags: they are zero at the start.
+template <int K>
+__global__ __launch_bounds__(kThreads) void bicg_init_kernel(int n, const double* __restrict__ B, long long ldb,
+                                                             const double* __restrict__ Q, const double* __restrict__ dinv,
+                                                             double* __restrict__ R, double* __restrict__ RH, double* __restrict__ P,
+                                                             double* __restrict__ s, int c0)
+{
+    double sums[2 * K];
+#pragma unroll
+    for (int c = 0; c < 2 * K; ++c) sums[c] = 0.0;
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const double di = dinv ? dinv[i] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            const size_t o = (size_t)(c0 + c) * n + i;
+            const double bi = B[(size_t)(c0 + c) * ldb + i], ri = bi - Q[o];
+            R[o] = ri;
+            RH[o] = ri;
+            P[o] = dinv ? ri * di : ri;
+            sums[c] = fma(ri, ri, sums[c]);
+            sums[K + c] = fma(bi, bi, sums[K + c]);
+        }
+    }
+    block_sum_n(sums);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            slot(s, c0 + c, B_RHO0)[blockIdx.x] = sums[c];
+            slot(s, c0 + c, B_RR)[blockIdx.x] = sums[c];
+            slot(s, c0 + c, B_BB)[blockIdx.x] = sums[K + c];
+        }
+    }
 }
 
 // step 2: partials of r^.v
-__global__ __launch_bounds__(kThreads) void bicg_dot_kernel(int n, const double* __restrict__ rh, const double* __restrict__ v,
-                                                            double* __restrict__ s, const int* __restrict__ flags)
+template <int K, int U>
+__global__ __launch_bounds__(kThreads) void bicg_dot_kernel(int n, const double* __restrict__ RH, const double* __restrict__ V,
+                                                            double* __restrict__ s, const int* __restrict__ flags, int c0)
 {
-    if (stopped(flags)) return;
-    double acc = 0.0;
+    bool on[K];
+    if (!running<K>(flags, c0, on)) return;
+    const double* rh[K];
+    const double* v[K];
+    double acc[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        rh[c] = RH + (size_t)(c0 + c) * n;
+        v[c] = V + (size_t)(c0 + c) * n;
+        acc[c] = 0.0;
+    }
     const int stride = (int)gridDim.x * kThreads;
     int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {  // four grid strides per trip, as ehyb_cg.hip's update kernel
-        double av[4], bv[4];
+    for (; i + (U - 1) * stride < n; i += U * stride) {  // U grid strides per trip, as ehyb_cg.hip's update kernel
+        double av[K][U], bv[K][U];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            av[u] = rh[i + u * stride];
-            bv[u] = v[i + u * stride];
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                av[c][u] = rh[c][i + u * stride];
+                bv[c][u] = v[c][i + u * stride];
+            }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) acc = fma(av[u], bv[u], acc);
-    }
-    for (; i < n; i += stride) acc = fma(rh[i], v[i], acc);
-    put_partial(acc, slot(s, B_RV));
-}
-
-// step 3: alpha = rho / r^.v;  s = r - alpha v;  s^ = M^-1 s;  partials of s.s
-__global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* __restrict__ r, const double* __restrict__ v,
-                                                          const double* __restrict__ dinv, double* __restrict__ sv,
-                                                          double* __restrict__ sh, double* __restrict__ s, int* __restrict__ flags,
-                                                          int cur)
-{
-    if (stopped(flags)) return;
-    double sums[2] = {partials_of(slot(s, B_RHO0 + 2 * cur)), partials_of(slot(s, B_RV))};
-    block_sum_n(sums);
-    const double rho = sums[0], rv = sums[1], alpha = rho / rv;
-    if (!isfinite(rho) || !usable_divisor(rv) || !isfinite(alpha)) {
-        set_status(flags, ST_BREAKDOWN);
-        return;
-    }
-    double ss = 0.0;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double rv4[4], vv[4], dv[4];
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            rv4[u] = r[i + u * stride];
-            vv[u] = v[i + u * stride];
-            dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double si = fma(-alpha, vv[u], rv4[u]);
-            sv[i + u * stride] = si;
-            sh[i + u * stride] = dinv ? si * dv[u] : si;
-            ss = fma(si, si, ss);
+            for (int u = 0; u < U; ++u) acc[c] = fma(av[c][u], bv[c][u], acc[c]);
         }
     }
-    for (; i < n; i += stride) {
-        const double si = fma(-alpha, v[i], r[i]);
-        sv[i] = si;
-        sh[i] = dinv ? si * dinv[i] : si;
-        ss = fma(si, si, ss);
-    }
-    put_partial(ss, slot(s, B_SS));
-}
-
-// step 5: partials of t.s and t.t in one pass
-__global__ __launch_bounds__(kThreads) void bicg_dot2_kernel(int n, const double* __restrict__ t, const double* __restrict__ sv,
-                                                             double* __restrict__ s, const int* __restrict__ flags)
-{
-    if (stopped(flags)) return;
-    double acc[2] = {0.0, 0.0};
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double tv[4], sv4[4];
+    if constexpr (U > 1) {
+        for (; i < n; i += stride) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            tv[u] = t[i + u * stride];
-            sv4[u] = sv[i + u * stride];
+            for (int c = 0; c < K; ++c)
+                if (on[c]) acc[c] = fma(rh[c][i], v[c][i], acc[c]);
         }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            acc[0] = fma(tv[u], sv4[u], acc[0]);
-            acc[1] = fma(tv[u], tv[u], acc[1]);
-        }
-    }
-    for (; i < n; i += stride) {
-        acc[0] = fma(t[i], sv[i], acc[0]);
-        acc[1] = fma(t[i], t[i], acc[1]);
     }
     block_sum_n(acc);
     if (threadIdx.x == 0) {
-        slot(s, B_TS)[blockIdx.x] = acc[0];
-        slot(s, B_TT)[blockIdx.x] = acc[1];
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) slot(s, c0 + c, B_RV)[blockIdx.x] = acc[c];
+    }
+}
+
+// step 3: alpha = rho / r^.v;  s = r - alpha v;  s^ = M^-1 s;  partials of s.s
+template <int K, int U>
+__global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* __restrict__ R, const double* __restrict__ V,
+                                                          const double* __restrict__ dinv, double* __restrict__ SV,
+                                                          double* __restrict__ SH, double* __restrict__ s, int* __restrict__ flags,
+                                                          int c0, int cur)
+{
+    bool on[K];
+    if (!running<K>(flags, c0, on)) return;
+    double sums[2 * K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        sums[c] = on[c] ? partials_of(slot(s, c0 + c, B_RHO0 + 2 * cur)) : 0.0;
+        sums[K + c] = on[c] ? partials_of(slot(s, c0 + c, B_RV)) : 0.0;
+    }
+    block_sum_n(sums);
+    double alpha[K], ss[K];
+    const double* r[K];
+    const double* v[K];
+    double* sv[K];
+    double* sh[K];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        r[c] = R + (size_t)(c0 + c) * n;
+        v[c] = V + (size_t)(c0 + c) * n;
+        sv[c] = SV + (size_t)(c0 + c) * n;
+        sh[c] = SH + (size_t)(c0 + c) * n;
+        ss[c] = 0.0;
+        const double rho = sums[c], rv = sums[K + c];
+        alpha[c] = rho / rv;
+        if (on[c] && uniform(!isfinite(rho) || !usable_divisor(rv) || !isfinite(alpha[c]))) {
+            set_status(flags, c0 + c, ST_BREAKDOWN);
+            on[c] = false;
+        }
+        any = any || on[c];
+    }
+    if (!any) return;
+    const int stride = (int)gridDim.x * kThreads;
+    int i = blockIdx.x * kThreads + threadIdx.x;
+    for (; i + (U - 1) * stride < n; i += U * stride) {
+        double rv[K][U], vv[K][U], dv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                rv[c][u] = r[c][i + u * stride];
+                vv[c][u] = v[c][i + u * stride];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const double si = fma(-alpha[c], vv[c][u], rv[c][u]);
+                sv[c][i + u * stride] = si;
+                sh[c][i + u * stride] = dinv ? si * dv[u] : si;
+                ss[c] = fma(si, si, ss[c]);
+            }
+        }
+    }
+    if constexpr (U > 1) {
+        for (; i < n; i += stride) {
+            const double di = dinv ? dinv[i] : 1.0;
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                if (!on[c]) continue;
+                const double si = fma(-alpha[c], v[c][i], r[c][i]);
+                sv[c][i] = si;
+                sh[c][i] = dinv ? si * di : si;
+                ss[c] = fma(si, si, ss[c]);
+            }
+        }
+    }
+    block_sum_n(ss);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) slot(s, c0 + c, B_SS)[blockIdx.x] = ss[c];
+    }
+}
+
+// step 5: partials of t.s and t.t in one pass
+template <int K, int U>
+__global__ __launch_bounds__(kThreads) void bicg_dot2_kernel(int n, const double* __restrict__ T, const double* __restrict__ SV,
+                                                             double* __restrict__ s, const int* __restrict__ flags, int c0)
+{
+    bool on[K];
+    if (!running<K>(flags, c0, on)) return;
+    const double* t[K];
+    const double* sv[K];
+    double acc[2 * K];  // t.s of the K columns, then t.t
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        t[c] = T + (size_t)(c0 + c) * n;
+        sv[c] = SV + (size_t)(c0 + c) * n;
+        acc[c] = acc[K + c] = 0.0;
+    }
+    const int stride = (int)gridDim.x * kThreads;
+    int i = blockIdx.x * kThreads + threadIdx.x;
+    for (; i + (U - 1) * stride < n; i += U * stride) {
+        double tv[K][U], sv4[K][U];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                tv[c][u] = t[c][i + u * stride];
+                sv4[c][u] = sv[c][i + u * stride];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                acc[c] = fma(tv[c][u], sv4[c][u], acc[c]);
+                acc[K + c] = fma(tv[c][u], tv[c][u], acc[K + c]);
+            }
+        }
+    }
+    if constexpr (U > 1) {
+        for (; i < n; i += stride) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                if (!on[c]) continue;
+                acc[c] = fma(t[c][i], sv[c][i], acc[c]);
+                acc[K + c] = fma(t[c][i], t[c][i], acc[K + c]);
+            }
+        }
+    }
+    block_sum_n(acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+            slot(s, c0 + c, B_TS)[blockIdx.x] = acc[c];
+            slot(s, c0 + c, B_TT)[blockIdx.x] = acc[K + c];
+        }
     }
 }
 
 // step 6: omega = t.s / t.t;  x += alpha p^ + omega s^;  r = s - omega t;  partials of rho_new = r^.r (the other rho slot)
-// and r.r; the counter advances.  Half step (s.s <= thr b.b): x += alpha p^, r = s, partials of r.r only.
-__global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const double* __restrict__ p, const double* __restrict__ sh,
-                                                               const double* __restrict__ sv, const double* __restrict__ t,
-                                                               const double* __restrict__ rh, double* __restrict__ x,
-                                                               double* __restrict__ r, double* __restrict__ s,
-                                                               int* __restrict__ flags, int cur, double thr)
+// and r.r; the counter advances.  Half step (s.s <= thr b.b): x += alpha p^, r = s, partials of r.r only.  Each column takes
+// its own way: the half-step columns first, one plain pass each, then the full updates together.
+template <int K, int U>
+__global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const double* __restrict__ P, const double* __restrict__ SH,
+                                                               const double* __restrict__ SV, const double* __restrict__ T,
+                                                               const double* __restrict__ RH, double* __restrict__ X, long long ldx,
+                                                               double* __restrict__ R, double* __restrict__ s,
+                                                               int* __restrict__ flags, int c0, int cur, double thr)
 {
-    if (stopped(flags)) return;
-    double sums[6] = {partials_of(slot(s, B_RHO0 + 2 * cur)), partials_of(slot(s, B_RV)), partials_of(slot(s, B_SS)),
-                      partials_of(slot(s, B_BB)), partials_of(slot(s, B_TS)), partials_of(slot(s, B_TT))};
+    bool on[K];
+    if (!running<K>(flags, c0, on)) return;
+    constexpr int slots[6] = {B_RHO0, B_RV, B_SS, B_BB, B_TS, B_TT};  // (B_RHO0: + 2 cur)
+    double sums[6 * K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+#pragma unroll
+        for (int w = 0; w < 6; ++w) sums[w * K + c] = on[c] ? partials_of(slot(s, c0 + c, slots[w] + (w == 0 ? 2 * cur : 0))) : 0.0;
+    }
     block_sum_n(sums);
-    const double alpha = sums[0] / sums[1], bb = sums[3] > 0 ? sums[3] : 1.0;
+    const double* p[K];
+    const double* sh[K];
+    const double* sv[K];
+    const double* t[K];
+    const double* rh[K];
+    double* x[K];
+    double* r[K];
+    double alpha[K], omega[K], rho[K], rr[K];
+    bool half[K], full[K], any = false, any_half = false;
     const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    if (sums[2] <= thr * bb) {  // half step: s is small enough
-        double rr = 0.0;
-        for (; i < n; i += stride) {
-            const double si = __builtin_nontemporal_load(&sv[i]);
-            x[i] = fma(alpha, p[i], x[i]);
-            r[i] = si;
-            rr = fma(si, si, rr);
-        }
-        put_partial(rr, slot(s, B_RR));
-        if (blockIdx.x == 0 && threadIdx.x == 0) flags[F_ITERS] += 1;
-        return;
-    }
-    const double tt = sums[5], omega = sums[4] / tt;
-    if (!usable_divisor(tt) || !isfinite(omega)) {
-        set_status(flags, ST_BREAKDOWN);
-        return;
-    }
-    double rho = 0.0, rr = 0.0;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double pv[4], shv[4], sv4[4], tv[4], rhv[4], xv[4];
+    const int i0 = blockIdx.x * kThreads + threadIdx.x;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            pv[u] = p[i + u * stride];
-            shv[u] = __builtin_nontemporal_load(&sh[i + u * stride]);  // s^, s and t are dead after this kernel, x is not read
-            sv4[u] = __builtin_nontemporal_load(&sv[i + u * stride]);  // again before the next update: streamed past the
-            tv[u] = __builtin_nontemporal_load(&t[i + u * stride]);    // caches, which hold the matrix's tail
-            xv[u] = __builtin_nontemporal_load(&x[i + u * stride]);
-            rhv[u] = rh[i + u * stride];
+    for (int c = 0; c < K; ++c) {
+        p[c] = P + (size_t)(c0 + c) * n;
+        sh[c] = SH + (size_t)(c0 + c) * n;
+        sv[c] = SV + (size_t)(c0 + c) * n;
+        t[c] = T + (size_t)(c0 + c) * n;
+        rh[c] = RH + (size_t)(c0 + c) * n;
+        r[c] = R + (size_t)(c0 + c) * n;
+        x[c] = X + (size_t)(c0 + c) * ldx;
+        rho[c] = rr[c] = 0.0;
+        alpha[c] = sums[c] / sums[K + c];
+        const double bb = sums[3 * K + c] > 0 ? sums[3 * K + c] : 1.0, tt = sums[5 * K + c];
+        omega[c] = sums[4 * K + c] / tt;
+        half[c] = on[c] && uniform(sums[2 * K + c] <= thr * bb);  // s is small enough
+        full[c] = on[c] && !half[c];
+        if (full[c] && uniform(!usable_divisor(tt) || !isfinite(omega[c]))) {
+            set_status(flags, c0 + c, ST_BREAKDOWN);
+            full[c] = false;
         }
+        any = any || full[c];
+        any_half = any_half || half[c];
+        if (half[c]) {
+            for (int i = i0; i < n; i += stride) {
+                const double si = __builtin_nontemporal_load(&sv[c][i]);
+                x[c][i] = fma(alpha[c], p[c][i], x[c][i]);
+                r[c][i] = si;
+                rr[c] = fma(si, si, rr[c]);
+            }
+        }
+    }
+    if (any) {
+        int i = i0;
+        for (; i + (U - 1) * stride < n; i += U * stride) {
+            double pv[K][U], shv[K][U], sv4[K][U], tv[K][U], rhv[K][U], xv[K][U];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            __builtin_nontemporal_store(fma(omega, shv[u], fma(alpha, pv[u], xv[u])), &x[i + u * stride]);
-            const double ri = fma(-omega, tv[u], sv4[u]);
-            r[i + u * stride] = ri;
-            rho = fma(rhv[u], ri, rho);
-            rr = fma(ri, ri, rr);
+            for (int c = 0; c < K; ++c) {
+                if (!full[c]) continue;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    pv[c][u] = p[c][i + u * stride];
+                    shv[c][u] = __builtin_nontemporal_load(&sh[c][i + u * stride]);  // s^, s and t are dead after this kernel, x is not
+                    sv4[c][u] = __builtin_nontemporal_load(&sv[c][i + u * stride]);  // read again before the next update: streamed
+                    tv[c][u] = __builtin_nontemporal_load(&t[c][i + u * stride]);    // past the caches, which hold the matrix's tail
+                    xv[c][u] = __builtin_nontemporal_load(&x[c][i + u * stride]);
+                    rhv[c][u] = rh[c][i + u * stride];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                if (!full[c]) continue;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    __builtin_nontemporal_store(fma(omega[c], shv[c][u], fma(alpha[c], pv[c][u], xv[c][u])), &x[c][i + u * stride]);
+                    const double ri = fma(-omega[c], tv[c][u], sv4[c][u]);
+                    r[c][i + u * stride] = ri;
+                    rho[c] = fma(rhv[c][u], ri, rho[c]);
+                    rr[c] = fma(ri, ri, rr[c]);
+                }
+            }
+        }
+        if constexpr (U > 1) {
+            for (; i < n; i += stride) {
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    if (!full[c]) continue;
+                    x[c][i] = fma(omega[c], sh[c][i], fma(alpha[c], p[c][i], x[c][i]));
+                    const double ri = fma(-omega[c], t[c][i], sv[c][i]);
+                    r[c][i] = ri;
+                    rho[c] = fma(rh[c][i], ri, rho[c]);
+                    rr[c] = fma(ri, ri, rr[c]);
+                }
+            }
         }
     }
-    for (; i < n; i += stride) {
-        x[i] = fma(omega, sh[i], fma(alpha, p[i], x[i]));
-        const double ri = fma(-omega, t[i], sv[i]);
-        r[i] = ri;
-        rho = fma(rh[i], ri, rho);
-        rr = fma(ri, ri, rr);
+    if (!any && !any_half) return;
+    double out[2 * K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        out[c] = rho[c];
+        out[K + c] = rr[c];
     }
-    double out[2] = {rho, rr};
     block_sum_n(out);
     if (threadIdx.x == 0) {
-        slot(s, B_RHO0 + 2 * (cur ^ 1))[blockIdx.x] = out[0];
-        slot(s, B_RR)[blockIdx.x] = out[1];
-        if (blockIdx.x == 0) flags[F_ITERS] += 1;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!half[c] && !full[c]) continue;
+            if (full[c]) slot(s, c0 + c, B_RHO0 + 2 * (cur ^ 1))[blockIdx.x] = out[c];
+            slot(s, c0 + c, B_RR)[blockIdx.x] = out[K + c];
+            if (blockIdx.x == 0) flags[(c0 + c) * F_COUNT + F_ITERS] += 1;
+        }
     }
 }
 
 // step 7: the stop test (converged: the half step was taken, or r.r <= thr b.b), then beta = (rho_new / rho) (alpha / omega)
 // and p^ = M^-1 r + beta (p^ - omega M^-1 v)
-__global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const double* __restrict__ r, const double* __restrict__ v,
-                                                                  const double* __restrict__ dinv, double* __restrict__ p,
-                                                                  const double* __restrict__ s, int* __restrict__ flags, int cur,
-                                                                  double thr)
+template <int K, int U>
+__global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const double* __restrict__ R, const double* __restrict__ V,
+                                                                  const double* __restrict__ dinv, double* __restrict__ P,
+                                                                  const double* __restrict__ s, int* __restrict__ flags, int c0,
+                                                                  int cur, double thr)
 {
-    if (stopped(flags)) return;
-    double sums[8] = {partials_of(slot(s, B_SS)), partials_of(slot(s, B_RR)), partials_of(slot(s, B_BB)),
-                      partials_of(slot(s, B_RHO0 + 2 * cur)), partials_of(slot(s, B_RHO0 + 2 * (cur ^ 1))),
-                      partials_of(slot(s, B_RV)), partials_of(slot(s, B_TS)), partials_of(slot(s, B_TT))};
+    bool on[K];
+    if (!running<K>(flags, c0, on)) return;
+    constexpr int slots[8] = {B_SS, B_RR, B_BB, B_RHO0, B_RHO0, B_RV, B_TS, B_TT};  // (the B_RHO0s: + 2 cur, + 2 (cur ^ 1))
+    double sums[8 * K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w)
+            sums[w * K + c] = on[c] ? partials_of(slot(s, c0 + c, slots[w] + (w == 3 ? 2 * cur : w == 4 ? 2 * (cur ^ 1) : 0))) : 0.0;
+    }
     block_sum_n(sums);
-    const double bb = sums[2] > 0 ? sums[2] : 1.0;
-    if (sums[0] <= thr * bb || sums[1] <= thr * bb) {
-        set_status(flags, ST_CONVERGED);
-        return;
+    const double* r[K];
+    const double* v[K];
+    double* p[K];
+    double omega[K], beta[K];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        r[c] = R + (size_t)(c0 + c) * n;
+        v[c] = V + (size_t)(c0 + c) * n;
+        p[c] = P + (size_t)(c0 + c) * n;
+        const double bb = sums[2 * K + c] > 0 ? sums[2 * K + c] : 1.0;
+        const double rho = sums[3 * K + c], rho_new = sums[4 * K + c], alpha = rho / sums[5 * K + c];
+        omega[c] = sums[6 * K + c] / sums[7 * K + c];
+        beta[c] = (rho_new / rho) * (alpha / omega[c]);
+        if (on[c] && uniform(sums[c] <= thr * bb || sums[K + c] <= thr * bb)) {
+            set_status(flags, c0 + c, ST_CONVERGED);
+            on[c] = false;
+        }
+        if (on[c] && uniform(!usable_divisor(rho) || !usable_divisor(omega[c]) || !isfinite(rho_new) || !isfinite(beta[c]))) {
+            set_status(flags, c0 + c, ST_BREAKDOWN);
+            on[c] = false;
+        }
+        any = any || on[c];
     }
-    const double rho = sums[3], rho_new = sums[4], alpha = rho / sums[5], omega = sums[6] / sums[7];
-    const double beta = (rho_new / rho) * (alpha / omega);
-    if (!usable_divisor(rho) || !usable_divisor(omega) || !isfinite(rho_new) || !isfinite(beta)) {
-        set_status(flags, ST_BREAKDOWN);
-        return;
-    }
+    if (!any) return;
     const int stride = (int)gridDim.x * kThreads;
     int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double pv[4], rv4[4], vv[4], dv[4];
+    for (; i + (U - 1) * stride < n; i += U * stride) {
+        double pv[K][U], rv[K][U], vv[K][U], dv[U];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            pv[u] = p[i + u * stride];
-            rv4[u] = r[i + u * stride];
-            vv[u] = __builtin_nontemporal_load(&v[i + u * stride]);  // v is dead after this kernel
-            dv[u] = dinv ? dinv[i + u * stride] : 1.0;
+        for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                pv[c][u] = p[c][i + u * stride];
+                rv[c][u] = r[c][i + u * stride];
+                vv[c][u] = __builtin_nontemporal_load(&v[c][i + u * stride]);  // v is dead after this kernel
+            }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double zi = dinv ? rv4[u] * dv[u] : rv4[u], wi = dinv ? vv[u] * dv[u] : vv[u];
-            p[i + u * stride] = fma(beta, fma(-omega, wi, pv[u]), zi);
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const double zi = dinv ? rv[c][u] * dv[u] : rv[c][u], wi = dinv ? vv[c][u] * dv[u] : vv[c][u];
+                p[c][i + u * stride] = fma(beta[c], fma(-omega[c], wi, pv[c][u]), zi);
+            }
         }
     }
-    for (; i < n; i += stride) {
-        const double zi = dinv ? r[i] * dinv[i] : r[i], wi = dinv ? v[i] * dinv[i] : v[i];
-        p[i] = fma(beta, fma(-omega, wi, p[i]), zi);
+    if constexpr (U > 1) {
+        for (; i < n; i += stride) {
+            const double di = dinv ? dinv[i] : 1.0;
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                if (!on[c]) continue;
+                const double zi = dinv ? r[c][i] * di : r[c][i], wi = dinv ? v[c][i] * di : v[c][i];
+                p[c][i] = fma(beta[c], fma(-omega[c], wi, p[c][i]), zi);
+            }
+        }
+    }
+}
+
+// grid strides per trip: four wherever the loads of a trip fit the registers, fewer for the wide update and direction kernels
+// (update: six vectors per column; at four strides and four columns its loads alone would be 192 doubles)
+constexpr int kDotU = 4;
+constexpr int s_depth(int K) { return K <= 2 ? 4 : 2; }
+constexpr int update_depth(int K) { return K == 1 ? 4 : K == 2 ? 2 : 1; }
+constexpr int direction_depth(int K) { return K <= 2 ? 4 : 2; }
+
+// what one iteration launches for columns c0 .. c0 + K - 1 between its multiplies: after v = A p^ ...
+template <int K>
+void launch_after_v(int grid, hipStream_t st, int n, const double* r, const double* rh, const double* v, const double* dinv, double* sv,
+                    double* sh, double* s, int* flags, int c0, int cur)
+{
+    hipLaunchKernelGGL((bicg_dot_kernel<K, kDotU>), dim3(grid), dim3(kThreads), 0, st, n, rh, v, s, flags, c0);
+    hipLaunchKernelGGL((bicg_s_kernel<K, s_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, sv, sh, s, flags, c0, cur);
+}
+
+// ... and after t = A s^
+template <int K>
+void launch_after_t(int grid, hipStream_t st, int n, double* p, const double* sh, const double* sv, const double* t, const double* rh,
+                    const double* v, const double* dinv, double* x, long long ldx, double* r, double* s, int* flags, int c0, int cur,
+                    double thr)
+{
+    hipLaunchKernelGGL((bicg_dot2_kernel<K, kDotU>), dim3(grid), dim3(kThreads), 0, st, n, t, sv, s, flags, c0);
+    hipLaunchKernelGGL((bicg_update_kernel<K, update_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, p, sh, sv, t, rh, x, ldx, r, s,
+                       flags, c0, cur, thr);
+    hipLaunchKernelGGL((bicg_direction_kernel<K, direction_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, p, s, flags,
+                       c0, cur, thr);
+}
+
+// f(K as an integral constant, c0) for k columns in groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
+template <typename F>
+void for_each_group(int k, F&& f)
+{
+    const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
+    for (int g = 0, c0 = 0; g < groups; ++g) {
+        const int w = k / groups + (g < k % groups ? 1 : 0);
+        switch (w) {
+        case 1: f(std::integral_constant<int, 1>{}, c0); break;
+        case 2: f(std::integral_constant<int, 2>{}, c0); break;
+        case 3: f(std::integral_constant<int, 3>{}, c0); break;
+        default: f(std::integral_constant<int, 4>{}, c0); break;
+        }
+        c0 += w;
     }
 }
 
@@ -305,7 +592,7 @@ extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, 
     HIP_TRY(hipMemsetAsync(flags, 0, F_COUNT * sizeof(int), st));
     // v = A x0, walked last to first so that the first iteration's first-to-last walk starts on what it left in the cache
     if ((rc = ehyb_spmv_walk(P, x, v, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, v, dinv, r, rh, p, s);
+    hipLaunchKernelGGL(bicg_init_kernel<1>, dim3(grid), dim3(kThreads), 0, st, n, b, (long long)n, v, dinv, r, rh, p, s, 0);
     HIP_TRY(L.read());
     const double bb0 = L.sum(B_BB), bb = bb0 > 0 ? bb0 : 1.0;
     double rr = L.sum(B_RR);
@@ -319,12 +606,9 @@ extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, 
         [&](int cur, bool) -> int {
             int e = ehyb_spmv_walk(P, p, v, st, EHYB_WALK_FIRST_TO_LAST);  // v = A p^
             if (e != EHYB_OK) return e;
-            hipLaunchKernelGGL(bicg_dot_kernel, dim3(grid), dim3(kThreads), 0, st, n, rh, v, s, flags);
-            hipLaunchKernelGGL(bicg_s_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, sv, sh, s, flags, cur);
+            launch_after_v<1>(grid, st, n, r, rh, v, dinv, sv, sh, s, flags, 0, cur);
             if ((e = ehyb_spmv_walk(P, sh, t, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // t = A s^
-            hipLaunchKernelGGL(bicg_dot2_kernel, dim3(grid), dim3(kThreads), 0, st, n, t, sv, s, flags);
-            hipLaunchKernelGGL(bicg_update_kernel, dim3(grid), dim3(kThreads), 0, st, n, p, sh, sv, t, rh, x, r, s, flags, cur, thr);
-            hipLaunchKernelGGL(bicg_direction_kernel, dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, p, s, flags, cur, thr);
+            launch_after_t<1>(grid, st, n, p, sh, sv, t, rh, v, dinv, x, n, r, s, flags, 0, cur, thr);
             return EHYB_OK;
         },
         [&](int) -> int {
@@ -343,10 +627,93 @@ extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, 
     return EHYB_OK;
 }
 
+// ------------------------------------------------------------------ k right-hand sides, two multiplies (ehyb_bicgstab_multi)
+// k solves as above that share v = A p^ and t = A s^ (ehyb_spmm, the same explicit walks).  Every column has its own slots,
+// status word and counter and is decided on the device like the one-vector solve; the host reads all of them at a check point
+// and goes on while any column is running.  A column that has nothing to do at the start, or a non-finite start, gets its
+// status planted before the first burst.
+extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                                   int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab_multi: k = %d right-hand sides (at least 1)", k);
+    if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, P->host.n_cols);
+    int rc = solve_prologue("ehyb_bicgstab_multi", P, B && X, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    const int n = P->host.n_cols;
+    SolveLoop L(n, check_every);
+    const int grid = L.grid;
+    double *r, *rh, *p, *v, *sv, *sh, *t, *s;
+    // two ints per column behind the k sets of slots: one double each
+    HIP_TRY(L.begin(stream, {&r, &rh, &p, &v, &sv, &sh, &t}, (size_t)n * k, &s, (size_t)k * B_COUNT, k));
+    const size_t flags_at = (size_t)k * B_COUNT * kMaxGrid;
+    int* flags = (int*)(s + flags_at);
+    const hipStream_t st = L.st;
+    const double thr = rtol * rtol;
+
+    HIP_TRY(hipMemsetAsync(flags, 0, (size_t)k * F_COUNT * sizeof(int), st));
+    if ((rc = ehyb_spmm(P, X, ldx, v, n, k, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return rc;  // V = A X0
+    for_each_group(k, [&](auto K, int c0) {
+        hipLaunchKernelGGL(bicg_init_kernel<decltype(K)::value>, dim3(grid), dim3(kThreads), 0, st, n, B, (long long)ldb, v, dinv, r, rh,
+                           p, s, c0);
+    });
+    HIP_TRY(L.read());
+    std::vector<double> bb(k), rr(k);
+    std::vector<int> f((size_t)k * F_COUNT, 0);  // {status, iterations} per column, as on the device
+    int n_running = 0;
+    for (int j = 0; j < k; ++j) {
+        const double bb0 = L.sum(j * B_COUNT + B_BB);
+        bb[j] = bb0 > 0 ? bb0 : 1.0;
+        rr[j] = L.sum(j * B_COUNT + B_RR);
+        const int status = !std::isfinite(bb0) || !std::isfinite(rr[j]) ? ST_BREAKDOWN : rr[j] <= thr * bb[j] ? ST_CONVERGED : ST_RUNNING;
+        f[j * F_COUNT + F_STATUS] = status;
+        n_running += status == ST_RUNNING;
+    }
+    if (n_running > 0 && n_running < k && max_iter > 0) {  // the columns that do not start: their status before the first burst
+        HIP_TRY(hipMemcpyAsync(flags, f.data(), f.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+
+    int it = 0;
+    rc = L.run(
+        P, max_iter, it, [&] { return n_running > 0; },
+        [&](int cur, bool) -> int {
+            int e = ehyb_spmm(P, p, n, v, n, k, st, EHYB_WALK_FIRST_TO_LAST);  // V = A P^, stopped columns included
+            if (e != EHYB_OK) return e;
+            for_each_group(k, [&](auto K, int c0) { launch_after_v<decltype(K)::value>(grid, st, n, r, rh, v, dinv, sv, sh, s, flags, c0, cur); });
+            if ((e = ehyb_spmm(P, sh, n, t, n, k, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // T = A S^
+            for_each_group(k, [&](auto K, int c0) {
+                launch_after_t<decltype(K)::value>(grid, st, n, p, sh, sv, t, rh, v, dinv, X, ldx, r, s, flags, c0, cur, thr);
+            });
+            return EHYB_OK;
+        },
+        [&](int) -> int {
+            std::memcpy(f.data(), &L.h[flags_at], f.size() * sizeof(int));
+            n_running = 0;
+            for (int j = 0; j < k; ++j) {
+                rr[j] = L.sum(j * B_COUNT + B_RR);
+                n_running += f[j * F_COUNT + F_STATUS] == ST_RUNNING;
+            }
+            return EHYB_OK;
+        });
+    if (rc != EHYB_OK) return rc;
+    int broke = -1;
+    for (int j = k - 1; j >= 0; --j) {
+        if (iters_done) iters_done[j] = f[j * F_COUNT + F_ITERS];
+        if (rel_residual) rel_residual[j] = std::sqrt(rr[j] / bb[j]);
+        if (f[j * F_COUNT + F_STATUS] == ST_BREAKDOWN) broke = j;
+    }
+    if (broke >= 0)
+        EHYB_FAIL(EHYB_ERR_ARG,
+                  "ehyb_bicgstab_multi: breakdown in column %d after %d iterations (a zero or non-finite rho, r^.v, t.t or omega)", broke,
+                  f[broke * F_COUNT + F_ITERS]);
+    return EHYB_OK;
+}
+
 // ------------------------------------------------------------------ building blocks for a caller that owns the loop
-// The six vector kernels above, one launch each, for a caller that issues the multiplies itself (and for tests that look at
-// one kernel at a time) -- the analogue of ehyb_cg_*_step.  s: `slots` slots of `slot_doubles` doubles and one more double
-// behind them, whose two ints are the status word and the iteration counter (ehyb_bicgstab_layout); every launch uses
+// The six vector kernels above at K = 1, one launch each, for a caller that issues the multiplies itself (and for tests that
+// look at one kernel at a time) -- the analogue of ehyb_cg_*_step.  s: `slots` slots of `slot_doubles` doubles and one more
+// double behind them, whose two ints are the status word and the iteration counter (ehyb_bicgstab_layout); every launch uses
 // slot_doubles / 2 workgroups.  Asynchronous on `stream`.
 extern "C" int ehyb_bicgstab_layout(ehyb_bicgstab_slots* out)
 {
@@ -390,7 +757,8 @@ extern "C" int ehyb_bicgstab_init_step(int n, const double* b, const double* q, 
 {
     int rc = check_step("ehyb_bicgstab_init_step", n, {b, q, r, rh, p, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_init_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, b, q, dinv, r, rh, p, s);
+    hipLaunchKernelGGL(bicg_init_kernel<1>, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, b, (long long)n, q, dinv, r, rh,
+                       p, s, 0);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -399,7 +767,7 @@ extern "C" int ehyb_bicgstab_dot_step(int n, const double* rh, const double* v, 
 {
     int rc = check_step("ehyb_bicgstab_dot_step", n, {rh, v, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_dot_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, rh, v, s, flags_of(s));
+    hipLaunchKernelGGL((bicg_dot_kernel<1, kDotU>), dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, rh, v, s, flags_of(s), 0);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -409,8 +777,8 @@ extern "C" int ehyb_bicgstab_s_step(int n, const double* r, const double* v, con
 {
     int rc = check_step("ehyb_bicgstab_s_step", n, {r, v, sv, sh, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_s_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v, dinv, sv, sh, s, flags_of(s),
-                       cur & 1);
+    hipLaunchKernelGGL((bicg_s_kernel<1, s_depth(1)>), dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v, dinv, sv, sh, s,
+                       flags_of(s), 0, cur & 1);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -419,7 +787,7 @@ extern "C" int ehyb_bicgstab_dot2_step(int n, const double* t, const double* sv,
 {
     int rc = check_step("ehyb_bicgstab_dot2_step", n, {t, sv, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_dot2_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, t, sv, s, flags_of(s));
+    hipLaunchKernelGGL((bicg_dot2_kernel<1, kDotU>), dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, t, sv, s, flags_of(s), 0);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -429,8 +797,8 @@ extern "C" int ehyb_bicgstab_update_step(int n, const double* p, const double* s
 {
     int rc = check_step("ehyb_bicgstab_update_step", n, {p, sh, sv, t, rh, x, r, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_update_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, p, sh, sv, t, rh, x, r, s,
-                       flags_of(s), cur & 1, thr);
+    hipLaunchKernelGGL((bicg_update_kernel<1, update_depth(1)>), dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, p, sh, sv, t,
+                       rh, x, (long long)n, r, s, flags_of(s), 0, cur & 1, thr);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -440,8 +808,8 @@ extern "C" int ehyb_bicgstab_direction_step(int n, const double* r, const double
 {
     int rc = check_step("ehyb_bicgstab_direction_step", n, {r, v, p, s});
     if (rc != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_direction_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v, dinv, p, s, flags_of(s),
-                       cur & 1, thr);
+    hipLaunchKernelGGL((bicg_direction_kernel<1, direction_depth(1)>), dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, r, v,
+                       dinv, p, s, flags_of(s), 0, cur & 1, thr);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }

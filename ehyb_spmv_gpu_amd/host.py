@@ -511,6 +511,25 @@ class Plan:
             raise EhybError(rc, "ehyb_bicgstab")
         return dx.download(), it.value, rel.value
 
+    def bicgstab_multi(self, B, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_bicgstab_multi: k independent BiCGSTAB solves (right Jacobi-preconditioned if inv_diag is given) that share both
+        multiplies of every iteration; B, X0 (k, n) in the permuted numbering, column j solved as bicgstab(B[j]) would -- with
+        plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,)), the counts those of the device.  A
+        breakdown in any column raises EhybError, unless allow_breakdown: then a broken column holds its last good iterate.
+        The multiplies are as wide as spmm_max_k allows (build the plan with lds_doubles = 20480 // k)."""
+        B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
+        k, n = B.shape
+        assert n == self.n, (n, self.n)
+        X0 = np.zeros_like(B) if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).reshape(k, n)
+        db, dx = DeviceBuffer(k * n).upload(B.ravel()), DeviceBuffer(k * n).upload(X0.ravel())
+        dd = None if inv_diag is None else DeviceBuffer(n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
+        it, rel = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64)
+        rc = self.lib.ehyb_bicgstab_multi(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k,
+                                          max_iter, rtol, check_every, C.c_void_p(stream), _ptr(it, C.c_int), _ptr(rel, C.c_double))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, "ehyb_bicgstab_multi")
+        return dx.download().reshape(k, n), it, rel
+
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)

@@ -832,6 +832,30 @@ int ehyb_pcg_multi(ehyb_plan* plan, const double* inv_diag_dev, const double* B_
                    int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
 
 /*
+ * k INDEPENDENT BiCGSTAB solves on the plan's (unsymmetric) matrix that share both multiplies of every iteration: column j of X
+ * is what ehyb_bicgstab(b_j) makes of it (not a block method: every column keeps its own rho, alpha, omega, beta, status word
+ * and iteration counter).  Per iteration ehyb_spmm of the k directions p^ (first to last) and of the k s^ (last to first) --
+ * ceil(k / ehyb_spmm_max_k) passes over the matrix each -- and the five vector kernels of ehyb_bicgstab up to four columns wide.
+ * B, X, ldb, ldx, inv_diag_dev, iters_done, rel_residual, stream and check_every as ehyb_pcg_multi: column j at B + j*ldb and
+ * X + j*ldx, ldb, ldx >= n, only rows [0, n) of a column are read or written, the outputs are host arrays of k entries and may be
+ * NULL.  X holds the initial guesses on entry and, per column, the last iterate whose update had finite scalars on return.
+ * Stopping and breakdown, per column and on the device, after every iteration, by the rules of ehyb_bicgstab: a column whose
+ * status is set is skipped by every vector kernel from then on -- its x, r, p^ and partial sums stop changing -- while the
+ * others go on; the multiplies keep multiplying it (a NaN stays in its column, ehyb_spmm).  A column with r.r <= rtol^2 b.b at
+ * the start is converged with 0 iterations, one with a non-finite b.b or r.r a breakdown with x untouched.  The host looks every
+ * check_every iterations and launches on while any column is running and fewer than max_iter iterations were issued.
+ * iters_done[j] is column j's device counter, rel_residual[j] = sqrt(r.r / b.b) of its last iterate (b.b = 0: 1 in its place).
+ * With plain storage column j therefore equals ehyb_bicgstab on b_j bit for bit -- x, iters_done and rel_residual -- for every
+ * k, every check_every, graphs and plain launches (cfg.graphs = 2), and whatever the other columns do, but for rows the residual
+ * splits into several segments (ehyb_spmm); with symmetric pair storage or a panel-form residual up to the order of summation.
+ * If any column broke down the call returns EHYB_ERR_ARG ("breakdown" in ehyb_last_error) after every output is written.
+ * Needs a plan over all rows.  EHYB_ERR_ARG for k < 1, ldb or ldx < n, a null plan, B or X, max_iter < 0, a negative or NaN rtol
+ * or a plan not over all rows, checked in this order; EHYB_ERR_STATE on a plan never uploaded -- all before any device work.
+ */
+int ehyb_bicgstab_multi(ehyb_plan* plan, const double* inv_diag_dev, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
+                        int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
