@@ -83,7 +83,8 @@ class Config(C.Structure):
         ("ell_nt", C.c_int32),
         ("ell_keep", C.c_int32),
         ("ell_triples", C.c_int32),
-        ("reserved", C.c_int32 * 19),
+        ("val_f32", C.c_int32),
+        ("reserved", C.c_int32 * 18),
     ]
 
 
@@ -158,6 +159,8 @@ SIGNATURES = {
     "ehyb_plan_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
     "ehyb_plan_device_col_words": (C.c_int64, [_vp]),
     "ehyb_plan_device_cols": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32)]),
+    "ehyb_plan_device_value_bytes": (C.c_int, [_vp, _i64p, _i64p]),
+    "ehyb_plan_device_values_f32": (C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int64]),
     "ehyb_spmv": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_spmv_phase": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
     "ehyb_spmv_walk": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
@@ -205,6 +208,9 @@ SIGNATURES = {
     "ehyb_measure_read_bw": (C.c_int, [C.c_size_t, C.c_int, _dp]),
     "ehyb_cg": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_pcg_refine": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _ip, _ip, _dp]),
+    "ehyb_refine_residual_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ehyb_refine_axpy_step": (C.c_int, [C.c_int, _vp, _vp, _vp]),
     "ehyb_bicgstab": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cg_multi": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),

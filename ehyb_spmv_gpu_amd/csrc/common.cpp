@@ -108,6 +108,12 @@ OmpScope::OmpScope(int want)
 }
 OmpScope::~OmpScope() { omp_set_num_threads(saved); }
 
+void device_values_f32(const double* src, size_t n, float* dst)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)n; ++i) dst[i] = (float)src[i];  // cvtsd2ss: nearest-even, +-inf beyond the range, subnormals kept
+}
+
 static int round_down(int v, int m) { return v / m * m; }
 
 Config resolve_config(const ehyb_config* in)
@@ -188,6 +194,7 @@ Config resolve_config(const ehyb_config* in)
     c.ell_nt = (z.ell_nt >= 1 && z.ell_nt <= 5) ? z.ell_nt : 4;  // 4: a fixed set of slabs stays in the Infinity Cache (ell_keep_rule)
     c.ell_keep = std::min(1000, std::max(0, z.ell_keep));  // 0: by the size of the Infinity Cache (ell_keep_rule)
     c.ell_triples = z.ell_triples == 2 ? 2 : 1;
+    c.val_f32 = z.val_f32 == 1 ? 1 : 0;
     c.er_queue = (z.er_queue == 1 || z.er_queue == 2) ? z.er_queue : 0;  // 0: by the number of items per resident workgroup (launch_panel_scale)
     // the automatic choice of the direct shape is for callers that left the window sizing alone: a caller
     // that names a window (lds_doubles / part_rows other than the defaults) gets that window
@@ -267,6 +274,7 @@ void ehyb_config_resolve(const ehyb_config* in, ehyb_config* out)
     r.ell_nt = c.ell_nt;
     r.ell_keep = c.ell_keep;
     r.ell_triples = c.ell_triples;
+    r.val_f32 = c.val_f32;
     *out = r;
 }
 

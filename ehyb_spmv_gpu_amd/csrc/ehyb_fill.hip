@@ -10,7 +10,7 @@
 // numeric part for new values on the same pattern (the next Newton step, the next time step, the next
 // matrix of a parameter sweep) as one gather per stream, straight into the arrays the multiply reads:
 //
-//   ehyb_fill_kernel        dst[i] = src[i] < 0 ? 0.0 : V[order ? order[src[i]] : src[i]]
+//   ehyb_fill_kernel<T>     dst[i] = (T)(src[i] < 0 ? 0.0 : V[order ? order[src[i]] : src[i]]);  T = float with cfg.val_f32
 //                           ELL stream ([pair][lane][2] incl. inline residual pairs), CSR residual
 //                           segments, panel stream of the residual -- whatever the plan holds on the device.
 //                           `order` composes the caller's entry order before ehyb_matrix_reorder with the
@@ -35,7 +35,9 @@ namespace {
 constexpr int kFillThreads = 256;
 constexpr int kFillUnroll = 4;  // independent gathers in flight per lane
 
-__global__ __launch_bounds__(kFillThreads) void ehyb_fill_kernel(double* __restrict__ dst, const int32_t* __restrict__ src, long long n,
+// T: a value as the device holds it -- double, or float (cfg.val_f32: rounded to nearest-even as ehyb_plan_upload rounds)
+template <class T>
+__global__ __launch_bounds__(kFillThreads) void ehyb_fill_kernel(T* __restrict__ dst, const int32_t* __restrict__ src, long long n,
                                                                  const double* __restrict__ V, const int32_t* __restrict__ order)
 {
     const long long stride = (long long)gridDim.x * kFillThreads;
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(kFillThreads) void ehyb_fill_kernel(double* __restr
 #pragma unroll
         for (int u = 0; u < kFillUnroll; ++u) {
             const long long i = base + u * stride;
-            if (i < n) dst[i] = v[u];
+            if (i < n) dst[i] = (T)v[u];
         }
     }
 }
@@ -179,7 +181,10 @@ extern "C" int ehyb_plan_set_values(ehyb_plan* P, const double* values, int64_t 
                  {P->d_pb_val, P->d_pb_src, P->d_pb_val ? (long long)H.pb_padded : 0}};
     for (const Job& j : jobs) {
         if (!j.dst || j.n == 0) continue;
-        hipLaunchKernelGGL(ehyb_fill_kernel, dim3(grid_for(j.n)), dim3(kFillThreads), 0, st, j.dst, j.src, j.n, dV, dOrder);
+        if (P->cfg.val_f32 == 1)  // (the plan holds floats behind the same pointers; the pair check above stays on the fp64 input)
+            hipLaunchKernelGGL(ehyb_fill_kernel<float>, dim3(grid_for(j.n)), dim3(kFillThreads), 0, st, (float*)j.dst, j.src, j.n, dV, dOrder);
+        else
+            hipLaunchKernelGGL(ehyb_fill_kernel<double>, dim3(grid_for(j.n)), dim3(kFillThreads), 0, st, j.dst, j.src, j.n, dV, dOrder);
         HIP_TRY(hipGetLastError());
     }
     P->host_values_stale = true;

@@ -77,6 +77,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))
     ell_items<THREADS, K, true, false, INLINE_ER, SYM>(A, ldx, ldy);
 }
 
+// cfg.val_f32: the one-vector kernel over a value stream held in fp32 ([pair][lane][2] floats, 8 B per lane and pair): the same
+// body with float2 loads, LDS slab counter, no stamps.  Plain storage without an inline residual keeps the 64 VGPRs of the fp64
+// kernel; with an inline residual the conversions on top of both forms of the column words spilled there (20 B per lane), so that
+// arm takes the 128 VGPRs of SYM: one workgroup of 1024 threads per CU whatever the window.
+template <int THREADS, bool INLINE_ER, bool SYM>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu((SYM || INLINE_ER) ? 4 : 8, 8))) void ehyb_ell_f32_kernel(const EllArgs A)
+{
+    ell_items<THREADS, 1, true, false, INLINE_ER, SYM, float2>(A, 0, 0);
+}
+
 // Two-launch form (multi-GPU phase 2, or a residual too large to ride in the window launch).
 template <int THREADS, bool ASSIGN>
 __global__ __launch_bounds__(THREADS) void ehyb_er_kernel(const int4* __restrict__ blocks,
@@ -87,6 +97,15 @@ __global__ __launch_bounds__(THREADS) void ehyb_er_kernel(const int4* __restrict
                                                           const double* __restrict__ x, double* __restrict__ y)
 {
     er_blocks<THREADS, ASSIGN, 1>(blocks, seg_ptr, seg_row, col, val, x, 0, y, 0);
+}
+
+// cfg.val_f32: one float per residual entry
+template <int THREADS, bool ASSIGN>
+__global__ __launch_bounds__(THREADS) void ehyb_er_f32_kernel(const int4* __restrict__ blocks, const int64_t* __restrict__ seg_ptr,
+                                                              const int* __restrict__ seg_row, const int* __restrict__ col,
+                                                              const float* __restrict__ val, const double* __restrict__ x, double* __restrict__ y)
+{
+    er_blocks<THREADS, ASSIGN, 1, float>(blocks, seg_ptr, seg_row, col, val, x, 0, y, 0);
 }
 
 template <int THREADS, bool ASSIGN, int K>
@@ -199,9 +218,18 @@ static int ell_auto_keep1024(long long value_bytes, long long plain_bytes)
 
 // successive launches of the plan walk in alternating directions by themselves (cfg.ell_alternate): where the stream does not
 // fit the cache but the cache is still a fair share of it.  A pinned set is the same for both directions: such plans do not alternate.
+// Bytes of the window launch's value stream and of everything it reads as the DEVICE holds them: cfg.val_f32 takes 4 B off
+// every value slot (stats, a property of the host layout, count 8)
+static long long ell_value_bytes(const ehyb_plan* P) { return (P->cfg.val_f32 == 1 ? 4 : 8) * (long long)P->host.stats.size_block_ell; }
+static long long ell_format_bytes(const ehyb_plan* P)
+{
+    const ehyb_stats& S = P->host.stats;
+    return S.bytes_format_ell - (P->cfg.val_f32 == 1 ? 4 * (long long)(S.size_block_ell + (P->host.inline_er ? S.er_inline : 0)) : 0);
+}
+
 static bool ell_alternates(const ehyb_plan* P)
 {
-    const long long b = P->host.stats.bytes_format_ell;
+    const long long b = ell_format_bytes(P);
     const bool pinned = P->cfg.ell_nt == 4 || P->cfg.ell_nt == 5;
     return P->cfg.ell_alternate == 1 || (P->cfg.ell_alternate == 0 && !pinned && b > kInfinityCache && b <= (8192ll << 20));
 }
@@ -209,24 +237,24 @@ static bool ell_alternates(const ehyb_plan* P)
 // cfg.ell_nt -> (keep1024, shape) of a launch; alternating_walk: the launch is one of an alternating walk (ell_walk)
 static void ell_keep_rule(const ehyb_plan* P, bool alternating_walk, int* keep1024, int* shape)
 {
-    const ehyb_stats& S = P->host.stats;
+    const long long format_bytes = ell_format_bytes(P);
     const int nt = P->cfg.ell_nt;
     // a stream the 256 MB Infinity Cache holds whole stays there from one multiply to the next: plain loads (120 k rows, 65 MB: 15.4 us, with
     // the hint 16.2)
-    const bool fits = S.bytes_format_ell <= kInfinityCache;
+    const bool fits = format_bytes <= kInfinityCache;
     *shape = nt == 4 ? ELL_KEEP_SPREAD : (nt == 5 ? ELL_KEEP_BLOCK : ELL_KEEP_WALK_END);
     if (nt == 1 || nt == 2) {
         *keep1024 = nt == 2 ? 1024 : 0;   // the A/B arms: never / always the hint
     } else if (nt == 4 || nt == 5) {
-        const long long value_bytes = 8 * S.size_block_ell;
-        *keep1024 = P->cfg.ell_keep > 0 ? (int)((long long)P->cfg.ell_keep * 1024 / 1000) : ell_auto_keep1024(value_bytes, S.bytes_format_ell - value_bytes);
+        const long long value_bytes = ell_value_bytes(P);  // (the plain bytes -- everything else -- do not depend on cfg.val_f32)
+        *keep1024 = P->cfg.ell_keep > 0 ? (int)((long long)P->cfg.ell_keep * 1024 / 1000) : ell_auto_keep1024(value_bytes, P->host.stats.bytes_format_ell - 8 * (long long)P->host.stats.size_block_ell);
     } else if (fits) {
         *keep1024 = 1024;
     } else if (alternating_walk) {
         // cfg.ell_nt = 3: the END of every walk -- the share of the stream the cache can hold -- is read with plain loads, so that it is
         // still there when the next launch starts from that end (half, three quarters and five quarters of that share measured level:
         // profiles/r04_nt_hints_ab.txt)
-        const double keep = std::min(1.0, (double)kInfinityCache / (double)std::max<long long>(1, S.bytes_format_ell));
+        const double keep = std::min(1.0, (double)kInfinityCache / (double)std::max<long long>(1, format_bytes));
         *keep1024 = 1024 - (int)(1024.0 * (1.0 - keep));
     } else {
         *keep1024 = 0;
@@ -293,6 +321,7 @@ struct EllKernel {
     int threads, k;
     bool dyn, stamp, inl, sym;
     const void* fn;
+    bool f32 = false;  // cfg.val_f32: ehyb_ell_f32_kernel
 };
 
 template <int T, int K, bool DYN, bool STAMP, bool INL, bool SYM>
@@ -322,6 +351,10 @@ static void add_ell_kernels(std::vector<EllKernel>* v)
     add_ell_kernels<T, 2>(v);
     add_ell_kernels<T, 3>(v);
     add_ell_kernels<T, 4>(v);
+    v->insert(v->end(), {{T, 1, true, false, false, false, (const void*)ehyb_ell_f32_kernel<T, false, false>, true},
+                         {T, 1, true, false, true, false, (const void*)ehyb_ell_f32_kernel<T, true, false>, true},
+                         {T, 1, true, false, false, true, (const void*)ehyb_ell_f32_kernel<T, false, true>, true},
+                         {T, 1, true, false, true, true, (const void*)ehyb_ell_f32_kernel<T, true, true>, true}});
 }
 
 static const std::vector<EllKernel>& ell_kernels()
@@ -345,9 +378,13 @@ int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y,
     if (H.pb_assign && H.segs.empty()) return EHYB_OK;  // no partition kept its window: pass 2 of the panel residual assigns every row
     // cfg.ell_variant: 0/1 = LDS slab counter (default), 3 = static round-robin (A/B arm, tools/sweep.py --variants; one vector only)
     const bool dyn = k > 1 || P->cfg.ell_variant != 3;
+    const bool f32 = P->cfg.val_f32 == 1;
+    if (f32 && (k > 1 || !dyn || stamps))
+        EHYB_FAIL(EHYB_ERR_ARG, "window launch: cfg.val_f32 serves one column, the LDS slab counter and no stamps (%d columns%s%s)", k,
+                  dyn ? "" : ", cfg.ell_variant = 3", stamps ? ", a stamped or probe launch" : "");
     const void* fn = nullptr;
     for (const EllKernel& e : ell_kernels()) {
-        if (e.threads == P->cfg.threads && e.k == k && e.dyn == dyn && e.stamp == (stamps != nullptr) && e.inl == inl && e.sym == H.sym) {
+        if (e.f32 == f32 && e.threads == P->cfg.threads && e.k == k && e.dyn == dyn && e.stamp == (stamps != nullptr) && e.inl == inl && e.sym == H.sym) {
             fn = e.fn;
             break;
         }
@@ -548,10 +585,15 @@ int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y,
          (const void*)ehyb_er_k_kernel<256, false, 4>},
         {(const void*)ehyb_er_kernel<256, true>, (const void*)ehyb_er_k_kernel<256, true, 2>, (const void*)ehyb_er_k_kernel<256, true, 3>,
          (const void*)ehyb_er_k_kernel<256, true, 4>}};
+    const void* launch = fn[H.direct][k - 1];  // ASSIGN: the direct shape
+    if (P->cfg.val_f32 == 1) {
+        if (k > 1) EHYB_FAIL(EHYB_ERR_ARG, "residual launch: cfg.val_f32 serves one column, not %d", k);
+        launch = H.direct ? (const void*)ehyb_er_f32_kernel<256, true> : (const void*)ehyb_er_f32_kernel<256, false>;  // (same arguments: d_er_val holds floats)
+    }
     const int4* blocks = (const int4*)P->d_er_blocks;
     void* args1[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &y};
     void* argsk[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &ldx, &y, &ldy};
-    (void)hipLaunchKernel(fn[H.direct][k - 1], dim3(n_blocks), dim3(256), k == 1 ? args1 : argsk, 0, st);  // ASSIGN: the direct shape
+    (void)hipLaunchKernel(launch, dim3(n_blocks), dim3(256), k == 1 ? args1 : argsk, 0, st);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
@@ -571,6 +613,18 @@ static int upload(T** dst, const std::vector<T, A>& src)
     HIP_TRY(hipMalloc((void**)dst, bytes));
     if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return EHYB_OK;
+}
+
+// cfg.val_f32: a value stream converted on the host (device_values_f32) and only the floats sent; *dst keeps its type, the
+// fp32 kernels reinterpret it
+static int upload_f32(const ehyb_plan* P, double** dst, const double* src, size_t n)
+{
+    BigVec<float> f(n);
+    {
+        OmpScope omp(P->cfg.host_threads);
+        device_values_f32(src, n, f.data());
+    }
+    return upload((float**)dst, f);
 }
 
 static void free_device(ehyb_plan* P)
@@ -716,6 +770,7 @@ int ehyb_debug_ell_stamps_probe(ehyb_plan* P, const double* x, double* y, unsign
 int ehyb_debug_ell_stamps(ehyb_plan* P, const double* x, double* y, unsigned long long* out_host)
 {
     if (!P || !P->uploaded || !out_host) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_ell_stamps: bad arguments");
+    if (P->cfg.val_f32 == 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_ell_stamps: no stamped kernel is built for cfg.val_f32");
     const int n_items = (int)(P->host.items.size() / kItemWords);
     unsigned long long* d = nullptr;
     HIP_TRY(hipMalloc((void**)&d, (size_t)n_items * 32));
@@ -749,6 +804,7 @@ int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* s
 {
     clear_error();
     if (!P || !P->uploaded || !x || !y) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_tune: bad arguments");
+    if (P->cfg.val_f32 == 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_tune: the tuning measures stamped launches, which cfg.val_f32 has none of");
     if (span_before_us) *span_before_us = 0;
     if (span_after_us) *span_after_us = 0;
     const HostLayout& H = P->host;
@@ -890,6 +946,11 @@ int ehyb_plan_upload(ehyb_plan* P)
     clear_error();
     if (!P) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_upload: null plan");
     if (P->uploaded) return EHYB_OK;
+    // (before the device is looked for: a property of the plan)
+    if (P->cfg.val_f32 == 1 && (P->host.er_panel || P->host.deferred.pending))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_upload: cfg.val_f32 is not built for a residual in panel form (the panel passes read fp64 values)");
+    if (P->cfg.val_f32 == 1 && P->cfg.ell_variant == 3)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_upload: cfg.val_f32 has no round-robin kernel (cfg.ell_variant = 3)");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
         EHYB_FAIL(EHYB_ERR_NO_DEVICE, "ehyb_plan_upload: no HIP device visible (the EHYB multiply has no CPU fallback)");
@@ -903,7 +964,15 @@ int ehyb_plan_upload(ehyb_plan* P)
         return rc;                             \
     }
     UP(d_halo_cols, halo_cols)
-    UP(d_ell_val, ell_val)
+    const bool f32 = P->cfg.val_f32 == 1;
+    if (f32) {
+        if ((rc = upload_f32(P, &P->d_ell_val, H.ell_val.data(), H.ell_val.size())) != EHYB_OK) {
+            free_device(P);
+            return rc;
+        }
+    } else {
+        UP(d_ell_val, ell_val)
+    }
     if (P->cfg.ell_triples == 1) {
         // the device's own form of the column words and slab records (col_triples.h); the host arrays stay the definition
         BigVec<uint32_t> words;
@@ -949,7 +1018,14 @@ int ehyb_plan_upload(ehyb_plan* P)
         UP(d_er_seg_ptr, er_seg_ptr)
         UP(d_er_seg_row, er_seg_row)
         UP(d_er_col, er_col)
-        UP(d_er_val, er_val)
+        if (f32) {
+            if ((rc = upload_f32(P, &P->d_er_val, H.er_val.data(), H.er_val.size())) != EHYB_OK) {
+                free_device(P);
+                return rc;
+            }
+        } else {
+            UP(d_er_val, er_val)
+        }
         UP(d_er_blocks, er_blocks)
     }
 #undef UP
@@ -1015,7 +1091,7 @@ int64_t ehyb_plan_resident_bytes(const ehyb_plan* P)
         const int sb = H.segs[sg + SEG_SLAB_BEGIN], se = H.segs[sg + SEG_SLAB_END];
         for (int s = sb; s < se; ++s)   // (WALK_END: the walk first to last)
             if (ell_slab_resident(s - sb, se - sb, keep1024, shape))
-                bytes += (int64_t)unpack_slab_shape(H.slab_meta[(size_t)s * kSlabWords + SLAB_SHAPE]).pairs * kSlabRows * 16;
+                bytes += (int64_t)unpack_slab_shape(H.slab_meta[(size_t)s * kSlabWords + SLAB_SHAPE]).pairs * kSlabRows * (P->cfg.val_f32 == 1 ? 8 : 16);
     }
     return bytes;
 }

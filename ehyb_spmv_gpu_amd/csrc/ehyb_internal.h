@@ -116,6 +116,7 @@ struct Config {
                             // Cache (spread over a segment / its first slabs), 3 all but the end of an alternating walk, 1 every slab, 2 never
     int ell_keep;           // ell_nt 4 / 5: the share of the slabs in that set, per mille; 0 = from the cache's size (ehyb_hip.hip)
     int ell_triples;        // 1: the device holds one column base per node triple where a slab allows it (col_triples.h), 2: the host's words
+    int val_f32;            // 1: the device holds the value streams in fp32 (device_values_f32), 0: fp64
 };
 Config resolve_config(const ehyb_config* cfg);
 
@@ -321,6 +322,12 @@ inline int spmm_width(const HostLayout& H)
 // One window kernel carries no triple arm (ell_device.h: it spilled with both forms of the column words in it): K columns from this
 // width up with symmetric pairs AND an inline residual.  A plan that can launch it keeps the host's column words on the device
 // (col_triples.cpp: plan_keeps_pair_words); launch_window refuses that kernel on a plan with coded slabs.
+// cfg.val_f32: the value streams as the device holds them -- every fp64 value rounded to nearest-even (the host's default
+// rounding mode; beyond the fp32 range +-inf, fp32 subnormals kept, NaN stays NaN).  common.cpp, on the OpenMP threads of the scope
+// the caller opened.
+void device_values_f32(const double* src, size_t n, float* dst);
+// the widest pass of ehyb_spmm on the plan: the fp32-value kernels are built one column wide
+inline int plan_spmm_width(const ehyb_plan* P);
 constexpr int kNoTripleArmK = 4;
 static_assert(kNoTripleArmK <= kSpmmMaxK + 1, "a width no kernel is built for");
 inline bool plan_keeps_pair_words(const HostLayout& H) { return H.sym && H.inline_er && spmm_width(H) >= kNoTripleArmK; }
@@ -429,3 +436,4 @@ struct ehyb_plan {
     std::atomic<int> launch_parity{0};
     std::atomic<int> panel_parity{0};
 };
+inline int ehyb::plan_spmm_width(const ehyb_plan* P) { return P->cfg.val_f32 == 1 ? 1 : spmm_width(P->host); }

@@ -16,7 +16,7 @@ int ehyb_spmm_max_k(const ehyb_plan* P, int* k_max)
 {
     clear_error();
     if (!P || !k_max) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_spmm_max_k: null argument");
-    *k_max = spmm_width(P->host);
+    *k_max = plan_spmm_width(P);
     return EHYB_OK;
 }
 
@@ -32,7 +32,7 @@ int ehyb_spmm(ehyb_plan* P, const double* X, int64_t ldx, double* Y, int64_t ldy
     if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmm: plan not uploaded (no CPU fallback exists)");
     hipStream_t st = (hipStream_t)stream;
     // ceil(k / k_max) passes over the matrix, as even as they come (k = 5 on a plan of k_max 4: 3 + 2)
-    const int kmax = spmm_width(H), passes = (k + kmax - 1) / kmax;
+    const int kmax = plan_spmm_width(P), passes = (k + kmax - 1) / kmax;
     int j0 = 0;
     for (int p = 0; p < passes; ++p) {
         const int w = k / passes + (p < k % passes ? 1 : 0);

@@ -103,6 +103,43 @@ __device__ __forceinline__ double2 ell_load_pair(const double2* __restrict__ p)
     }
     return *p;
 }
+// cfg.val_f32: the pair as the device holds it in fp32 -- one 8-byte load.  A step keeps what its loads return (float2: half the
+// registers of a double2 while the loads are in flight) and converts each half to fp64 once, where the pair is first used
+// (ell_pair); everything behind that is the fp64 code.
+template <bool NT>
+__device__ __forceinline__ float2 ell_load_pair(const float2* __restrict__ p)
+{
+    if (NT) {
+        typedef float pair_f32 __attribute__((ext_vector_type(2)));
+        const pair_f32 r = __builtin_nontemporal_load(reinterpret_cast<const pair_f32*>(p));
+        return make_float2(r.x, r.y);
+    }
+    return *p;
+}
+__device__ __forceinline__ const double2& ell_pair(const double2& r) { return r; }
+__device__ __forceinline__ double2 ell_pair(const float2& r) { return make_double2((double)r.x, (double)r.y); }
+// a pair used where it is loaded (single pairs behind the steps, the inline residual)
+template <bool NT, class VP>
+__device__ __forceinline__ double2 ell_load_pair_f64(const VP* __restrict__ p)
+{
+    if constexpr (sizeof(VP) == sizeof(double2))
+        return ell_load_pair<NT>(p);
+    else
+        return ell_pair(ell_load_pair<NT>(p));
+}
+template <class VP>
+__device__ __forceinline__ VP ell_zero_pair();
+template <>
+__device__ __forceinline__ double2 ell_zero_pair<double2>() { return make_double2(0.0, 0.0); }
+template <>
+__device__ __forceinline__ float2 ell_zero_pair<float2>() { return make_float2(0.0f, 0.0f); }
+// fp32 values: the loads of a step are issued before its first conversion (left to itself the scheduler converts and multiplies
+// each pair behind its own load, one load in flight per wave); nothing for fp64, whose kernels stay as they are
+template <class VP>
+__device__ __forceinline__ void ell_loads_issued()
+{
+    if constexpr (sizeof(VP) == sizeof(float2)) __builtin_amdgcn_sched_barrier(0);
+}
 
 // The K values of window column `idx`: one ds_read_b128 for K = 2, two for K = 4 (16-byte aligned: 16 K bytes per column).
 template <int K>
@@ -212,7 +249,8 @@ __device__ __forceinline__ void ell_triple_word(const double2& v0, const double2
 }
 
 // One slab of 64 rows.  xy (K = 1, A.xy_out set): the lane's running sum of y[row] * x[row].
-template <int K, bool INLINE_ER, bool SYM, bool NT>
+// VP: the value pair as the device holds it -- double2, or float2 (cfg.val_f32: A.ell_val reinterpreted, same offsets in pairs).
+template <int K, bool INLINE_ER, bool SYM, bool NT, class VP = double2>
 __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long long ldy, const double* __restrict__ win, double* yacc, int s,
                                          int base, int pe, int lane, double& xy)
 {
@@ -220,7 +258,7 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
     const uint4 sm = A.slab_meta[s];
     const int np = (int)(sm.w >> 16);
     const int G = (int)(sm.w & 0x3fu) + 1;  // lanes with equal column lists share one word per pair
-    const double2* __restrict__ v = A.ell_val + (size_t)sm.x * 64 + lane;
+    const VP* __restrict__ v = reinterpret_cast<const VP*>(A.ell_val) + (size_t)sm.x * 64 + lane;
     // the lane's group (bits 0-5) and, with symmetric pairs, its part in the group's sum (bits 6-7)
     const uint32_t lgb = A.lane_group[(size_t)s * 64 + lane];
     const int code = SYM ? (int)(lgb >> 6) : 0;
@@ -234,10 +272,10 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
         // First, so that the loads are in flight while the ELL pairs stream; only the gather of x
         // from global memory (L2) waits for them.  No second launch, no read-modify-write of y.
         const int ner = (int)(sm.w >> 8) & 0xff;
-        const double2* __restrict__ ve = v + (size_t)np * 64;
+        const VP* __restrict__ ve = v + (size_t)np * 64;
         const uint32_t* __restrict__ ce = A.ell_col + sm.y + (size_t)np * G + lane;
         for (int q = 0; q < ner; ++q) {
-            const double2 vv = ve[q * 64];
+            const double2 vv = ell_load_pair_f64<false>(ve + q * 64);
             const uint32_t ca = ce[q * 128], cb = ce[q * 128 + 64];
             double xa[K], xb[K];
 #pragma unroll
@@ -279,7 +317,7 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
         // Running pointers and a count.  The empty asm hides where the pointers come from: without it the compiler hoists this
         // arm's lane addresses (ell_val + lane + a constant, ...) out of the walk over the slabs, next to the ones of the pair
         // form, and the kernels built for 64 VGPRs have no registers for both -- they spilled.
-        const double2* vp = v;
+        const VP* vp = v;
         const uint32_t* cp = c;
         asm volatile("" : "+v"(vp), "+v"(cp));
         int left = np;
@@ -306,21 +344,23 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
         } else {
             if constexpr (SYM && K == 1) {
                 for (; left >= 6; left -= 6, vp += 6 * 64, cp += 2 * G) {
-                    double2 vv[6];
+                    VP vv[6];
 #pragma unroll
                     for (int q = 0; q < 6; ++q) vv[q] = ell_load_pair<NT>(vp + q * 64);
                     const uint32_t w0 = cp[0], w1 = cp[G];
-                    ell_triple_word<K, SYM>(vv[0], vv[1], vv[2], w0, 3, win, yacc, xi, code, acc0, acc1);
-                    ell_triple_word<K, SYM>(vv[3], vv[4], vv[5], w1, 3, win, yacc, xi, code, acc0, acc1);
+                    ell_loads_issued<VP>();
+                    ell_triple_word<K, SYM>(ell_pair(vv[0]), ell_pair(vv[1]), ell_pair(vv[2]), w0, 3, win, yacc, xi, code, acc0, acc1);
+                    ell_triple_word<K, SYM>(ell_pair(vv[3]), ell_pair(vv[4]), ell_pair(vv[5]), w1, 3, win, yacc, xi, code, acc0, acc1);
                 }
             }
 #pragma nounroll
             for (; left >= 3; left -= 3, vp += 3 * 64, cp += G) {
-                double2 vv[3];
+                VP vv[3];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) vv[q] = ell_load_pair<NT>(vp + q * 64);
                 const uint32_t w0 = cp[0];
-                ell_triple_word<K, SYM>(vv[0], vv[1], vv[2], w0, 3, win, yacc, xi, code, acc0, acc1);
+                ell_loads_issued<VP>();
+                ell_triple_word<K, SYM>(ell_pair(vv[0]), ell_pair(vv[1]), ell_pair(vv[2]), w0, 3, win, yacc, xi, code, acc0, acc1);
             }
         }
         if constexpr (K >= 4) {
@@ -339,11 +379,12 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
                 }
             }
         } else if (left > 0) {
-            const double2 v0 = ell_load_pair<NT>(vp);
-            double2 v1 = make_double2(0.0, 0.0);
+            const VP v0 = ell_load_pair<NT>(vp);
+            VP v1 = ell_zero_pair<VP>();
             if (left > 1) v1 = ell_load_pair<NT>(vp + 64);
             const uint32_t w0 = cp[0];
-            ell_triple_word<K, SYM>(v0, v1, v1, w0, left, win, yacc, xi, code, acc0, acc1);
+            ell_loads_issued<VP>();
+            ell_triple_word<K, SYM>(ell_pair(v0), ell_pair(v1), ell_pair(v1), w0, left, win, yacc, xi, code, acc0, acc1);
         }
     } else {
     // Four value pairs per step; symmetric pairs at K = 4 take two, which keeps them within 128 VGPRs.
@@ -351,20 +392,21 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
     constexpr int STEP = (SYM && K >= 4) ? 2 : 4;
     int k = 0;
     for (; k + STEP <= np; k += STEP) {
-        double2 vv[STEP];
+        VP vv[STEP];
         uint32_t cc[STEP];
 #pragma unroll
         for (int q = 0; q < STEP; ++q) vv[q] = ell_load_pair<NT>(v + (k + q) * 64);
 #pragma unroll
         for (int q = 0; q < STEP; ++q) cc[q] = c[(k + q) * G];
+        ell_loads_issued<VP>();
 #pragma unroll
         for (int q = 0; q < STEP; ++q) {
-            ell_entry<K, SYM>(vv[q].x, ELL_COL_LO(cc[q]), win, yacc, xi, code, acc0);
-            ell_entry<K, SYM>(vv[q].y, ELL_COL_HI(cc[q]), win, yacc, xi, code, acc1);
+            ell_entry<K, SYM>(ell_pair(vv[q]).x, ELL_COL_LO(cc[q]), win, yacc, xi, code, acc0);
+            ell_entry<K, SYM>(ell_pair(vv[q]).y, ELL_COL_HI(cc[q]), win, yacc, xi, code, acc1);
         }
     }
     for (; k < np; ++k) {
-        const double2 v0 = ell_load_pair<NT>(v + k * 64);
+        const double2 v0 = ell_load_pair_f64<NT>(v + k * 64);
         const uint32_t c0 = c[k * G];
         ell_entry<K, SYM>(v0.x, ELL_COL_LO(c0), win, yacc, xi, code, acc0);
         ell_entry<K, SYM>(v0.y, ELL_COL_HI(c0), win, yacc, xi, code, acc1);
@@ -388,7 +430,7 @@ __device__ __forceinline__ void ell_slab(const EllArgs& A, long long ldx, long l
 // SYM (symmetric pair storage): the segment is a whole partition; its rows' accumulators sit in LDS
 // right behind the K-wide x image, take the lanes' own sums and the scattered mirror products, and are
 // written to y in one coalesced sweep at the end.
-template <int THREADS, int K, bool DYN, bool INLINE_ER, bool SYM, bool STAMP>
+template <int THREADS, int K, bool DYN, bool INLINE_ER, bool SYM, bool STAMP, class VP = double2>
 __device__ __forceinline__ void ell_segment(const EllArgs& A, long long ldx, long long ldy, double* __restrict__ win,
                                             int* __restrict__ next_slab, int g, int lane, int wave, double& xy)
 {
@@ -455,9 +497,9 @@ __device__ __forceinline__ void ell_segment(const EllArgs& A, long long ldx, lon
     while (s < se) {
         const int slab = A.reverse ? se - 1 - (s - sb) : s;
         if (ell_slab_resident((A.keep_shape == ELL_KEEP_WALK_END ? s : slab) - sb, se - sb, A.keep1024, A.keep_shape))
-            ell_slab<K, INLINE_ER, SYM, false>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);
+            ell_slab<K, INLINE_ER, SYM, false, VP>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);
         else
-            ell_slab<K, INLINE_ER, SYM, true>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);   // value stream past the caches
+            ell_slab<K, INLINE_ER, SYM, true, VP>(A, ldx, ldy, win, yacc, slab, base, pe, lane, xy);   // value stream past the caches
         if (DYN) {
             int nx = 0;
             if (lane == 0) nx = atomicAdd(next_slab, 1);
@@ -486,7 +528,7 @@ __device__ __forceinline__ void ell_segment(const EllArgs& A, long long ldx, lon
 
 // The body of the window kernel: one workgroup per work item, its segments one after the other.  The LDS slab counter
 // sits right behind the K window images.
-template <int THREADS, int K, bool DYN, bool STAMP, bool INLINE_ER, bool SYM>
+template <int THREADS, int K, bool DYN, bool STAMP, bool INLINE_ER, bool SYM, class VP = double2>
 __device__ __forceinline__ void ell_items(const EllArgs& A, long long ldx, long long ldy)
 {
     static_assert(K == 1 || (DYN && !STAMP), "the k-vector window kernel is built with the LDS counter only, without stamps");
@@ -497,7 +539,7 @@ __device__ __forceinline__ void ell_items(const EllArgs& A, long long ldx, long 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double xy = 0.0;
-    for (int sg = it.x; sg < it.y; ++sg) ell_segment<THREADS, K, DYN, INLINE_ER, SYM, STAMP>(A, ldx, ldy, win, next_slab, sg, lane, wave, xy);
+    for (int sg = it.x; sg < it.y; ++sg) ell_segment<THREADS, K, DYN, INLINE_ER, SYM, STAMP, VP>(A, ldx, ldy, win, next_slab, sg, lane, wave, xy);
     if (K == 1 && A.xy_out != nullptr) {  // (wave-uniform: a kernel argument)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) xy += __shfl_xor(xy, off, 64);
@@ -533,9 +575,10 @@ __device__ __forceinline__ void ell_items(const EllArgs& A, long long ldx, long 
 // value) -> x[column] -> y.  Everything that does not depend on the products is therefore requested up
 // front (row number and the old y with the bounds), and a lane's column/value loads are issued four at
 // a time before the first gather of x (measured on R-MAT 2^22: DESIGN.md 3.2).
-template <int G, int THREADS, bool ASSIGN, int K>
+// VT: a value as the device holds it -- double, or float (cfg.val_f32), converted to fp64 where it is loaded.
+template <int G, int THREADS, bool ASSIGN, int K, class VT = double>
 __device__ __forceinline__ void er_bin(int lo, int hi, const int64_t* __restrict__ seg_ptr, const int* __restrict__ seg_row,
-                                       const int* __restrict__ col, const double* __restrict__ val, const double* __restrict__ x, long long ldx,
+                                       const int* __restrict__ col, const VT* __restrict__ val, const double* __restrict__ x, long long ldx,
                                        double* __restrict__ y, long long ldy)
 {
     constexpr int SEGS = THREADS / G;
@@ -603,18 +646,18 @@ __device__ __forceinline__ void er_bin(int lo, int hi, const int64_t* __restrict
 }
 
 // One workgroup per descriptor {seg_lo, seg_hi, lanes per segment}: a single pass of same-bin segments.
-template <int THREADS, bool ASSIGN, int K>
+template <int THREADS, bool ASSIGN, int K, class VT = double>
 __device__ __forceinline__ void er_blocks(const int4* __restrict__ blocks, const int64_t* __restrict__ seg_ptr, const int* __restrict__ seg_row,
-                                          const int* __restrict__ col, const double* __restrict__ val, const double* __restrict__ x, long long ldx,
+                                          const int* __restrict__ col, const VT* __restrict__ val, const double* __restrict__ x, long long ldx,
                                           double* __restrict__ y, long long ldy)
 {
     const int4 b = blocks[blockIdx.x];  // (the XCD map of the window kernel was tried here: no difference on R-MAT)
     if (b.z == 64)
-        er_bin<64, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+        er_bin<64, THREADS, ASSIGN, K, VT>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
     else if (b.z == 16)
-        er_bin<16, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+        er_bin<16, THREADS, ASSIGN, K, VT>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
     else
-        er_bin<4, THREADS, ASSIGN, K>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
+        er_bin<4, THREADS, ASSIGN, K, VT>(b.x, b.y, seg_ptr, seg_row, col, val, x, ldx, y, ldy);
 }
 
 // ------------------------------------------------------------------ host side (ehyb_hip.hip)

@@ -212,6 +212,30 @@ int ehyb_plan_device_cols(const ehyb_plan* plan, uint32_t* words_out, uint32_t* 
     return EHYB_OK;
 }
 
+// The value streams ehyb_plan_upload sends for this plan (cfg.val_f32)
+int ehyb_plan_device_value_bytes(const ehyb_plan* plan, int64_t* ell_bytes, int64_t* er_bytes)
+{
+    if (!plan) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_device_value_bytes: null plan");
+    const int64_t per = plan->cfg.val_f32 == 1 ? 4 : 8;
+    if (ell_bytes) *ell_bytes = per * (int64_t)plan->host.ell_val.size();
+    if (er_bytes) *er_bytes = per * (int64_t)plan->host.er_val.size();
+    return EHYB_OK;
+}
+
+int ehyb_plan_device_values_f32(const ehyb_plan* plan, int which, float* out, int64_t count)
+{
+    if (!plan || !out) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_device_values_f32: null argument");
+    if (plan->cfg.val_f32 != 1) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_plan_device_values_f32: the plan was built without cfg.val_f32 = 1");
+    if (which != EHYB_ARR_ELL_VAL && which != EHYB_ARR_ER_VAL) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_device_values_f32: array id %d is not a value stream", which);
+    const HostLayout& H = plan->host;
+    const double* src = which == EHYB_ARR_ELL_VAL ? H.ell_val.data() : H.er_val.data();
+    const int64_t n = (int64_t)(which == EHYB_ARR_ELL_VAL ? H.ell_val.size() : H.er_val.size());
+    if (count != n) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_plan_device_values_f32: room for %lld values, the stream holds %lld", (long long)count, (long long)n);
+    OmpScope omp(plan->cfg.host_threads);
+    device_values_f32(src, (size_t)n, out);
+    return EHYB_OK;
+}
+
 }  // extern "C"
 
 // defer_panel (ehyb_plan_create[_segs] only): a panel form that is certain is left to the device -- the plan comes back with

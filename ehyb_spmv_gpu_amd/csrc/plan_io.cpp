@@ -42,14 +42,16 @@ bool get(FILE* f, T& v)
 }
 // The configuration as the files hold it: the fields up to ell_nt.  Knobs added since (ell_keep: how a launch reads; ell_triples:
 // the form of the column words on the device; nothing of the host layout) stay out, so that files written before them remain
-// valid; a loaded plan has them at their defaults.
+// valid; a loaded plan has them at their defaults.  (val_f32, the form of the values on the device, travels in the spare word of
+// the scalars, which files written before it hold as 0 = off.)
 constexpr size_t kCfgFileBytes = offsetof(Config, ell_keep);
-static_assert(kCfgFileBytes + 2 * sizeof(int) == sizeof(Config), "fields added to Config go behind ell_keep and stay out of plan files");
+static_assert(kCfgFileBytes + 3 * sizeof(int) == sizeof(Config), "fields added to Config go behind ell_keep and stay out of plan files");
 bool put_cfg(FILE* f, const Config& c) { return fwrite(&c, kCfgFileBytes, 1, f) == 1; }
 bool get_cfg(FILE* f, Config& c)
 {
     c.ell_keep = 0;
     c.ell_triples = resolve_config(nullptr).ell_triples;
+    c.val_f32 = 0;
     return fread(&c, kCfgFileBytes, 1, f) == 1;
 }
 template <class T, class A>
@@ -84,7 +86,7 @@ struct Scalars {
     int32_t sym, yacc_doubles;
     int32_t er_panel, pb_panel_cols, pb_rows_max, direct;
     int64_t pb_partials, pb_bytes;
-    int32_t pb_assign, reserved;
+    int32_t pb_assign, val_f32;
 };
 
 // The panel residual's arrays must fit together as the two kernels index them.
@@ -162,7 +164,7 @@ int ehyb_plan_save(const ehyb_plan* plan, const int* reorder_list, uint64_t matr
     File f(fopen(path, "wb"));
     if (!f) EHYB_FAIL(EHYB_ERR_IO, "ehyb_plan_save: cannot create %s", path);
     Scalars s{H.n_cols, H.row_begin, H.row_end, H.n_parts, H.lds_doubles, H.inline_er ? 1 : 0, {0}, H.sym ? 1 : 0, H.yacc_doubles,
-              H.er_panel ? 1 : 0, H.pb_panel_cols, H.pb_rows_max, H.direct ? 1 : 0, H.pb_partials, H.pb_bytes, H.pb_assign ? 1 : 0, 0};
+              H.er_panel ? 1 : 0, H.pb_panel_cols, H.pb_rows_max, H.direct ? 1 : 0, H.pb_partials, H.pb_bytes, H.pb_assign ? 1 : 0, plan->cfg.val_f32 == 1 ? 1 : 0};
     memcpy(s.er_bins, H.er_bins, sizeof s.er_bins);
     std::vector<int32_t> perm;
     if (reorder_list) perm.assign(reorder_list, reorder_list + H.n_cols);
@@ -230,6 +232,7 @@ int ehyb_plan_load(const char* path, uint64_t expect_key, ehyb_plan** plan, int*
         panel_consistent(H);
     if (!consistent) EHYB_FAIL(EHYB_ERR_FORMAT, "ehyb_plan_load: %s holds inconsistent array sizes", path);
     if (H.er_panel) encode_panel_slots(&H);  // what pass 1 streams is derived from pb_col + pb_dst, not stored
+    P->cfg.val_f32 = s.val_f32 == 1 ? 1 : 0;
     P->cfg.value_map = 0;  // the slot maps are not part of the file: a loaded plan cannot be refilled
     if (reorder_list) {
         if (perm.empty()) EHYB_FAIL(EHYB_ERR_FORMAT, "ehyb_plan_load: %s holds no permutation", path);

@@ -380,6 +380,21 @@ class Plan:
             raise EhybError(b, "ehyb_plan_resident_bytes")
         return b
 
+    @property
+    def device_value_bytes(self):
+        """ehyb_plan_device_value_bytes -> (bytes of the window kernel's value stream, of the CSR residual's values) as the
+        device holds them: 8 per value, 4 with cfg.val_f32 = 1"""
+        e, r = C.c_int64(0), C.c_int64(0)
+        _check(self.lib.ehyb_plan_device_value_bytes(self.h, C.byref(e), C.byref(r)), "ehyb_plan_device_value_bytes")
+        return e.value, r.value
+
+    def device_values_f32(self, name):
+        """ehyb_plan_device_values_f32: the fp32 stream ehyb_plan_upload sends for "ell_val" or "er_val" (cfg.val_f32 = 1)"""
+        which, _ = ARRAYS[name]
+        out = np.empty(len(self.array(name)), dtype=np.float32)
+        _check(self.lib.ehyb_plan_device_values_f32(self.h, which, _ptr(out, C.c_float), len(out)), "ehyb_plan_device_values_f32")
+        return out
+
     def array(self, name):
         which, dtype = ARRAYS[name]
         p = C.c_void_p()
@@ -495,6 +510,20 @@ class Plan:
         if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
             raise EhybError(rc, "ehyb_pcg_multi")
         return dx.download().reshape(k, n), it, rel
+
+    def pcg_refine(self, inner_plan, b, x0=None, max_outer=10, inner_max_iter=1000, rtol=1e-12, inner_rtol=1e-6, inv_diag=None, stream=0):
+        """ehyb_pcg_refine: iterative refinement -- residuals and updates in fp64 on this plan, the corrections from ehyb_pcg on
+        inner_plan (normally the cfg.val_f32 plan of the same reordered matrix).  -> (x, outer steps, inner iterations in all,
+        relative residual ||b - A x|| / ||b|| on this plan); a run that stagnates returns normally: compare the residual with rtol."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        db = DeviceBuffer(self.n).upload(b)
+        dx = DeviceBuffer(self.n).upload(np.zeros(self.n) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64))
+        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
+        outer, inner, rel = C.c_int(0), C.c_int(0), C.c_double(0)
+        _check(self.lib.ehyb_pcg_refine(self.h, inner_plan.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), C.c_void_p(dx.ptr),
+                                        max_outer, inner_max_iter, rtol, inner_rtol, C.c_void_p(stream), C.byref(outer), C.byref(inner),
+                                        C.byref(rel)), "ehyb_pcg_refine")
+        return dx.download(), outer.value, inner.value, rel.value
 
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;

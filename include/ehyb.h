@@ -225,7 +225,14 @@ typedef struct ehyb_config {
                               of such a slab; ehyb_plan_upload transcodes, the host layout (EHYB_ARR_ELL_COL, EHYB_ARR_SLAB_META,
                               stats, plan files) is the same either way; 2 = the host's words as they are (A/B).  With every x
                               finite the result does not depend on it (ehyb_plan_device_cols)                       */
-    int32_t reserved[19];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
+    int32_t val_f32;       /* 1 = the DEVICE holds every value stream of the plan in fp32 (half the bytes of the window kernel's
+                              largest stream): each value is the fp64 value rounded to nearest-even by ehyb_plan_upload (out of
+                              range: +-inf; fp32 subnormals kept; NaN stays NaN; a pair a_ij == a_ji stays a pair), converted back
+                              to fp64 right after its load; x, y, the LDS window and every sum stay fp64.  The host layout
+                              (EHYB_ARR_ELL_VAL, EHYB_ARR_ER_VAL), stats, the slot maps and plan files are the same either way
+                              (ehyb_plan_device_values_f32).  Not for a residual in panel form, stamped launches, ehyb_plan_tune
+                              or ell_variant = 3 (EHYB_ERR_ARG); ehyb_spmm_max_k is 1.  0 = off (default): fp64 values      */
+    int32_t reserved[18];  /* zero; keeps sizeof(ehyb_config) = 260 bytes when knobs are added                  */
 } ehyb_config;
 
 void ehyb_config_default(ehyb_config* cfg);
@@ -456,6 +463,16 @@ enum {
  */
 int64_t ehyb_plan_device_col_words(const ehyb_plan* plan);
 int ehyb_plan_device_cols(const ehyb_plan* plan, uint32_t* words_out, uint32_t* meta_out);
+/*
+ * The value streams as ehyb_plan_upload sends them (cfg.val_f32); host arithmetic, valid on a plan that was never uploaded.
+ *   ehyb_plan_device_value_bytes  bytes of the window kernel's value stream (inline residual pairs included) and of the CSR
+ *                                 residual's values on the device: 8 per value, 4 with cfg.val_f32 = 1.  Either output may be NULL.
+ *   ehyb_plan_device_values_f32   (cfg.val_f32 = 1 only, else EHYB_ERR_STATE) the fp32 stream itself: which = EHYB_ARR_ELL_VAL
+ *                                 ([pair][lane][2] floats, the order and slab offsets of the host array) or EHYB_ARR_ER_VAL (one
+ *                                 float per entry); count must be the host array's length.
+ */
+int ehyb_plan_device_value_bytes(const ehyb_plan* plan, int64_t* ell_bytes, int64_t* er_bytes);
+int ehyb_plan_device_values_f32(const ehyb_plan* plan, int which, float* out, int64_t count);
 
 /* Read-only view of one array of the plan's host layout.  A plan whose panel form was built on the device (ehyb_plan_create,
  * cfg.symbolic) downloads the PB_* streams on the first call that asks for one; it has no CSR form of that residual
@@ -491,6 +508,12 @@ int ehyb_plan_host_array(const ehyb_plan* plan, int which, const void** ptr, int
  * set_values and the plan cache included; the refill compares a stored pair a_ij == a_ji as fp64 numbers, so two different
  * subnormals differ).  No row's arithmetic touches another row's: rows hundreds of binades apart do not disturb each other.  A
  * product is finite whenever every ordering of its partial sums is: no path meets an infinity before the end of a finite sum.
+ * fp32 values (cfg.val_f32 = 1).  The multiply is the fp64 multiply of the matrix whose values are float(a_ij): the same kernels'
+ * arithmetic on fp64 operands, per accumulator in the same order (inline residual, pairs in rising order, .x and .y halves apart,
+ * then their sum), so with plain storage and no split rows the result equals, bit for bit, that of an fp64 plan built from the
+ * rounded values; with symmetric pairs or split rows, up to the order of their atomic adds.  A value beyond the fp32 range is
+ * +-inf and its row comes out so; fp32 subnormal values (down to 2^-149) are kept and multiplied exactly.  A solver on such a
+ * plan solves the ROUNDED system: ehyb_pcg_refine gives the fp64 answer.
  */
 int ehyb_spmv(ehyb_plan* plan, const double* x_dev, double* y_dev, void* stream);
 /*
@@ -779,6 +802,25 @@ int ehyb_measure_read_bw(size_t bytes, int iters, double* gbps);
  */
 int ehyb_cg(ehyb_plan* plan, const double* b_dev, double* x_dev, int max_iter, double rtol,
             int check_every, void* stream, int* iters_done, double* rel_residual);
+/*
+ * Iterative refinement: fp64 answers from a plan that stores fp32 values (cfg.val_f32).  Per outer step: q = A x on `plan` (its
+ * values fp64; walked first to last), r = b - q with ||r||^2 and ||b||^2 (one kernel; per-workgroup partials added in the fixed
+ * order of the solvers); stop if ||r|| <= rtol ||b||, or if ||r|| did not at least halve since the previous step (stagnation:
+ * EHYB_OK, the caller reads rel_residual); else d = 0, ehyb_pcg(inner_plan, inv_diag, r, d, inner_max_iter, inner_rtol) on the
+ * same stream, x += d (one kernel).  At most max_outer corrections.  inner_plan is normally the val_f32 plan of the same reordered
+ * matrix; any uploaded plan over all rows with the same number of rows is taken (an fp64 plan: restarted CG).  x_dev: the initial
+ * guess in, the solution out.  outer_done: corrections applied; inner_iters_total: CG iterations over all of them; rel_residual:
+ * the last ||b - A x|| / ||b|| computed with `plan`.  Stream and NULL outputs as for ehyb_pcg.  A breakdown of an inner solve is
+ * returned as ehyb_pcg returns it.
+ * ehyb_refine_residual_step / ehyb_refine_axpy_step launch the two vector kernels one at a time, as the ehyb_cg_*_step calls do:
+ * r = b - q with the partials of r.r in s[0 .. slot_doubles) and of b.b in s[slot_doubles .. 2 slot_doubles) (slot_doubles of
+ * ehyb_cg_layout; slot_doubles / 2 workgroups write, the rest stays as it is), and x += d.
+ */
+int ehyb_pcg_refine(ehyb_plan* plan, ehyb_plan* inner_plan, const double* inv_diag_dev, const double* b_dev, double* x_dev,
+                    int max_outer, int inner_max_iter, double rtol, double inner_rtol, void* stream, int* outer_done,
+                    int* inner_iters_total, double* rel_residual);
+int ehyb_refine_residual_step(int n, const double* b_dev, const double* q_dev, double* r_dev, double* s_dev, void* stream);
+int ehyb_refine_axpy_step(int n, const double* d_dev, double* x_dev, void* stream);
 /* The same with the diagonal (Jacobi) preconditioner -- the PRECOND switch of the reference's cb_s
  * (spmv.h:7-15): inv_diag_dev[i] = 1 / a_ii in the permuted numbering (matrixCOO.diag, permuted
  * like x); NULL = ehyb_cg.  z = M^-1 r is recomputed on the fly, no extra vector is stored. */
