@@ -23,11 +23,12 @@
 //
 // k right-hand sides (ehyb_bicgstab_multi) are k such solves that share the two multiplies (ehyb_spmm): the vector kernels are
 // templated on K columns per launch, every column with its own slots, status word and counter, and K = 1 is the one-vector solve.
+// The host side is written once too: bicgstab_solve drives k columns, ehyb_bicgstab is its own argument check and that driver at
+// k = 1, ehyb_bicgstab_multi the k and leading-dimension checks and the driver.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "ehyb_internal.h"
@@ -44,11 +45,6 @@ enum { B_BB = 0, B_RV = 1, B_SS = 2, B_TS = 3, B_TT = 4, B_RHO0 = 5, B_RR = 6, B
 enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
 enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
 
-template <typename T>
-__device__ __forceinline__ T* slot(T* s, int col, int which)
-{
-    return s + ((size_t)col * B_COUNT + which) * kMaxGrid;
-}
 __device__ __forceinline__ bool usable_divisor(double d) { return d != 0.0 && isfinite(d); }
 // a decision every thread of the workgroup takes alike (it comes from the status words or from sums in the fixed order), as a
 // scalar: the branches on it are not divergent
@@ -80,14 +76,13 @@ __device__ __forceinline__ void set_status(int* __restrict__ flags, int col, int
 }
 
 // ------------------------------------------------------------------ the vector kernels, K columns per launch
-// Columns c0 .. c0 + K - 1 of vectors with leading dimension n (B: ldb, X: ldx); K <= 4 per launch, ceil(k / 4) launches for k
-// columns, K = 1 for the one-vector solve and the ehyb_bicgstab_*_step building blocks.  Every kernel walks the indices with the
+// Columns c0 .. c0 + K - 1 of vectors with leading dimension n (B: ldb, X: ldx); K <= 4 per launch (kMultiMaxK, for_each_group
+// of solve_loop.h), K = 1 for the one-vector solve and the ehyb_bicgstab_*_step building blocks.  Every kernel walks the indices with the
 // grid and the per-thread order of the one-vector kernel and does the same arithmetic in the same order per column, so a
 // column's partials and scalars are the one-vector solve's bits.  One thread serves the K columns at one index: one inv_diag
 // load for all of them, and the loads of every column are issued before the first store.  U grid strides per trip: a thread
 // accumulates in rising index order whatever U is, so U is free per K and is chosen to keep the loads of a trip in registers.
 // A column whose status is set is skipped: its vectors and partials stay as they are.
-constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
 
 // r = b - q (q = A x0), r^ = r, p^ = M^-1 r; partials of rho = r^.r, r.r, b.b.  Takes no flags: they are zero at the start.
 template <int K>
@@ -116,9 +111,9 @@ __global__ __launch_bounds__(kThreads) void bicg_init_kernel(int n, const double
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < K; ++c) {
-            slot(s, c0 + c, B_RHO0)[blockIdx.x] = sums[c];
-            slot(s, c0 + c, B_RR)[blockIdx.x] = sums[c];
-            slot(s, c0 + c, B_BB)[blockIdx.x] = sums[K + c];
+            slot<B_COUNT>(s, c0 + c, B_RHO0)[blockIdx.x] = sums[c];
+            slot<B_COUNT>(s, c0 + c, B_RR)[blockIdx.x] = sums[c];
+            slot<B_COUNT>(s, c0 + c, B_BB)[blockIdx.x] = sums[K + c];
         }
     }
 }
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void bicg_dot_kernel(int n, const double*
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < K; ++c)
-            if (on[c]) slot(s, c0 + c, B_RV)[blockIdx.x] = acc[c];
+            if (on[c]) slot<B_COUNT>(s, c0 + c, B_RV)[blockIdx.x] = acc[c];
     }
 }
 
@@ -186,8 +181,8 @@ __global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* _
     double sums[2 * K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-        sums[c] = on[c] ? partials_of(slot(s, c0 + c, B_RHO0 + 2 * cur)) : 0.0;
-        sums[K + c] = on[c] ? partials_of(slot(s, c0 + c, B_RV)) : 0.0;
+        sums[c] = on[c] ? partials_of(slot<B_COUNT>(s, c0 + c, B_RHO0 + 2 * cur)) : 0.0;
+        sums[K + c] = on[c] ? partials_of(slot<B_COUNT>(s, c0 + c, B_RV)) : 0.0;
     }
     block_sum_n(sums);
     double alpha[K], ss[K];
@@ -256,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* _
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < K; ++c)
-            if (on[c]) slot(s, c0 + c, B_SS)[blockIdx.x] = ss[c];
+            if (on[c]) slot<B_COUNT>(s, c0 + c, B_SS)[blockIdx.x] = ss[c];
     }
 }
 
@@ -314,8 +309,8 @@ __global__ __launch_bounds__(kThreads) void bicg_dot2_kernel(int n, const double
 #pragma unroll
         for (int c = 0; c < K; ++c) {
             if (!on[c]) continue;
-            slot(s, c0 + c, B_TS)[blockIdx.x] = acc[c];
-            slot(s, c0 + c, B_TT)[blockIdx.x] = acc[K + c];
+            slot<B_COUNT>(s, c0 + c, B_TS)[blockIdx.x] = acc[c];
+            slot<B_COUNT>(s, c0 + c, B_TT)[blockIdx.x] = acc[K + c];
         }
     }
 }
@@ -337,7 +332,7 @@ __global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const doub
 #pragma unroll
     for (int c = 0; c < K; ++c) {
 #pragma unroll
-        for (int w = 0; w < 6; ++w) sums[w * K + c] = on[c] ? partials_of(slot(s, c0 + c, slots[w] + (w == 0 ? 2 * cur : 0))) : 0.0;
+        for (int w = 0; w < 6; ++w) sums[w * K + c] = on[c] ? partials_of(slot<B_COUNT>(s, c0 + c, slots[w] + (w == 0 ? 2 * cur : 0))) : 0.0;
     }
     block_sum_n(sums);
     const double* p[K];
@@ -437,8 +432,8 @@ __global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const doub
 #pragma unroll
         for (int c = 0; c < K; ++c) {
             if (!half[c] && !full[c]) continue;
-            if (full[c]) slot(s, c0 + c, B_RHO0 + 2 * (cur ^ 1))[blockIdx.x] = out[c];
-            slot(s, c0 + c, B_RR)[blockIdx.x] = out[K + c];
+            if (full[c]) slot<B_COUNT>(s, c0 + c, B_RHO0 + 2 * (cur ^ 1))[blockIdx.x] = out[c];
+            slot<B_COUNT>(s, c0 + c, B_RR)[blockIdx.x] = out[K + c];
             if (blockIdx.x == 0) flags[(c0 + c) * F_COUNT + F_ITERS] += 1;
         }
     }
@@ -460,7 +455,7 @@ __global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const d
     for (int c = 0; c < K; ++c) {
 #pragma unroll
         for (int w = 0; w < 8; ++w)
-            sums[w * K + c] = on[c] ? partials_of(slot(s, c0 + c, slots[w] + (w == 3 ? 2 * cur : w == 4 ? 2 * (cur ^ 1) : 0))) : 0.0;
+            sums[w * K + c] = on[c] ? partials_of(slot<B_COUNT>(s, c0 + c, slots[w] + (w == 3 ? 2 * cur : w == 4 ? 2 * (cur ^ 1) : 0))) : 0.0;
     }
     block_sum_n(sums);
     const double* r[K];
@@ -556,90 +551,15 @@ void launch_after_t(int grid, hipStream_t st, int n, double* p, const double* sh
                        c0, cur, thr);
 }
 
-// f(K as an integral constant, c0) for k columns in groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
-template <typename F>
-void for_each_group(int k, F&& f)
+// The one driver: k solves that share v = A p^ and t = A s^ (ehyb_spmm with explicit walks; its pass of width 1 is ehyb_spmv_walk,
+// so k = 1 launches the one-vector sequence: the multiplies, one <1> launch per vector kernel, and the one-vector workspace).  Every
+// column has its own slots, status word and counter and is decided on the device; the host reads all of them at a check point and
+// goes on while any column is running.  A column that has nothing to do at the start, or a non-finite start, gets its status
+// planted before the first burst -- where some column does start and some does not, so never at k = 1.  The entry points have
+// made their checks (solve_loop.h); who: the entry point, name_column: whether the breakdown text says which column.
+int bicgstab_solve(const char* who, bool name_column, ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X,
+                   int64_t ldx, int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
 {
-    const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
-    for (int g = 0, c0 = 0; g < groups; ++g) {
-        const int w = k / groups + (g < k % groups ? 1 : 0);
-        switch (w) {
-        case 1: f(std::integral_constant<int, 1>{}, c0); break;
-        case 2: f(std::integral_constant<int, 2>{}, c0); break;
-        case 3: f(std::integral_constant<int, 3>{}, c0); break;
-        default: f(std::integral_constant<int, 4>{}, c0); break;
-        }
-        c0 += w;
-    }
-}
-
-}  // namespace
-
-extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
-                             int check_every, void* stream, int* iters_done, double* rel_residual)
-{
-    int rc = solve_prologue("ehyb_bicgstab", P, b && x, max_iter, rtol);
-    if (rc != EHYB_OK) return rc;
-    const int n = P->host.n_cols;
-    SolveLoop L(n, check_every);
-    const int grid = L.grid;
-    double *r, *rh, *p, *v, *sv, *sh, *t, *s;
-    HIP_TRY(L.begin(stream, {&r, &rh, &p, &v, &sv, &sh, &t}, n, &s, B_COUNT, 1));  // the flags in the double behind the slots
-    int* flags = (int*)(s + (size_t)B_COUNT * kMaxGrid);
-    const hipStream_t st = L.st;
-    const double thr = rtol * rtol;
-
-    HIP_TRY(hipMemsetAsync(flags, 0, F_COUNT * sizeof(int), st));
-    // v = A x0, walked last to first so that the first iteration's first-to-last walk starts on what it left in the cache
-    if ((rc = ehyb_spmv_walk(P, x, v, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return rc;
-    hipLaunchKernelGGL(bicg_init_kernel<1>, dim3(grid), dim3(kThreads), 0, st, n, b, (long long)n, v, dinv, r, rh, p, s, 0);
-    HIP_TRY(L.read());
-    const double bb0 = L.sum(B_BB), bb = bb0 > 0 ? bb0 : 1.0;
-    double rr = L.sum(B_RR);
-    int status = !std::isfinite(bb0) || !std::isfinite(rr) ? ST_BREAKDOWN : rr <= thr * bb ? ST_CONVERGED : ST_RUNNING;
-    int done = 0, it = 0;
-
-    // An even and an odd iteration -- four multiplies walking first to last, last to first, first to last, last to first --
-    // are one graph; the plain launches use the same walks.
-    rc = L.run(
-        P, max_iter, it, [&] { return status == ST_RUNNING; },
-        [&](int cur, bool) -> int {
-            int e = ehyb_spmv_walk(P, p, v, st, EHYB_WALK_FIRST_TO_LAST);  // v = A p^
-            if (e != EHYB_OK) return e;
-            launch_after_v<1>(grid, st, n, r, rh, v, dinv, sv, sh, s, flags, 0, cur);
-            if ((e = ehyb_spmv_walk(P, sh, t, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // t = A s^
-            launch_after_t<1>(grid, st, n, p, sh, sv, t, rh, v, dinv, x, n, r, s, flags, 0, cur, thr);
-            return EHYB_OK;
-        },
-        [&](int) -> int {
-            int f[F_COUNT];
-            std::memcpy(f, &L.h[(size_t)B_COUNT * kMaxGrid], sizeof f);
-            status = f[F_STATUS];
-            done = f[F_ITERS];
-            rr = L.sum(B_RR);
-            return EHYB_OK;
-        });
-    if (rc != EHYB_OK) return rc;
-    if (iters_done) *iters_done = done;
-    if (rel_residual) *rel_residual = std::sqrt(rr / bb);
-    if (status == ST_BREAKDOWN)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab: breakdown after %d iterations (a zero or non-finite rho, r^.v, t.t or omega)", done);
-    return EHYB_OK;
-}
-
-// ------------------------------------------------------------------ k right-hand sides, two multiplies (ehyb_bicgstab_multi)
-// k solves as above that share v = A p^ and t = A s^ (ehyb_spmm, the same explicit walks).  Every column has its own slots,
-// status word and counter and is decided on the device like the one-vector solve; the host reads all of them at a check point
-// and goes on while any column is running.  A column that has nothing to do at the start, or a non-finite start, gets its
-// status planted before the first burst.
-extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
-                                   int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
-{
-    if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab_multi: k = %d right-hand sides (at least 1)", k);
-    if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bicgstab_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, P->host.n_cols);
-    int rc = solve_prologue("ehyb_bicgstab_multi", P, B && X, max_iter, rtol);
-    if (rc != EHYB_OK) return rc;
     const int n = P->host.n_cols;
     SolveLoop L(n, check_every);
     const int grid = L.grid;
@@ -652,7 +572,9 @@ extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const doubl
     const double thr = rtol * rtol;
 
     HIP_TRY(hipMemsetAsync(flags, 0, (size_t)k * F_COUNT * sizeof(int), st));
-    if ((rc = ehyb_spmm(P, X, ldx, v, n, k, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return rc;  // V = A X0
+    // V = A X0, walked last to first so that the first iteration's first-to-last walk starts on what it left in the cache
+    int rc = ehyb_spmm(P, X, ldx, v, n, k, st, EHYB_WALK_LAST_TO_FIRST);
+    if (rc != EHYB_OK) return rc;
     for_each_group(k, [&](auto K, int c0) {
         hipLaunchKernelGGL(bicg_init_kernel<decltype(K)::value>, dim3(grid), dim3(kThreads), 0, st, n, B, (long long)ldb, v, dinv, r, rh,
                            p, s, c0);
@@ -674,6 +596,8 @@ extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const doubl
         HIP_TRY(hipStreamSynchronize(st));
     }
 
+    // An even and an odd iteration -- four multiplies walking first to last, last to first, first to last, last to first --
+    // are one graph; the plain launches use the same walks.
     int it = 0;
     rc = L.run(
         P, max_iter, it, [&] { return n_running > 0; },
@@ -703,11 +627,32 @@ extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const doubl
         if (rel_residual) rel_residual[j] = std::sqrt(rr[j] / bb[j]);
         if (f[j * F_COUNT + F_STATUS] == ST_BREAKDOWN) broke = j;
     }
-    if (broke >= 0)
-        EHYB_FAIL(EHYB_ERR_ARG,
-                  "ehyb_bicgstab_multi: breakdown in column %d after %d iterations (a zero or non-finite rho, r^.v, t.t or omega)", broke,
-                  f[broke * F_COUNT + F_ITERS]);
-    return EHYB_OK;
+    if (broke < 0) return EHYB_OK;
+    const int done = f[broke * F_COUNT + F_ITERS];
+    const char* what = "a zero or non-finite rho, r^.v, t.t or omega";
+    if (name_column) EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown in column %d after %d iterations (%s)", who, broke, done, what);
+    EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown after %d iterations (%s)", who, done, what);
+}
+
+}  // namespace
+
+extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
+                             int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    const int rc = solve_prologue("ehyb_bicgstab", P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    const int n = P->host.n_cols;
+    return bicgstab_solve("ehyb_bicgstab", false, P, dinv, b, n, x, n, 1, max_iter, rtol, check_every, stream, iters_done, rel_residual);
+}
+
+// k right-hand sides, two multiplies per iteration
+extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                                   int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    const int rc = multi_prologue("ehyb_bicgstab_multi", P, B && X, ldb, ldx, k, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    return bicgstab_solve("ehyb_bicgstab_multi", true, P, dinv, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done,
+                          rel_residual);
 }
 
 // ------------------------------------------------------------------ building blocks for a caller that owns the loop
@@ -739,14 +684,6 @@ extern "C" int ehyb_bicgstab_layout(ehyb_bicgstab_slots* out)
 namespace {
 
 constexpr int kStepGrid = kMaxGrid / 2;
-
-inline int check_step(const char* who, int n, std::initializer_list<const void*> pointers)
-{
-    bool ok = n >= 0;
-    for (const void* a : pointers) ok = ok && a;
-    if (!ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: bad arguments", who);
-    return EHYB_OK;
-}
 
 inline int* flags_of(double* s) { return (int*)(s + (size_t)B_COUNT * kMaxGrid); }
 

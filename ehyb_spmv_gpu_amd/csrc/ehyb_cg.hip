@@ -67,13 +67,6 @@ __global__ __launch_bounds__(kThreads) void cg_init_kernel(int n, const double* 
 // multiply is (plain storage).  One thread serves the K columns at one index: the inv_diag load is shared and K times the loads
 // are in flight.  A column whose active flag is 0 (converged or broken down) is skipped: its x, r, p and partials stay as they
 // are.  A one-vector launch passes no flags (active = null: its column is live; K = 1 only, the wider kernels' code stays as it is).
-constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
-
-template <typename T>
-__device__ __forceinline__ T* slot(T* s, int col, int which)
-{
-    return s + ((size_t)col * A_COUNT + which) * kMaxGrid;
-}
 
 // columns c0 .. c0 + K - 1: P, Q, R with leading dimension n, X with ldx.  pq = p . q
 template <int K>
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void cg_multi_dot_kernel(int n, const dou
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < K; ++c)
-            if (on[c]) slot(s, c0 + c, A_PQ)[blockIdx.x] = acc[c];
+            if (on[c]) slot<A_COUNT>(s, c0 + c, A_PQ)[blockIdx.x] = acc[c];
     }
 }
 
@@ -115,8 +108,8 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
 #pragma unroll
     for (int c = 0; c < K; ++c) {
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
-        sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
-        sums[K + c] = partials_of(slot(s, c0 + c, A_PQ));
+        sums[c] = partials_of(slot<A_COUNT>(s, c0 + c, A_RZ0 + 2 * cur));
+        sums[K + c] = partials_of(slot<A_COUNT>(s, c0 + c, A_PQ));
     }
     block_sum_n(sums);
     double rz[K], rr[K];
@@ -192,8 +185,8 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
 #pragma unroll
         for (int c = 0; c < K; ++c) {
             if (!on[c]) continue;
-            slot(s, c0 + c, A_RZ0 + 2 * (cur ^ 1))[blockIdx.x] = sums[c];
-            slot(s, c0 + c, A_RR)[blockIdx.x] = sums[K + c];
+            slot<A_COUNT>(s, c0 + c, A_RZ0 + 2 * (cur ^ 1))[blockIdx.x] = sums[c];
+            slot<A_COUNT>(s, c0 + c, A_RR)[blockIdx.x] = sums[K + c];
         }
     }
 }
@@ -209,8 +202,8 @@ __global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, con
 #pragma unroll
     for (int c = 0; c < K; ++c) {
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
-        sums[c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * (cur ^ 1)));
-        sums[K + c] = partials_of(slot(s, c0 + c, A_RZ0 + 2 * cur));
+        sums[c] = partials_of(slot<A_COUNT>(s, c0 + c, A_RZ0 + 2 * (cur ^ 1)));
+        sums[K + c] = partials_of(slot<A_COUNT>(s, c0 + c, A_RZ0 + 2 * cur));
     }
     block_sum_n(sums);
     const double* r[K];
@@ -269,6 +262,9 @@ extern "C" int ehyb_cg(ehyb_plan* P, const double* b, double* x, int max_iter, d
     return ehyb_pcg(P, nullptr, b, x, max_iter, rtol, check_every, stream, iters_done, rel_residual);
 }
 
+// A driver of its own, not ehyb_pcg_multi at k = 1: it fuses p . q into the multiply (spmv_xy) and issues its multiplies with the
+// plan's own alternation, where a k = 1 ehyb_pcg_multi states explicit walks in its captured graph -- which ell_walk honours
+// even on a plan that does not alternate.  Folding the two would change what a one-vector solve launches.
 extern "C" int ehyb_pcg(ehyb_plan* P, const double* dinv, const double* b, double* x, int max_iter, double rtol,
                         int check_every, void* stream, int* iters_done, double* rel_residual)
 {
@@ -325,10 +321,7 @@ extern "C" int ehyb_cg_multi(ehyb_plan* P, const double* B, int64_t ldb, double*
 extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
                               int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
 {
-    if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: k = %d right-hand sides (at least 1)", k);
-    if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_pcg_multi: ldb %lld, ldx %lld < %d rows", (long long)ldb, (long long)ldx, P->host.n_cols);
-    int rc = solve_prologue("ehyb_pcg_multi", P, B && X, max_iter, rtol);
+    int rc = multi_prologue("ehyb_pcg_multi", P, B && X, ldb, ldx, k, max_iter, rtol);
     if (rc != EHYB_OK) return rc;
     const int n = P->host.n_cols;
     SolveLoop L(n, check_every);
@@ -355,8 +348,6 @@ extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B,
     }
     HIP_TRY(hipMemcpyAsync(active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
 
-    // column groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
-    const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
     int it = 0;
     rc = L.run(
         P, max_iter, it, [&] { return n_live > 0; },
@@ -366,16 +357,9 @@ extern "C" int ehyb_pcg_multi(ehyb_plan* P, const double* dinv, const double* B,
             const int walk = !captured ? EHYB_WALK_AUTO : cur ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST;
             const int e = ehyb_spmm(P, Pd, n, Q, n, k, st, walk);
             if (e != EHYB_OK) return e;
-            for (int g = 0, c0 = 0; g < groups; ++g) {
-                const int w = k / groups + (g < k % groups ? 1 : 0);
-                switch (w) {
-                case 1: launch_vector_kernels<1>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
-                case 2: launch_vector_kernels<2>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
-                case 3: launch_vector_kernels<3>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
-                default: launch_vector_kernels<4>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur); break;
-                }
-                c0 += w;
-            }
+            for_each_group(k, [&](auto K, int c0) {
+                launch_vector_kernels<decltype(K)::value>(grid, st, n, Pd, Q, dinv, X, ldx, R, s, active, c0, cur);
+            });
             return EHYB_OK;
         },
         [&](int cur) -> int {
@@ -426,18 +410,12 @@ extern "C" int ehyb_cg_layout(int* slots, int* slot_doubles, int* slot_bb, int* 
     return EHYB_OK;
 }
 
-static int check_vec(int n, const void* a, const void* b, const void* c, const char* who)
-{
-    if (n < 0 || !a || !b || !c) EHYB_FAIL(EHYB_ERR_ARG, "%s: bad arguments", who);
-    return EHYB_OK;
-}
-
 // r = b - q, p = z = M^-1 r; partials of r.z (slot rz0), r.r, b.b
 extern "C" int ehyb_cg_init_step(int n, const double* b, const double* q, const double* dinv, double* r, double* p, double* s,
                                  void* stream)
 {
-    int rc = check_vec(n, b, q, s, "ehyb_cg_init_step");
-    if (rc != EHYB_OK || !r || !p) return rc != EHYB_OK ? rc : EHYB_ERR_ARG;
+    int rc = check_step("ehyb_cg_init_step", n, {b, q, r, p, s});
+    if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(cg_init_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, b, q, dinv, r, p, s);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
@@ -445,7 +423,7 @@ extern "C" int ehyb_cg_init_step(int n, const double* b, const double* q, const 
 // partials of p.q (slot pq)
 extern "C" int ehyb_cg_dot_step(int n, const double* p, const double* q, double* s, void* stream)
 {
-    int rc = check_vec(n, p, q, s, "ehyb_cg_dot_step");
+    int rc = check_step("ehyb_cg_dot_step", n, {p, q, s});
     if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(cg_multi_dot_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, s, nullptr, 0);
     HIP_TRY(hipGetLastError());
@@ -455,8 +433,8 @@ extern "C" int ehyb_cg_dot_step(int n, const double* p, const double* q, double*
 extern "C" int ehyb_cg_update_step(int n, const double* p, const double* q, const double* dinv, double* x, double* r, double* s,
                                    int cur, void* stream)
 {
-    int rc = check_vec(n, p, q, s, "ehyb_cg_update_step");
-    if (rc != EHYB_OK || !x || !r) return rc != EHYB_OK ? rc : EHYB_ERR_ARG;
+    int rc = check_step("ehyb_cg_update_step", n, {p, q, x, r, s});
+    if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(cg_multi_update_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, p, q, dinv, x, n, r, s,
                        nullptr, 0, cur & 1);
     HIP_TRY(hipGetLastError());
@@ -465,7 +443,7 @@ extern "C" int ehyb_cg_update_step(int n, const double* p, const double* q, cons
 // beta = rz[cur ^ 1] / rz[cur]; p = z + beta p
 extern "C" int ehyb_cg_direction_step(int n, const double* r, const double* dinv, double* p, const double* s, int cur, void* stream)
 {
-    int rc = check_vec(n, r, p, s, "ehyb_cg_direction_step");
+    int rc = check_step("ehyb_cg_direction_step", n, {r, p, s});
     if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(cg_multi_direction_kernel<1>, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, r, dinv, p, s, nullptr,
                        0, cur & 1);

@@ -102,7 +102,8 @@ extern "C" int ehyb_pcg_refine(ehyb_plan* P, ehyb_plan* inner, const double* din
 // ------------------------------------------------------------------ the two kernels one at a time (as ehyb_cg_*_step)
 extern "C" int ehyb_refine_residual_step(int n, const double* b, const double* q, double* r, double* s, void* stream)
 {
-    if (n < 0 || !b || !q || !r || !s) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_refine_residual_step: bad arguments");
+    int rc = check_step("ehyb_refine_residual_step", n, {b, q, r, s});
+    if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(refine_residual_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, b, q, r, s);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
@@ -110,7 +111,8 @@ extern "C" int ehyb_refine_residual_step(int n, const double* b, const double* q
 
 extern "C" int ehyb_refine_axpy_step(int n, const double* d, double* x, void* stream)
 {
-    if (n < 0 || !d || !x) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_refine_axpy_step: bad arguments");
+    int rc = check_step("ehyb_refine_axpy_step", n, {d, x});
+    if (rc != EHYB_OK) return rc;
     hipLaunchKernelGGL(refine_axpy_kernel, dim3(kMaxGrid / 2), dim3(kThreads), 0, (hipStream_t)stream, n, d, x);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;

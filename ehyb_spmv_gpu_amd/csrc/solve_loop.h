@@ -1,11 +1,13 @@
-// The host side of the device-resident solvers (ehyb_cg.hip, ehyb_bicgstab.hip): the checks a solve starts with, what it owns,
-// and the loop that issues its iterations in bursts between check points.  A solver keeps its recurrences (one iteration of
-// parity cur), its slot layout, and what it reads and decides at a check point.
+// The host side of the device-resident solvers (ehyb_cg.hip, ehyb_bicgstab.hip, ehyb_refine.hip): the checks a solve or a
+// *_step building block starts with, the split of k columns into launches, what a solve owns, and the loop that issues its
+// iterations in bursts between check points.  A solver keeps its recurrences (one iteration of parity cur), its slot layout,
+// and what it reads and decides at a check point.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "ehyb_internal.h"
@@ -23,6 +25,43 @@ inline int solve_prologue(const char* who, const ehyb_plan* P, bool args_ok, int
     if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "%s: needs a plan over all rows", who);
     if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: plan not uploaded (no CPU fallback exists)", who);
     return EHYB_OK;
+}
+
+// a k-column solve: k first, then the leading dimensions, then solve_prologue
+inline int multi_prologue(const char* who, const ehyb_plan* P, bool args_ok, int64_t ldb, int64_t ldx, int k, int max_iter, double rtol)
+{
+    if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "%s: k = %d right-hand sides (at least 1)", who, k);
+    if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: ldb %lld, ldx %lld < %d rows", who, (long long)ldb, (long long)ldx, P->host.n_cols);
+    return solve_prologue(who, P, args_ok, max_iter, rtol);
+}
+
+// a *_step building block: n and every pointer it requires (an optional one, dinv, is not listed)
+inline int check_step(const char* who, int n, std::initializer_list<const void*> required)
+{
+    bool ok = n >= 0;
+    for (const void* a : required) ok = ok && a;
+    if (!ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: bad arguments", who);
+    return EHYB_OK;
+}
+
+constexpr int kMultiMaxK = 4;  // columns per vector-kernel launch
+
+// f(K as an integral constant, c0) for k columns in groups of at most kMultiMaxK, as even as they come (k = 5: 3 + 2)
+template <typename F>
+void for_each_group(int k, F&& f)
+{
+    const int groups = (k + kMultiMaxK - 1) / kMultiMaxK;
+    for (int g = 0, c0 = 0; g < groups; ++g) {
+        const int w = k / groups + (g < k % groups ? 1 : 0);
+        switch (w) {
+        case 1: f(std::integral_constant<int, 1>{}, c0); break;
+        case 2: f(std::integral_constant<int, 2>{}, c0); break;
+        case 3: f(std::integral_constant<int, 3>{}, c0); break;
+        default: f(std::integral_constant<int, 4>{}, c0); break;
+        }
+        c0 += w;
+    }
 }
 
 // what a solve owns, released on every way out, and the loop that drives it

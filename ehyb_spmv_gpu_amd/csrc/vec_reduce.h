@@ -67,4 +67,11 @@ __device__ __forceinline__ double partials_of(const double* __restrict__ part)
     return v;
 }
 
+// slot `which` of column col, where a column has COUNT slots (the solver's A_COUNT or B_COUNT) of kMaxGrid partials
+template <int COUNT, typename T>
+__device__ __forceinline__ T* slot(T* s, int col, int which)
+{
+    return s + ((size_t)col * COUNT + which) * kMaxGrid;
+}
+
 }  // namespace

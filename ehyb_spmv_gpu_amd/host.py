@@ -481,64 +481,54 @@ class Plan:
                                         C.byref(r) if per_kernel else None), "ehyb_spmv_bench")
         return {"ms_total": t.value, "ms_ell_avg": e.value, "ms_er_avg": r.value}
 
+    def _solve(self, name, B, X0, inv_diag, scalars, stream=0, allow_breakdown=False, multi=False, inner=None):
+        """One call of the solver `name`: B, X0 (zeros if None) and the optional inv_diag staged on the device; the arguments in
+        the one-vector shape or (multi) the (ldb, ldx, k) one, `scalars` between the vectors and the stream; `inner`: the second
+        plan of ehyb_pcg_refine, which also reports two integer counters instead of one.  A failure raises EhybError, unless
+        allow_breakdown and the error text says breakdown.  -> (X, counters ...): scalars from a one-vector call, (k,) arrays
+        and X (k, n) from a multi one."""
+        n, k = self.n, 1
+        B = np.ascontiguousarray(np.atleast_2d(B) if multi else B, dtype=np.float64)
+        if multi:
+            k, nb = B.shape
+            assert nb == n, (nb, n)
+            X0 = None if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).reshape(k, n)
+        db = DeviceBuffer(k * n).upload(B.ravel())
+        dx = DeviceBuffer(k * n).upload(np.zeros(k * n) if X0 is None else np.ravel(X0))
+        dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
+        counts, rel = np.zeros((1 if inner is None else 2, k), dtype=np.int32), np.zeros(k, dtype=np.float64)
+        vectors = (C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k) if multi else (C.c_void_p(db.ptr), C.c_void_p(dx.ptr))
+        rc = getattr(self.lib, name)(self.h, *(() if inner is None else (inner.h,)), C.c_void_p(dd.ptr) if dd else None, *vectors,
+                                     *scalars, C.c_void_p(stream), *(_ptr(c, C.c_int) for c in counts), _ptr(rel, C.c_double))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, name)
+        if multi:
+            return dx.download().reshape(k, n), counts[0], rel
+        return (dx.download(), *(int(c[0]) for c in counts), float(rel[0]))
+
     def cg(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None):
         """ehyb_cg / ehyb_pcg: (Jacobi-preconditioned if inv_diag is given) conjugate gradients on the
         device; b, x, inv_diag in the permuted numbering.  -> (x, iterations, relative residual)"""
-        b = np.ascontiguousarray(b, dtype=np.float64)
-        db, dx = DeviceBuffer(self.n).upload(b), DeviceBuffer(self.n)
-        dx.upload(np.zeros(self.n) if x0 is None else x0)
-        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
-        it, rel = C.c_int(0), C.c_double(0)
-        _check(self.lib.ehyb_pcg(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), C.c_void_p(dx.ptr),
-                                 max_iter, rtol, check_every, None, C.byref(it), C.byref(rel)), "ehyb_pcg")
-        return dx.download(), it.value, rel.value
+        return self._solve("ehyb_pcg", b, x0, inv_diag, (max_iter, rtol, check_every))
 
     def cg_multi(self, B, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_cg_multi / ehyb_pcg_multi: k independent (Jacobi-preconditioned if inv_diag is given) CG solves that share every
         multiply; B, X0 (k, n) in the permuted numbering, column j solved as cg(B[j]) would.  -> (X (k, n), iterations (k,),
         relative residuals (k,)).  A breakdown raises EhybError, unless allow_breakdown: then the broken columns report NaN.
         The multiplies are as wide as spmm_max_k allows -- on a panel-form plan too, when it was built with er_panel_cols = 16384 // k."""
-        B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
-        k, n = B.shape
-        assert n == self.n, (n, self.n)
-        X0 = np.zeros_like(B) if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).reshape(k, n)
-        db, dx = DeviceBuffer(k * n).upload(B.ravel()), DeviceBuffer(k * n).upload(X0.ravel())
-        dd = None if inv_diag is None else DeviceBuffer(n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
-        it, rel = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64)
-        rc = self.lib.ehyb_pcg_multi(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k,
-                                     max_iter, rtol, check_every, C.c_void_p(stream), _ptr(it, C.c_int), _ptr(rel, C.c_double))
-        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
-            raise EhybError(rc, "ehyb_pcg_multi")
-        return dx.download().reshape(k, n), it, rel
+        return self._solve("ehyb_pcg_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
     def pcg_refine(self, inner_plan, b, x0=None, max_outer=10, inner_max_iter=1000, rtol=1e-12, inner_rtol=1e-6, inv_diag=None, stream=0):
         """ehyb_pcg_refine: iterative refinement -- residuals and updates in fp64 on this plan, the corrections from ehyb_pcg on
         inner_plan (normally the cfg.val_f32 plan of the same reordered matrix).  -> (x, outer steps, inner iterations in all,
         relative residual ||b - A x|| / ||b|| on this plan); a run that stagnates returns normally: compare the residual with rtol."""
-        b = np.ascontiguousarray(b, dtype=np.float64)
-        db = DeviceBuffer(self.n).upload(b)
-        dx = DeviceBuffer(self.n).upload(np.zeros(self.n) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64))
-        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
-        outer, inner, rel = C.c_int(0), C.c_int(0), C.c_double(0)
-        _check(self.lib.ehyb_pcg_refine(self.h, inner_plan.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), C.c_void_p(dx.ptr),
-                                        max_outer, inner_max_iter, rtol, inner_rtol, C.c_void_p(stream), C.byref(outer), C.byref(inner),
-                                        C.byref(rel)), "ehyb_pcg_refine")
-        return dx.download(), outer.value, inner.value, rel.value
+        return self._solve("ehyb_pcg_refine", b, x0, inv_diag, (max_outer, inner_max_iter, rtol, inner_rtol), stream, inner=inner_plan)
 
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
         b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative residual).  A breakdown raises EhybError,
         unless allow_breakdown: then x is the last good iterate and the counts are those of the device."""
-        b = np.ascontiguousarray(b, dtype=np.float64)
-        db = DeviceBuffer(self.n).upload(b)
-        dx = DeviceBuffer(self.n).upload(np.zeros(self.n) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64))
-        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
-        it, rel = C.c_int(0), C.c_double(0)
-        rc = self.lib.ehyb_bicgstab(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), C.c_void_p(dx.ptr), max_iter,
-                                    rtol, check_every, C.c_void_p(stream), C.byref(it), C.byref(rel))
-        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
-            raise EhybError(rc, "ehyb_bicgstab")
-        return dx.download(), it.value, rel.value
+        return self._solve("ehyb_bicgstab", b, x0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown)
 
     def bicgstab_multi(self, B, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab_multi: k independent BiCGSTAB solves (right Jacobi-preconditioned if inv_diag is given) that share both
@@ -546,18 +536,7 @@ class Plan:
         plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,)), the counts those of the device.  A
         breakdown in any column raises EhybError, unless allow_breakdown: then a broken column holds its last good iterate.
         The multiplies are as wide as spmm_max_k allows (build the plan with lds_doubles = 20480 // k)."""
-        B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
-        k, n = B.shape
-        assert n == self.n, (n, self.n)
-        X0 = np.zeros_like(B) if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).reshape(k, n)
-        db, dx = DeviceBuffer(k * n).upload(B.ravel()), DeviceBuffer(k * n).upload(X0.ravel())
-        dd = None if inv_diag is None else DeviceBuffer(n).upload(np.ascontiguousarray(inv_diag, dtype=np.float64))
-        it, rel = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64)
-        rc = self.lib.ehyb_bicgstab_multi(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k,
-                                          max_iter, rtol, check_every, C.c_void_p(stream), _ptr(it, C.c_int), _ptr(rel, C.c_double))
-        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
-            raise EhybError(rc, "ehyb_bicgstab_multi")
-        return dx.download().reshape(k, n), it, rel
+        return self._solve("ehyb_bicgstab_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
     def destroy(self):
         if self.h:

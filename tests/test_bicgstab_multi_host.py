@@ -1,5 +1,6 @@
-"""ehyb_bicgstab_multi on the host: every argument check of the k-right-hand-side BiCGSTAB, on plans that were never
-uploaded -- the checks come before any device work, so nothing here needs a GPU."""
+"""ehyb_bicgstab_multi and ehyb_bicgstab on the host: every argument check of the k-right-hand-side BiCGSTAB and of the one-vector
+entry point onto the same driver, on plans that were never uploaded -- the checks come before any device work, so nothing here
+needs a GPU."""
 import ctypes as C
 
 import pytest
@@ -79,3 +80,52 @@ def test_plan_over_some_rows_is_refused(E):
     assert 0 < part.rows[1] < part.n
     rc, msg = call(lib, part)
     assert rc == ERR_ARG and b"all rows" in msg
+
+
+# ------------------------------------------------------------------ the one-vector entry point: the same driver, its own name
+def call_one(lib, plan, h=None, d=D, b=B, x=X, max_iter=50, rtol=1e-8, check_every=10, outputs=True):
+    it, rel = (C.c_int(0), C.c_double(0)) if outputs else (None, None)
+    rc = lib.ehyb_bicgstab(plan.h if h is None else h, d, b, x, max_iter, rtol, check_every, None,
+                           C.byref(it) if outputs else None, C.byref(rel) if outputs else None)
+    return rc, lib.ehyb_last_error()
+
+
+def says_one_vector(msg):
+    return b"ehyb_bicgstab:" in msg and b"_multi" not in msg
+
+
+def test_one_vector_never_uploaded_plan_is_a_state_error(E, plan):
+    lib = E.host._lib.load()
+    rc, msg = call_one(lib, plan)
+    assert rc == ERR_STATE and b"upload" in msg and says_one_vector(msg), msg
+    for kw in (dict(max_iter=0, rtol=0.0, check_every=0), dict(max_iter=0, rtol=0.0, check_every=-1), dict(d=None),
+               dict(outputs=False), dict(d=None, outputs=False, max_iter=0, check_every=0)):
+        rc, msg = call_one(lib, plan, **kw)
+        assert rc == ERR_STATE and says_one_vector(msg), (kw, msg)
+
+
+@pytest.mark.parametrize("bad", [dict(b=None), dict(x=None), dict(max_iter=-1), dict(rtol=-1e-9), dict(rtol=float("nan"))],
+                         ids=["b", "x", "max_iter", "rtol-neg", "rtol-nan"])
+def test_one_vector_argument_errors_come_before_the_state_error(E, plan, bad):
+    lib = E.host._lib.load()
+    assert call_one(lib, plan, d=None)[0] == ERR_STATE           # a different error first: a stale text would show
+    rc, msg = call_one(lib, plan, **bad)
+    assert rc == ERR_ARG, bad
+    assert says_one_vector(msg) and b"upload" not in msg, (bad, msg)
+    assert (b"null argument" in msg) == ("b" in bad or "x" in bad), (bad, msg)
+    assert (b"max_iter" in msg) == ("max_iter" in bad or "rtol" in bad), (bad, msg)
+
+
+def test_one_vector_null_plan(E, plan):
+    lib = E.host._lib.load()
+    assert call_one(lib, plan)[0] == ERR_STATE
+    rc = lib.ehyb_bicgstab(None, D, B, X, 10, 1e-8, 10, None, None, None)
+    msg = lib.ehyb_last_error()
+    assert rc == ERR_ARG and says_one_vector(msg) and b"null argument" in msg, msg
+
+
+def test_one_vector_plan_over_some_rows_is_refused(E):
+    lib = E.host._lib.load()
+    part = host_plan(E, half=True, direct=2, sym_pairs=0)
+    rc, msg = call_one(lib, part)
+    assert rc == ERR_ARG and b"all rows" in msg and says_one_vector(msg), msg

@@ -222,6 +222,37 @@ def test_plain_storage_is_exact_for_every_check_every_graph_and_stream(E, gpu, m
     _same_bits(s.plan.bicgstab(b, check_every=1, **run), ref, "second run")
 
 
+def test_short_runs_follow_the_cpu_rule_with_and_without_graphs(E, gpu):
+    """The one-vector solve is the k-column driver at k = 1.  Runs too short for a capture (max_iter < 2), a capture followed by an
+    odd last burst (7 = 4 + 3 at check_every 4, 2 + 2 + 2 + 1 at check_every 1) and a start that is already converged (b = A x0):
+    status and iteration count are those of cpu_bicgstab, and the plan that replays a graph and the one that launches plainly
+    (graphs = 2) give the same bits."""
+    A = cd_matrix(120, 100, 3000, 1)
+    kw = dict(window_mode=2, lds_doubles=2048, sym_pairs=0)
+    s = System(E, A, **kw)
+    plain = E.Plan(s.m, E.make_config(graphs=2, **kw))
+    rng = np.random.default_rng(15)
+    x_start = rng.uniform(-1, 1, s.n)
+    rtol, dinv = 1e-10, 1.0 / A.diagonal()
+    for what, b, x0 in (("random b", rng.uniform(-1, 1, s.n), None), ("b = A x0", A @ x_start, x_start)):
+        bp, x0p = E.vector_reorder(b, s.perm), None if x0 is None else E.vector_reorder(x0, s.perm)
+        for jacobi in (True, False):
+            for max_iter in (0, 1, 2, 7):
+                _, it_cpu, _, status_cpu = cpu_bicgstab(A, b, x0=x0, max_iter=max_iter, rtol=rtol, dinv=dinv if jacobi else None)
+                assert status_cpu == ("converged" if x0 is not None else "max_iter"), (what, jacobi, max_iter, status_cpu)
+                for check_every in (1, 4):
+                    case = (what, jacobi, max_iter, check_every)
+                    run = dict(x0=x0p, max_iter=max_iter, rtol=rtol, check_every=check_every, inv_diag=s.inv_diag if jacobi else None)
+                    got = s.plan.bicgstab(bp, **run)              # (a breakdown would raise)
+                    _same_bits(plain.bicgstab(bp, **run), got, f"graphs=2 {case}")
+                    status = "converged" if got[2] <= rtol else "max_iter"
+                    print(case, "device", got[1], status, got[2], "cpu", it_cpu, status_cpu)
+                    assert status == status_cpu, (case, got[1:], it_cpu, status_cpu)
+                    assert abs(got[1] - it_cpu) <= 5, (case, got[1], it_cpu)
+                    if status_cpu == "max_iter":
+                        assert got[1] == max_iter, (case, got[1])
+
+
 def test_max_iter_is_the_count(E, gpu):
     s = System(E, cd_matrix(100, 90, 2000, 9), lds_doubles=2048)
     b = E.vector_reorder(np.ones(s.n), s.perm)
