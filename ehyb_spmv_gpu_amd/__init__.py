@@ -20,6 +20,7 @@ from .host import (  # noqa: F401
     Plan,
     SpmvGraph,
     Stream,
+    cheb_coeffs,
     device_count,
     entry_order,
     host_threads,

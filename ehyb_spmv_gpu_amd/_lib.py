@@ -220,6 +220,13 @@ SIGNATURES = {
     "ehyb_cg_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_cg_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_cg_direction_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_cheb_coeffs": (C.c_int, [C.c_double, C.c_double, C.c_int, _dp, _dp, _dp]),
+    "ehyb_lambda_max": (C.c_int, [_vp, _vp, C.c_int, _vp, _dp]),
+    "ehyb_pcg_cheb": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_pcg_cheb_multi": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                      C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_cheb_start_step": (C.c_int, [C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_cheb_step": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_bicgstab_layout": (C.c_int, [_P(BicgstabSlots)]),
     "ehyb_bicgstab_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),

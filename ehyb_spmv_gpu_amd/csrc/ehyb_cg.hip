@@ -25,6 +25,7 @@
 #include <cmath>
 #include <vector>
 
+#include "cg_shared.h"
 #include "ehyb_internal.h"
 #include "solve_loop.h"
 
@@ -32,10 +33,7 @@ using namespace ehyb;
 
 namespace {
 
-// partial arrays, kMaxGrid doubles each
-// (r.r sits between the two r.z slots, so that the pair an iteration writes -- its new r.z and r.r -- is one
-// contiguous range for a multi-GPU caller's all-reduce: slot of r.z number c = A_RZ0 + 2 c)
-enum { A_BB = 0, A_PQ = 1, A_RZ0 = 2, A_RR = 3, A_RZ1 = 4, A_COUNT = 5 };
+// (the partial arrays of a column -- A_BB, A_PQ, A_RZ0, A_RR, A_RZ1 -- are cg_shared.h's: ehyb_cheb.hip uses the same layout)
 
 // r = b - q (q = A x0), z = dinv .* r (or r), p = z; partials of r.z, r.r, b.b
 __global__ __launch_bounds__(kThreads) void cg_init_kernel(int n, const double* __restrict__ b,
@@ -254,7 +252,48 @@ void launch_vector_kernels(int grid, hipStream_t st, int n, double* P, const dou
     hipLaunchKernelGGL(cg_multi_direction_kernel<K>, dim3(grid), dim3(kThreads), 0, st, n, R, dinv, P, s, active, c0, cur);
 }
 
+// launch<K>(...) for a width known at run time
+template <typename F>
+void with_width(int K, F&& f)
+{
+    switch (K) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 }  // namespace
+
+// ------------------------------------------------------------------ the same kernels for ehyb_cheb.hip (cg_shared.h)
+void ehyb::cg_launch_init(int grid, hipStream_t st, int n, const double* b, const double* q, const double* dinv, double* r, double* p,
+                          double* s)
+{
+    hipLaunchKernelGGL(cg_init_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, q, dinv, r, p, s);
+}
+void ehyb::cg_launch_dot(int K, int grid, hipStream_t st, int n, const double* P, const double* Q, double* s, const int* active, int c0)
+{
+    with_width(K, [&](auto W) {
+        hipLaunchKernelGGL(cg_multi_dot_kernel<decltype(W)::value>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, s, active, c0);
+    });
+}
+void ehyb::cg_launch_update(int K, int grid, hipStream_t st, int n, const double* P, const double* Q, const double* dinv, double* X,
+                            long long ldx, double* R, double* s, const int* active, int c0, int cur)
+{
+    with_width(K, [&](auto W) {
+        hipLaunchKernelGGL(cg_multi_update_kernel<decltype(W)::value>, dim3(grid), dim3(kThreads), 0, st, n, P, Q, dinv, X, ldx, R, s, active,
+                           c0, cur);
+    });
+}
+void ehyb::cg_launch_direction(int K, int grid, hipStream_t st, int n, const double* Zv, const double* dinv, double* P, const double* s,
+                               const int* active, int c0, int cur)
+{
+    with_width(K, [&](auto W) {
+        hipLaunchKernelGGL(cg_multi_direction_kernel<decltype(W)::value>, dim3(grid), dim3(kThreads), 0, st, n, Zv, dinv, P, s, active, c0,
+                           cur);
+    });
+}
 
 extern "C" int ehyb_cg(ehyb_plan* P, const double* b, double* x, int max_iter, double rtol, int check_every,
                        void* stream, int* iters_done, double* rel_residual)

@@ -16,24 +16,39 @@
 
 namespace {
 
-// in this order: the arguments (args_ok: the solver's own pointers), a plan over all rows, the upload; who: the entry point
-inline int solve_prologue(const char* who, const ehyb_plan* P, bool args_ok, int max_iter, double rtol)
+// in this order: the arguments (args_ok: the solver's own pointers), a plan over all rows, the upload; who: the entry point.
+// solve_args is the part that returns EHYB_ERR_ARG: a solver with argument checks of its own runs them between the two.
+inline int solve_args(const char* who, const ehyb_plan* P, bool args_ok, int max_iter, double rtol)
 {
     ::ehyb::clear_error();
     if (!P || !args_ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
     if (max_iter < 0 || !(rtol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "%s: max_iter %d, rtol %g", who, max_iter, rtol);
     if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "%s: needs a plan over all rows", who);
+    return EHYB_OK;
+}
+inline int solve_uploaded(const char* who, const ehyb_plan* P)
+{
     if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: plan not uploaded (no CPU fallback exists)", who);
     return EHYB_OK;
 }
+inline int solve_prologue(const char* who, const ehyb_plan* P, bool args_ok, int max_iter, double rtol)
+{
+    const int rc = solve_args(who, P, args_ok, max_iter, rtol);
+    return rc != EHYB_OK ? rc : solve_uploaded(who, P);
+}
 
 // a k-column solve: k first, then the leading dimensions, then solve_prologue
-inline int multi_prologue(const char* who, const ehyb_plan* P, bool args_ok, int64_t ldb, int64_t ldx, int k, int max_iter, double rtol)
+inline int multi_args(const char* who, const ehyb_plan* P, int64_t ldb, int64_t ldx, int k)
 {
     if (k < 1) EHYB_FAIL(EHYB_ERR_ARG, "%s: k = %d right-hand sides (at least 1)", who, k);
     if (P && (ldb < P->host.n_cols || ldx < P->host.n_cols))
         EHYB_FAIL(EHYB_ERR_ARG, "%s: ldb %lld, ldx %lld < %d rows", who, (long long)ldb, (long long)ldx, P->host.n_cols);
-    return solve_prologue(who, P, args_ok, max_iter, rtol);
+    return EHYB_OK;
+}
+inline int multi_prologue(const char* who, const ehyb_plan* P, bool args_ok, int64_t ldb, int64_t ldx, int k, int max_iter, double rtol)
+{
+    const int rc = multi_args(who, P, ldb, ldx, k);
+    return rc != EHYB_OK ? rc : solve_prologue(who, P, args_ok, max_iter, rtol);
 }
 
 // a *_step building block: n and every pointer it requires (an optional one, dinv, is not listed)

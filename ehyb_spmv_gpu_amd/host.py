@@ -481,10 +481,11 @@ class Plan:
                                         C.byref(r) if per_kernel else None), "ehyb_spmv_bench")
         return {"ms_total": t.value, "ms_ell_avg": e.value, "ms_er_avg": r.value}
 
-    def _solve(self, name, B, X0, inv_diag, scalars, stream=0, allow_breakdown=False, multi=False, inner=None):
+    def _solve(self, name, B, X0, inv_diag, scalars, stream=0, allow_breakdown=False, multi=False, inner=None, counters=None):
         """One call of the solver `name`: B, X0 (zeros if None) and the optional inv_diag staged on the device; the arguments in
         the one-vector shape or (multi) the (ldb, ldx, k) one, `scalars` between the vectors and the stream; `inner`: the second
-        plan of ehyb_pcg_refine, which also reports two integer counters instead of one.  A failure raises EhybError, unless
+        plan of ehyb_pcg_refine, which also reports two integer counters instead of one, or of ehyb_pcg_cheb (counters=1).  A
+        failure raises EhybError, unless
         allow_breakdown and the error text says breakdown.  -> (X, counters ...): scalars from a one-vector call, (k,) arrays
         and X (k, n) from a multi one."""
         n, k = self.n, 1
@@ -496,7 +497,7 @@ class Plan:
         db = DeviceBuffer(k * n).upload(B.ravel())
         dx = DeviceBuffer(k * n).upload(np.zeros(k * n) if X0 is None else np.ravel(X0))
         dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
-        counts, rel = np.zeros((1 if inner is None else 2, k), dtype=np.int32), np.zeros(k, dtype=np.float64)
+        counts, rel = np.zeros((counters or (1 if inner is None else 2), k), dtype=np.int32), np.zeros(k, dtype=np.float64)
         vectors = (C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k) if multi else (C.c_void_p(db.ptr), C.c_void_p(dx.ptr))
         rc = getattr(self.lib, name)(self.h, *(() if inner is None else (inner.h,)), C.c_void_p(dd.ptr) if dd else None, *vectors,
                                      *scalars, C.c_void_p(stream), *(_ptr(c, C.c_int) for c in counts), _ptr(rel, C.c_double))
@@ -524,6 +525,32 @@ class Plan:
         relative residual ||b - A x|| / ||b|| on this plan); a run that stagnates returns normally: compare the residual with rtol."""
         return self._solve("ehyb_pcg_refine", b, x0, inv_diag, (max_outer, inner_max_iter, rtol, inner_rtol), stream, inner=inner_plan)
 
+    def lambda_max(self, inv_diag=None, iters=20, stream=0):
+        """ehyb_lambda_max: the Rayleigh quotient after `iters` steps of the power method on D^-1 A (inv_diag in the permuted
+        numbering; None: on A) -- an estimate of the largest eigenvalue from below."""
+        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(inv_diag)
+        lam = C.c_double(0)
+        _check(self.lib.ehyb_lambda_max(self.h, C.c_void_p(dd.ptr) if dd else None, int(iters), C.c_void_p(stream), C.byref(lam)),
+               "ehyb_lambda_max")
+        return lam.value
+
+    def cg_cheb(self, b, degree, poly_plan=None, lmin=0.0, lmax=0.0, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None,
+                allow_breakdown=False, stream=0):
+        """ehyb_pcg_cheb: CG on this plan, preconditioned with a Chebyshev polynomial of `degree` in D^-1 A evaluated on
+        poly_plan (None: this plan; intended: the cfg.val_f32 plan of the same reordered matrix).  lmax <= 0: estimated
+        (1.1 * lambda_max on poly_plan), lmin <= 0: lmax / 30; lmax must be an upper bound of the spectrum of D^-1 A.
+        -> (x, iterations, relative residual).  A breakdown raises EhybError, unless allow_breakdown: then the residual is NaN."""
+        return self._solve("ehyb_pcg_cheb", b, x0, inv_diag, (int(degree), lmin, lmax, max_iter, rtol, check_every), stream, allow_breakdown,
+                           inner=poly_plan or self, counters=1)
+
+    def cg_cheb_multi(self, B, degree, poly_plan=None, lmin=0.0, lmax=0.0, X0=None, max_iter=1000, rtol=1e-10, check_every=10,
+                      inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_pcg_cheb_multi: k independent cg_cheb solves that share every multiply; B, X0 (k, n), column j solved as
+        cg_cheb(B[j]) would -- with plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,)).  The
+        multiplies are as wide as spmm_max_k of each plan allows: a cfg.val_f32 poly_plan runs passes of width 1."""
+        return self._solve("ehyb_pcg_cheb_multi", B, X0, inv_diag, (int(degree), lmin, lmax, max_iter, rtol, check_every), stream,
+                           allow_breakdown, multi=True, inner=poly_plan or self, counters=1)
+
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
         b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative residual).  A breakdown raises EhybError,
@@ -548,6 +575,14 @@ class Plan:
             self.destroy()
         except Exception:
             pass
+
+
+def cheb_coeffs(lmin, lmax, degree):
+    """ehyb_cheb_coeffs -> (c0, a (degree,), b (degree,)): the coefficients of the Chebyshev preconditioner's recurrence."""
+    c0 = C.c_double(0)
+    a, b = np.zeros(max(int(degree), 0)), np.zeros(max(int(degree), 0))
+    _check(_lib.load().ehyb_cheb_coeffs(lmin, lmax, int(degree), C.byref(c0), _ptr(a, C.c_double), _ptr(b, C.c_double)), "ehyb_cheb_coeffs")
+    return c0.value, a, b
 
 
 def spmv_gpu_ehyb(matrix, vector_in, max_iter, cfg=None, timing=False):

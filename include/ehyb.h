@@ -898,6 +898,75 @@ int ehyb_bicgstab_multi(ehyb_plan* plan, const double* inv_diag_dev, const doubl
                         int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
 
 /*
+ * CG with a Chebyshev polynomial preconditioner: the preconditioner that is all multiplies -- no triangular solve, no second
+ * matrix format, no dot product inside.  Let [lmin, lmax] enclose the spectrum of D^-1 A, where D^-1 = inv_diag (NULL: the
+ * identity, and the interval encloses the spectrum of A).  theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2,
+ * sigma = theta / delta.  z = M^-1 r of degree m >= 0 is
+ *   c0 = 1 / theta;  rho_0 = 1 / sigma
+ *   d = c0 D^-1 r;  z = d;  w = r
+ *   for j = 1 .. m:  t = A~ d;  w = w - t;  rho_j = 1 / (2 sigma - rho_{j-1});  a_j = rho_j rho_{j-1};  b_j = 2 rho_j / delta
+ *                    d = a_j d + b_j D^-1 w;  z = z + d
+ * A~ is the matrix of poly_plan; m multiplies per application; degree 0 is Jacobi scaled by 1 / theta.  With z = p(D^-1 A) D^-1 r,
+ * 1 - lambda p(lambda) = T_{m+1}((theta - lambda) / delta) / T_{m+1}(sigma), and p > 0 on (0, lmax].  p can turn negative just
+ * above lmax (degree 1 does at 1.1 lmax): lmax MUST be an upper bound of the spectrum, or CG breaks down.  lmin need not be a
+ * lower bound: it only says where the polynomial stops trying.
+ *
+ * ehyb_cheb_coeffs (host only): c0 and a[j-1], b[j-1] for j = 1 .. degree, computed in the order stated above.  EHYB_ERR_ARG
+ * for a degree outside 0 .. EHYB_CHEB_MAX_DEGREE, unless 0 < lmin < lmax < inf, or a null output that would be written.
+ *
+ * ehyb_lambda_max: `iters` steps of the power method on D^-1 A from v_i = 1 + (i mod 7) / 8, v <- D^-1 A v / ||D^-1 A v||_2;
+ * *lambda = (v.Av) / (v.Dv) of the last v -- a Rayleigh quotient: never above the largest eigenvalue in exact arithmetic, so a
+ * caller multiplies it by a safety factor.  iters + 1 multiplies (walks alternating) and as many launches of one small kernel;
+ * the norms stay on the device.  Stream and plan as for a solve; EHYB_ERR_ARG for iters < 1, and -- after *lambda is written --
+ * for an estimate that is not a positive finite number.
+ *
+ * ehyb_pcg_cheb: x_dev, b_dev, stream, check_every, outputs and stopping as ehyb_pcg; iters_done is the check point at which the
+ * solve stopped, as in ehyb_pcg_multi.  poly_plan NULL = plan; otherwise any uploaded plan over all rows with the same number of
+ * rows -- the intended one is the cfg.val_f32 = 1 plan of the same reordered matrix (half the value bytes per multiply of the
+ * polynomial; the CG around it stays in fp64 on `plan`, so the answer is an fp64 answer without an outer refinement loop); a
+ * panel-form plan works too, the polynomial only calls the multiply.  lmax <= 0: estimated, 1.1 * ehyb_lambda_max(poly_plan,
+ * inv_diag_dev, 20) on the solve's stream.  lmin <= 0: lmax / 30.  The 20 steps, the factor 1.1 and the ratio 30 are the defaults
+ * hypre and Ifpack2 ship for their Chebyshev smoothers: defaults, not values tuned on this library's matrices.
+ * Per iteration: q = A p on `plan`, p.q (a dot kernel of its own: cfg.cg_fused_dot is ignored), the update kernel of ehyb_pcg
+ * without a preconditioner (x += alpha p, r -= alpha q, r.r), the polynomial -- one start kernel, then `degree` rounds of a
+ * multiply on poly_plan and one step kernel; whichever kernel finishes z also reads r and leaves the partials of r.z --, and
+ * the direction kernel p = z + beta p.  Every multiply states its walk, alternating along the sequence each plan sees; an even
+ * and an odd iteration are replayed from one hipGraph, cfg.graphs = 2 issues the same launches unrecorded.  With plain storage
+ * x, iters_done and rel_residual are the same bits from run to run, for graphs and plain launches.
+ * Breakdown (EHYB_ERR_ARG, "breakdown" in ehyb_last_error, after every output is written, rel_residual NaN): r.r or r.z NaN at
+ * a check point, or an r.z <= 0 there short of convergence -- the polynomial was not positive on the spectrum.
+ * EHYB_ERR_ARG, in this order: what ehyb_pcg rejects (a null plan, b or x, max_iter < 0, a negative or NaN rtol, a plan not over
+ * all rows); a degree outside 0 .. EHYB_CHEB_MAX_DEGREE; lmin >= lmax when both are positive; a NaN bound; a poly_plan with
+ * another number of rows, or one that does not cover all rows.  Then EHYB_ERR_STATE for a plan, then a poly_plan, that was never
+ * uploaded.  All before any device work.  (A given lmin that turns out >= an estimated lmax is EHYB_ERR_ARG after the estimate.)
+ *
+ * ehyb_pcg_cheb_multi is ehyb_pcg_multi with this preconditioner: B, X, ldb, ldx, k, the per-column freezing at check points and
+ * the outputs as there (k < 1 and ldb, ldx < n are rejected first).  One ehyb_spmm of the k directions on `plan` and `degree`
+ * ehyb_spmm of the k columns of d on poly_plan per iteration, each ceil(k / ehyb_spmm_max_k) passes: a cfg.val_f32 plan has
+ * k_max = 1 and runs k passes of width 1.  The coefficients are the same for every column.  With plain storage column j equals
+ * ehyb_pcg_cheb on b_j bit for bit -- it is the same driver --, but for rows the residual splits into several segments (ehyb_spmm).
+ *
+ * ehyb_cheb_start_step / ehyb_cheb_step: the two kernels one launch at a time with slot_doubles / 2 workgroups, as the
+ * ehyb_cg_*_step calls.  start: d = z = c0 D^-1 r.  step: w_out = w_in - t, d = a d + b D^-1 w_out, z += d; w_out may be w_in.
+ * rz = -1: no sum, s_dev is not touched (and r_dev of the step not read); rz = 0 / 1: the partials of r.z go to r.z slot number
+ * rz of ehyb_cg_layout (slot rz0 + 2 rz).  EHYB_ERR_ARG for n < 0, another rz or a null pointer that would be used.
+ */
+#define EHYB_CHEB_MAX_DEGREE 16
+/* host only: c0 and a[j-1], b[j-1] for j = 1..degree, computed in the order stated above */
+int ehyb_cheb_coeffs(double lmin, double lmax, int degree, double* c0, double* a, double* b);
+int ehyb_lambda_max(ehyb_plan* plan, const double* inv_diag_dev, int iters, void* stream, double* lambda);
+int ehyb_pcg_cheb(ehyb_plan* plan, ehyb_plan* poly_plan, const double* inv_diag_dev, const double* b_dev, double* x_dev,
+                  int degree, double lmin, double lmax, int max_iter, double rtol, int check_every, void* stream,
+                  int* iters_done, double* rel_residual);
+int ehyb_pcg_cheb_multi(ehyb_plan* plan, ehyb_plan* poly_plan, const double* inv_diag_dev, const double* B_dev, int64_t ldb,
+                        double* X_dev, int64_t ldx, int k, int degree, double lmin, double lmax, int max_iter, double rtol,
+                        int check_every, void* stream, int* iters_done, double* rel_residual);
+int ehyb_cheb_start_step(int n, const double* r_dev, const double* inv_diag_dev, double c0, double* d_dev, double* z_dev,
+                         double* s_dev, int rz, void* stream);
+int ehyb_cheb_step(int n, const double* w_in_dev, const double* t_dev, const double* inv_diag_dev, double a, double b,
+                   double* w_out_dev, double* d_dev, double* z_dev, const double* r_dev, double* s_dev, int rz, void* stream);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
