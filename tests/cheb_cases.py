@@ -48,15 +48,17 @@ def apply(mul, dinv, r, c0, a, b):
     return z
 
 
-def pcg(A, b, degree, lmin, lmax, dinv=None, poly_A=None, max_iter=1000, rtol=1e-10):
-    """The solve of ehyb_pcg_cheb, iteration for iteration (x0 = 0) -> (x, iterations, smallest r.z seen)"""
+def pcg(A, b, degree, lmin, lmax, dinv=None, poly_A=None, max_iter=1000, rtol=1e-10, x0=None, check_every=1):
+    """The solve of ehyb_pcg_cheb, iteration for iteration (x0 None: 0; the stopping test is made every check_every
+    iterations, as the device makes it) -> (x, iterations, smallest r.z seen)"""
     P = A if poly_A is None else poly_A
     c0, ca, cb = coeffs(lmin, lmax, degree)
-    x, r = np.zeros_like(b), b.copy()
+    x = np.zeros_like(b) if x0 is None else x0.copy()
+    r = b.copy() if x0 is None else b - A @ x0
     z = apply(lambda v: P @ v, dinv, r, c0, ca, cb)
-    p, rz, bb = z.copy(), r @ z, b @ b
+    p, rz, bb = z.copy(), r @ z, (b @ b) or 1.0
     it, rz_min = 0, rz
-    while it < max_iter and np.sqrt((r @ r) / bb) > rtol:
+    while it < max_iter and (it % check_every or np.sqrt((r @ r) / bb) > rtol):
         q = A @ p
         alpha = rz / (p @ q)
         x += alpha * p
@@ -67,6 +69,54 @@ def pcg(A, b, degree, lmin, lmax, dinv=None, poly_A=None, max_iter=1000, rtol=1e
         rz_min = min(rz_min, rz)
         it += 1
     return x, it, rz_min
+
+
+# ------------------------------------------------------------------ the freezing mix at full size (test_gpu_cheb_full.py)
+# The right-hand-side bank of test_gpu_solver_kernels.MIX_KINDS with the e of its "near" columns (b = A x*, x0 = x* + e u)
+# chosen for this solver.  Relative residual per unit e on spd_matrix(1024, 921, 3000, 21) after 0, 2, 4, 6, 8 iterations, from
+# pcg above with lmax = 2.1 and inv_diag (Jacobi) or lmax = 1.05 max_i sum_j |a_ij| without, lmin = lmax / 30:
+#   degree 4, Jacobi (the same to three digits with the polynomial on the fp32-rounded matrix)
+#                      3.4  0.118  0.0046  0.00127  0.00037     a random b from x0 = 0 is at 9.9e-5 after 12
+#   degree 2, plain    3.4  0.146  0.0299  0.0107   0.0049                                   7.8e-3
+#   degree 1, Jacobi   3.4  0.264  0.0328  0.0158   0.0078                                   1.2e-2
+#   degree 0, Jacobi   3.4  0.354  0.108   0.0487   0.0264   (any lmin, lmax: a scaled z)    7.1e-2
+# MIX_E[degree, Jacobi] = the three e that cross MIX_RTOL = 1e-6 at check points 2, 4 and 6 (check_every = 2): each near the
+# geometric middle of its interval, 1e-6 / sqrt(residual before * residual after), a factor of 1.4 to 4.8 from either edge.
+MIX_E = {(4, True): (5e-6, 1e-4, 5e-4), (2, False): (1.5e-6, 1.5e-5, 5.6e-5), (1, True): (1e-6, 1.1e-5, 4.4e-5),
+         (0, True): (9e-7, 5e-6, 1.4e-5)}
+
+
+def mix_bank(A, kinds, seed=77):
+    """The bank of big_spd (test_gpu_solver_kernels.py), drawn in the same order, without its e: -> (x*, B, U, rank) in A's own
+    numbering; U[j] is the u of a "near" column (uniform in [-1, 1]) and None otherwise; rank[j] of a near column says which of
+    the three e it takes: 0, 1, 2 for the smallest, middle and largest e of `kinds`."""
+    n = A.shape[0]
+    rng = np.random.default_rng(seed)
+    x_star = np.sin(np.arange(n) * 1e-3) + 1.5
+    order = sorted({e for kind, e in kinds if kind == "near"})
+    B, U, rank = [], [], []
+    for kind, e in kinds:
+        if kind == "near":
+            B.append(A @ x_star)
+            U.append(rng.uniform(-1, 1, n))
+            rank.append(order.index(e))
+        else:
+            B.append(np.zeros(n) if kind == "zero" else rng.uniform(-1, 1, n))
+            U.append(None)
+            rank.append(None)
+    return x_star, B, U, rank
+
+
+def mix_x0(x_star, U, rank, es):
+    """the start vectors of the bank for the three e of MIX_E"""
+    return [np.zeros_like(x_star) if u is None else x_star + es[k] * u for u, k in zip(U, rank)]
+
+
+def tridiagonal(n):
+    """2.05 on the diagonal, -1 beside it: SPD, strictly diagonally dominant, any n >= 1"""
+    import scipy.sparse as sp
+
+    return sp.diags([np.full(max(n - 1, 0), -1.0), np.full(n, 2.05), np.full(max(n - 1, 0), -1.0)], [-1, 0, 1], shape=(n, n)).tocsr()
 
 
 def jacobi_pcg(A, b, dinv, max_iter=1000, rtol=1e-10):

@@ -252,3 +252,35 @@ def test_precondition_and_width_at_every_size(n):
                 assert wide == 0, (name, k)
             else:
                 assert wide >= n // 2, (name, k, wide)
+
+
+# ------------------------------------------------------------------ what test_gpu_cheb_full.py rests on
+def test_the_walk_at_full_size_and_at_the_size_of_the_k_column_tests():
+    """n = 943,104: the solve launches the grid of the step entry points, every thread runs an unrolled body; at 12,000 none"""
+    n = 1024 * 921
+    assert sc.solver_grid(n) == sc.STEP_GRID and sc.walk_profile(n, sc.STEP_GRID) == {(1, 3), (2, 0)}
+    assert sc.walk_profile(12000, sc.solver_grid(12000)) == {(0, 0), (0, 1)}
+    assert -(-n // sc.S) == 8, "trips of the lambda kernels' loop"
+    assert [sc.solver_grid(k) for k in (1, 2, 65, 257)] == [1, 1, 1, 2]
+
+
+def test_the_restatement_from_a_start_vector_and_the_mix_bank():
+    """pcg with x0 and check_every on a tridiagonal system: x0 = 0 is the default, the stopping test is made at multiples of
+    check_every only; the bank keeps the order of the draws and gives every near column its e by rank"""
+    A = cc.tridiagonal(65)
+    assert abs(A - A.T).nnz == 0 and A.diagonal().min() == 2.05 and A.nnz == 3 * 65 - 2 and cc.tridiagonal(1).toarray().tolist() == [[2.05]]
+    b = A @ np.ones(65)
+    x, it, _ = cc.pcg(A, b, 3, 4.05 / 30, 4.05, rtol=1e-10)
+    x2, it2, _ = cc.pcg(A, b, 3, 4.05 / 30, 4.05, rtol=1e-10, x0=np.zeros(65), check_every=1)
+    assert it == it2 and np.array_equal(x, x2) and np.abs(x - 1).max() < 1e-8
+    x4, it4, _ = cc.pcg(A, b, 3, 4.05 / 30, 4.05, rtol=1e-10, check_every=4)
+    assert it4 % 4 == 0 and it <= it4 < it + 4
+    assert cc.pcg(A, b, 3, 4.05 / 30, 4.05, x0=np.ones(65))[1] == 0
+    kinds = [("near", 5e-6), ("zero", 0), ("random", 0), ("near", 1e-6), ("near", 1.2e-5), ("near", 5e-6)]
+    x_star, B, U, rank = cc.mix_bank(A, kinds)
+    assert rank == [1, None, None, 0, 2, 1] and [u is None for u in U] == [False, True, True, False, False, False]
+    assert not B[1].any() and np.array_equal(B[0], A @ x_star) and np.abs(B[2]).max() <= 1 and not np.array_equal(U[0], U[3])
+    X0 = cc.mix_x0(x_star, U, rank, (1.0, 2.0, 3.0))
+    assert np.array_equal(X0[3], x_star + U[3]) and np.array_equal(X0[4], x_star + 3.0 * U[4]) and not X0[1].any()
+    for es in cc.MIX_E.values():
+        assert es[0] < es[1] < es[2]

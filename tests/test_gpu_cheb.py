@@ -215,6 +215,46 @@ def test_multi_with_the_polynomial_on_the_val_f32_plan(E, gpu, wide):
         assert np.linalg.norm(s.A @ x - bj) <= 2e-10 * np.linalg.norm(bj)
 
 
+# ------------------------------------------------------------------ the small ends
+@pytest.mark.parametrize("n", [1, 2, 65, 257])
+def test_small_tridiagonal_systems(E, gpu, n):
+    """cheb_cases.tridiagonal, n = 1, 2, 65: one workgroup, most of its threads (all but one) without an element; n = 257:
+    two.  The eigenvalues of D^-1 A lie in (0.024, 1.976): lmax = 2.1 is an upper bound.  x against spsolve: cond(A) <= 4.05 / 0.05
+    = 81, so rel <= 1e-10 leaves an error below 8.1e-9 -- the 1e-8 of this file."""
+    A = cc.tridiagonal(n)
+    cfg = E.make_config(sym_pairs=0)
+    m = E.Matrix.from_csr(A.indptr, A.indices, A.data, cfg, symmetric=True)
+    m.reorder(cfg)
+    perm = m.reorder_list.copy()
+    plan = E.Plan(m, cfg)
+    assert plan.stats["sym_pairs"] == 0 and not (plan.array("er_seg_row") < 0).any() and -(-n // 256) == (2 if n == 257 else 1)
+    xs = np.stack([np.ones(n), np.cos(np.arange(n) * 0.3) + 2.0, np.random.default_rng(n).uniform(-1, 1, n)])
+    B = np.stack([E.vector_reorder(A @ x, perm) for x in xs])
+    kw = dict(lmax=2.1, rtol=RTOL, check_every=1, inv_diag=E.vector_reorder(1.0 / A.diagonal(), perm))
+    want = singles(plan, B, 3, **kw)
+    got = plan.cg_cheb_multi(B, 3, **kw)
+    print(f"n={n}: iterations {list(got[1])}, relative residuals {list(got[2])}")
+    assert_same_bits(got, want, f"tridiagonal n={n}")
+    assert (got[2] <= RTOL).all() and (want[2] <= RTOL).all(), (got[2], want[2])
+    for j in range(3):
+        x_ref = np.atleast_1d(spla.spsolve(A.tocsc(), A @ xs[j]))
+        assert np.linalg.norm(E.vector_recover(got[0][j], perm) - x_ref) <= 1e-8 * np.linalg.norm(x_ref), j
+    plan.destroy()
+
+
+def test_lambda_max_of_a_one_by_one_matrix(E, gpu):
+    """[4.0]: u = 1, A u = 4, every scale a power of two -- the quotient is exactly 1 with inv_diag = [0.25], exactly 4 without"""
+    A = sp.csr_matrix(np.array([[4.0]]))
+    cfg = E.make_config()
+    m = E.Matrix.from_csr(A.indptr, A.indices, A.data, cfg, symmetric=True)
+    m.reorder(cfg)
+    plan = E.Plan(m, cfg)
+    for iters in (1, 20):
+        assert plan.lambda_max(np.array([0.25]), iters) == 1.0
+        assert plan.lambda_max(None, iters) == 4.0
+    plan.destroy()
+
+
 # ------------------------------------------------------------------ breakdown, and the state error that needs a device
 def test_lmax_below_the_spectrum_breaks_down_or_converges(E, gpu, small):
     """Degree 1 with lmax at half the largest eigenvalue: the polynomial is negative on part of the spectrum.  Either a normal

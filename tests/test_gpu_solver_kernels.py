@@ -497,6 +497,7 @@ MIX_RTOL, MIX_ITERS, MIX_EVERY = 1e-6, 12, 2
 # and without Jacobi), so e = 1e-6, 5e-6, 1.2e-5 cross MIX_RTOL at the check points 2, 4 and 6.  "zero": b = 0, frozen before
 # the first iteration.  "random": a random b from x0 = 0 is at 0.1 after 12 iterations and runs to max_iter.
 MIX_KINDS = [("near", 5e-6), ("zero", 0), ("random", 0), ("near", 1e-6), ("near", 1.2e-5), ("near", 5e-6), ("random", 0)]
+BIG_SPD_KW = dict(lds_doubles=5120, direct=2, sym_pairs=0, cg_fused_dot=2)       # (test_gpu_cheb_full.py builds its val_f32 plan with them)
 
 
 class BigSystem:
@@ -520,7 +521,7 @@ class BigSystem:
 
 @pytest.fixture(scope="module")
 def big_spd(E, gpu):
-    s = BigSystem(E, spd_matrix(FULL_NX, FULL_NY, 3000, 21), True, lds_doubles=5120, direct=2, sym_pairs=0, cg_fused_dot=2)
+    s = BigSystem(E, spd_matrix(FULL_NX, FULL_NY, 3000, 21), True, **BIG_SPD_KW)
     rng = np.random.default_rng(77)
     x_star = np.sin(np.arange(s.n) * 1e-3) + 1.5
     B, X0 = [], []

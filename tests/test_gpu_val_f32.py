@@ -6,7 +6,26 @@ matrix float(a_ij), per accumulator in the fp64 kernel's order.  So
     matrix, which differs from the exact product of the matrix itself;
   - with plain storage and no split rows the result equals that of an fp64 plan built from the rounded values for ANY values
     and x (np.array_equal), the solvers' iterates included; with symmetric pairs up to the order of the LDS adds.
-Without the feature every test here fails at make_config(val_f32=1)."""
+Without the feature every test here fails at make_config(val_f32=1).
+
+Which exact test launches which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> (the plan's cfg.threads, stats["er_inline"] > 0,
+stats["sym_pairs"] > 0; test_val_f32_host.py pins the seeds' share of the table from host-only plans):
+
+  THREADS  INLINE_ER  SYM    test_exact_random_plan_f32 (seeds)      named
+  256      no         no     102 107 109 115 122 123 128 135 137     refwindow-t256-lds1024
+  256      no         yes    134
+  256      yes        no     108
+  256      yes        yes    120                                     test_inline_residual_with_symmetric_pairs_f32[256-*]
+  512      no         no     104 114 129 136                         halo-t512-lds64
+  512      no         yes    131                                     sym-fem-3dof-t512-lds20480
+  512      yes        no     101
+  512      yes        yes    --                                      test_inline_residual_with_symmetric_pairs_f32[512-*]
+  1024     no         no     100 111 118 121 127 130                 refwindow-t1024-lds20480, csr-split-*, relative-columns
+  1024     no         yes    138                                     sym-fem-3dof, sym-*-accidental-pairs
+  1024     yes        no     110 117 124                             halo-t1024-lds20480, inline-residual
+  1024     yes        yes    --                                      test_inline_residual_with_symmetric_pairs_f32[1024-*]
+(named: ids of test_exact_named_path_f32 unless a test is named.  test_rounded_random_plan_f32 runs the same seeds on tie values,
+where the accidental pairs of seeds 134 and 138 are gone: those two take the arm without pairs there.)"""
 import ctypes as C
 
 import numpy as np
@@ -17,7 +36,7 @@ from exact_cases import assert_exact, exact_reference, integer_values, nonfinite
 from range_cases import family
 from test_gpu_exact import (FEM, PATHS, REFILL_PLANS, RMAT11, ExactCase, _device_set_values, _integer_spd, _sync, all_ways, is_direct,
                             multiply)
-from val_f32_cases import f32, small_odd_x, tie_values
+from val_f32_cases import FALLBACK_MAX, FEM_INLINE_SYM, FUZZ_SEEDS, f32, fuzz_case_f32, small_odd_x, tie_values, window_arm
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +54,118 @@ def test_exact_named_path_f32(E, O, gpu, name, gen, kw, sym, taken):
     assert taken(plan, c.n), (name, plan.stats)
     assert plan.device_value_bytes[0] == 4 * len(plan.array("ell_val")) and plan.spmm_max_k == 1
     all_ways(E, plan, c.xp, c.y_ref_p, name + " val_f32")
+    plan.destroy()
+
+
+# ---------------------------------------------------------------------------------------------- the random configurations
+_fell_back = set()
+
+
+def _fuzz_f32(E, O, seed, **more):
+    m, cfg, kw, x, y_ref, fell_back = fuzz_case_f32(E, O, seed, **more)
+    if fell_back:
+        _fell_back.add(seed)
+    assert len(_fell_back) <= FALLBACK_MAX, sorted(_fell_back)
+    return m, cfg, kw, x, y_ref
+
+
+def _checked_f32_plan(E, m, cfg, what):
+    """The upload of a configuration that passed fuzz_case_f32 must not be refused; the fp32 streams are what the device holds."""
+    plan = E.Plan(m, cfg)
+    assert plan.spmm_max_k == 1 and plan.device_value_bytes[0] == 4 * len(plan.array("ell_val")), what
+    assert plan.stats["er_partials"] == 0 and plan.stats["nnz_ell"] + plan.stats["nnz_er"] == m.nnz, what
+    return plan
+
+
+def _multiplies(E, plan, n, xp, yp, what):
+    for k in range(2):                          # (an alternating walk: the second multiply walks back)
+        assert_exact(multiply(E, plan, xp), yp, f"{what} multiply {k}")
+    if not is_direct(plan, n):
+        assert_exact(multiply(E, plan, xp, phases=(1, 2)), yp, f"{what} phases 1+2")
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
+def test_exact_random_plan_f32(E, O, gpu, seed):
+    """test_exact_random_plan with cfg.val_f32 = 1: every knob drawn at random, integer values (fp32 holds them) and x."""
+    m, cfg, kw, x, y_ref = _fuzz_f32(E, O, seed)
+    plan = _checked_f32_plan(E, m, cfg, str(kw))
+    print(f"seed {seed}: n={m.n} nnz={m.nnz} window arm {window_arm(cfg, plan.stats)}")
+    _multiplies(E, plan, m.n, E.vector_reorder(x, m.reorder_list), E.vector_reorder(y_ref, m.reorder_list), str(kw))
+    plan.destroy()
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
+def test_rounded_random_plan_f32(E, O, gpu, seed):
+    """The same plans on tie values (set after the reorder, in the plan's numbering): the exact product of the ROUNDED matrix,
+    which differs from that of the matrix; then a host refill with other tie values: exact again and the bits of a fresh plan."""
+    m, cfg, kw, _, _ = _fuzz_f32(E, O, seed, value_map=1)
+    n = m.n
+    A = m.to_scipy()
+    sym = m.nnz > 0 and abs(A - A.T).nnz == 0
+    xp = small_odd_x(n, seed)
+    V1, V2 = (tie_values(m.I, m.J, sym, salt=salt) if m.nnz else np.zeros(0) for salt in (seed, seed + 1))
+    if m.nnz:
+        y_full, y1, y2 = (exact_reference(n, m.I, m.J, V, xp) for V in (V1, f32(V1), f32(V2)))      # (asserts sum |a x| < 2^52)
+        assert (y_full != y1).any() and (y1 != y2).any(), "rounding the values, and the refill, must change the product"
+    else:
+        y1 = y2 = np.zeros(n)
+    m.V[:] = V1
+    plan = _checked_f32_plan(E, m, cfg, str(kw))
+    _multiplies(E, plan, n, xp, y1, f"{kw} ties")
+    if m.nnz:                                   # (no entry: nothing to refill)
+        plan.set_values(V2)
+        _multiplies(E, plan, n, xp, y2, f"{kw} ties after the refill")
+        m.V[:] = V2
+        fresh = _checked_f32_plan(E, m, cfg, str(kw))
+        assert fresh.stats == plan.stats
+        assert np.array_equal(multiply(E, fresh, xp).view(np.int64), multiply(E, plan, xp).view(np.int64))
+        fresh.destroy()
+    plan.destroy()
+
+
+# ---------------------------------------------------------------------------------------------- inline residual x symmetric pairs
+def _alternating_walk_and_a_graph(E, plan, n, xp, yp, what):
+    """four multiplies of an ell_alternate = 1 plan and a graph of three, as test_alternating_walk_and_graphs"""
+    dx, dy = E.DeviceBuffer(n).upload(xp), E.DeviceBuffer(n)
+    for k in range(4):
+        dy.upload(np.full(n, np.nan))
+        plan.spmv(dx.ptr, dy.ptr)
+        _sync(E)
+        assert_exact(dy.download(), yp, f"{what} multiply {k}")
+    g = plan.graph(dx.ptr, dy.ptr, 3)
+    for k in range(2):
+        dy.upload(np.full(n, np.nan))
+        g.launch()
+        _sync(E)
+        assert_exact(dy.download(), yp, f"{what} graph replay {k}")
+    g.destroy()
+    dx.free(), dy.free()
+
+
+@pytest.mark.parametrize("triples", [1, 2], ids=["triples1", "pair-form"])
+@pytest.mark.parametrize("threads", [256, 512, 1024])
+def test_inline_residual_with_symmetric_pairs_f32(E, O, gpu, threads, triples):
+    """ehyb_ell_f32_kernel<THREADS, true, true>, the arm that takes 128 VGPRs: no random configuration reaches it at 512 or 1024
+    threads and no named path at any size.  Integer values, tie values (the rounded reference), both walks, two phases, the
+    alternating walk and a graph."""
+    kw = dict(threads=threads, ell_triples=triples, ell_alternate=1, **FEM_INLINE_SYM)
+    cfg = E.make_config(val_f32=1, **kw)
+    c = ExactCase(E, O, FEM, cfg, symmetric=True)
+    plan = _checked_f32_plan(E, c.m, cfg, str(kw))
+    st = plan.stats
+    assert window_arm(cfg, st) == (threads, True, True) and st["sym_pairs"] > 0.25 * st["nnz"], st
+    coded = (_device_meta(plan)[:, 3] & 0x40) != 0
+    print(f"threads={threads} ell_triples={triples}: {int(coded.sum())} of {len(coded)} slabs triple-coded, er_inline={st['er_inline']}")
+    if triples == 2:
+        assert not coded.any()
+    all_ways(E, plan, c.xp, c.y_ref_p, f"{kw} integers")
+    _alternating_walk_and_a_graph(E, plan, c.n, c.xp, c.y_ref_p, f"{kw} integers")
+    plan.destroy()
+    t = TieCase(E, FEM, cfg, True)
+    plan = _checked_f32_plan(E, t.m, cfg, str(kw))
+    assert plan.stats == st and (t.y_full_p != t.y_rounded_p).mean() > 0.5
+    all_ways(E, plan, t.xp, t.y_rounded_p, f"{kw} ties")
+    _alternating_walk_and_a_graph(E, plan, t.n, t.xp, t.y_rounded_p, f"{kw} ties")
     plan.destroy()
 
 

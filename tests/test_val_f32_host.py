@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from test_gpu_exact import PATHS, RMAT14
-from val_f32_cases import SPECIALS, same_bits_f32, special_values
+from val_f32_cases import FALLBACK_MAX, FEM_INLINE_SYM, FUZZ_SEEDS, SPECIALS, fuzz_case_f32, same_bits_f32, special_values, window_arm
 
 _BY_NAME = {p[0]: p for p in PATHS}
 # FEM with plain storage (a residual of its own; one that rides inline behind the slabs' pairs), FEM with symmetric pairs, R-MAT
@@ -118,3 +118,45 @@ def test_panel_form_is_refused_at_upload_without_a_device(E):
     with pytest.raises(E.EhybError) as ei:
         plan.upload()
     assert ei.value.code == 1 and "val_f32" in str(ei.value) and "panel" in str(ei.value)
+
+
+# ------------------------------------------------------------------ what the fuzz seeds of test_gpu_val_f32.py reach
+def test_what_the_random_configurations_reach_with_val_f32(E, O):
+    """From host-only plans of the forty seeds: ten of the twelve ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> -- all but an inline
+    residual together with symmetric pairs at 512 and 1024 threads (test_inline_residual_with_symmetric_pairs_f32 has those) --,
+    split residual rows, the direct shape, matrices of up to five rows and without an entry; and how many seeds had to leave
+    the panel form their draw asked for."""
+    arms, fell_back, split, tiny, empty, direct = set(), [], 0, 0, 0, 0
+    for seed in FUZZ_SEEDS:
+        m, cfg, kw, x, y_ref, fb = fuzz_case_f32(E, O, seed)
+        plan = E.Plan(m, cfg, upload=False)
+        st = plan.stats
+        assert cfg.val_f32 == 1 and st["er_partials"] == 0 and st["nnz_ell"] + st["nnz_er"] == m.nnz, (seed, kw)
+        if fb:
+            fell_back.append(seed)
+        arms.add(window_arm(cfg, st))
+        split += bool((plan.array("er_seg_row") < 0).any())
+        tiny += m.n <= 5
+        empty += m.nnz == 0
+        direct += m.nnz > 0 and st["nnz_ell"] == 0
+        plan.destroy()
+    print(f"arms {sorted(a for a in arms if a)}, fell back {fell_back}, split rows in {split}, n <= 5 in {tiny}, empty {empty}, direct {direct}")
+    assert len(fell_back) <= FALLBACK_MAX, fell_back
+    want = {(256, i, s) for i in (False, True) for s in (False, True)} | {(t, i, s) for t in (512, 1024) for i, s in ((False, False), (False, True), (True, False))}
+    assert len(want) == 10 and want <= arms, sorted(want - arms)
+    assert split >= 1 and tiny >= 4 and empty == 6 and direct >= 1
+
+
+@pytest.mark.parametrize("threads", [256, 512, 1024])
+def test_the_named_plan_has_an_inline_residual_and_symmetric_pairs(E, threads):
+    """FEM_INLINE_SYM: what the named arms of test_gpu_val_f32.py launch, from the stats of a host-only plan"""
+    from test_gpu_exact import FEM
+
+    for triples in (1, 2):
+        cfg = E.make_config(val_f32=1, threads=threads, ell_triples=triples, **FEM_INLINE_SYM)
+        m = E.Matrix.generate(FEM[0], *FEM[1], cfg=cfg)
+        m.reorder(cfg)
+        plan = E.Plan(m, cfg, upload=False)
+        st = plan.stats
+        assert window_arm(cfg, st) == (threads, True, True) and st["sym_pairs"] > 0.25 * st["nnz"] and st["er_partials"] == 0, st
+        plan.destroy()

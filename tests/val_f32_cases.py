@@ -54,3 +54,30 @@ def same_bits_f32(got, want_f64):
         want = np.asarray(want_f64, dtype=np.float64).astype(np.float32)
     nan = np.isnan(want)
     return got.dtype == np.float32 and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+
+
+# ------------------------------------------------------------------ the random configurations of fuzz_cases.py with cfg.val_f32
+FUZZ_SEEDS = range(100, 140)      # those of test_gpu_exact.test_exact_random_plan
+FALLBACK_MAX = 4                  # seeds whose drawn configuration puts the residual in panel form (seen: 104 and 118)
+FEM_INLINE_SYM = dict(window_mode=2, sym_pairs=1, fuse_er=1, lds_doubles=1024)   # FEM of test_gpu_exact.py: an inline residual AND pairs
+
+
+def fuzz_case_f32(E, O, seed, **more):
+    """fuzz_cases.build(seed, exact=True, val_f32=1, **more) -> (matrix (reordered), cfg, kw, x, exact y, fell back).
+    cfg.val_f32 refuses a residual in panel form at upload, so a seed whose host-only plan has one is built again with
+    er_mode = 1 (CSR segments), which must remove it: `fell back`.  Nothing else of the draw changes."""
+    from fuzz_cases import build
+
+    for fell_back in (False, True):
+        m, cfg, kw, x, y_ref, _ = build(E, O, seed, exact=True, val_f32=1, **more, **(dict(er_mode=1) if fell_back else {}))
+        probe = E.Plan(m, cfg, upload=False)
+        panel = probe.stats["er_partials"] > 0
+        probe.destroy()
+        if not panel:
+            return m, cfg, kw, x, y_ref, fell_back
+    raise AssertionError(f"seed {seed}: er_mode = 1 left a residual in panel form")
+
+
+def window_arm(cfg, stats):
+    """which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> a plan's window launch is, None without a window launch"""
+    return (int(cfg.threads), stats["er_inline"] > 0, stats["sym_pairs"] > 0) if stats["nnz_ell"] > 0 else None
