@@ -25,6 +25,7 @@ from .host import (  # noqa: F401
     entry_order,
     host_threads,
     make_config,
+    minres_inv_diag,
     partition_graph,
     sizing,
     spmv_gpu_ehyb,

@@ -117,6 +117,21 @@ class BicgstabSlots(C.Structure):
         return {n: int(getattr(self, n)) for n in _BICGSTAB_SLOT_NAMES}
 
 
+_MINRES_SLOT_NAMES = [
+    "slots", "slot_doubles", "slot_bb", "slot_zq", "slot_beta0", "tail_doubles", "state_doubles",
+    "state_dbar", "state_eps", "state_phibar", "state_cs", "state_sn", "state_beta_old",
+    "flags_at", "flag_status", "flag_iters", "flag_count", "status_running", "status_converged", "status_breakdown",
+]
+
+
+class MinresSlots(C.Structure):
+    """ehyb_minres_slots (include/ehyb.h): the slot, state and flag layout behind the ehyb_minres_*_step building blocks"""
+    _fields_ = [(n, C.c_int32) for n in _MINRES_SLOT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in _MINRES_SLOT_NAMES}
+
+
 # every symbol include/*.h declares with C linkage: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -234,6 +249,13 @@ SIGNATURES = {
     "ehyb_bicgstab_dot2_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
     "ehyb_bicgstab_direction_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
+    "ehyb_minres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_minres_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_minres_layout": (C.c_int, [_P(MinresSlots)]),
+    "ehyb_minres_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ehyb_minres_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
+    "ehyb_minres_lanczos_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_minres_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

@@ -565,6 +565,20 @@ class Plan:
         The multiplies are as wide as spmm_max_k allows (build the plan with lds_doubles = 20480 // k)."""
         return self._solve("ehyb_bicgstab_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
+    def minres(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_minres: MINRES for a symmetric, possibly indefinite system on the device; inv_diag: an optional POSITIVE
+        diagonal preconditioner (minres_inv_diag gives 1 / |a_ii|); b, x0, inv_diag in the permuted numbering.
+        -> (x, iterations, relative residual phibar / sqrt(b.M^-1 b)).  A breakdown raises EhybError, unless allow_breakdown:
+        then x is the last good iterate and the counts are those of the device."""
+        return self._solve("ehyb_minres", b, x0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown)
+
+    def minres_multi(self, B, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_minres_multi: k independent MINRES solves that share the multiply of every iteration; B, X0 (k, n) in the
+        permuted numbering, column j solved as minres(B[j]) would -- with plain storage bit for bit.  -> (X (k, n), iterations
+        (k,), relative residuals (k,)), the counts those of the device.  A breakdown in any column raises EhybError, unless
+        allow_breakdown: then a broken column holds its last good iterate."""
+        return self._solve("ehyb_minres_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
+
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)
@@ -575,6 +589,12 @@ class Plan:
             self.destroy()
         except Exception:
             pass
+
+
+def minres_inv_diag(diag):
+    """The positive diagonal preconditioner of Plan.minres from the matrix's diagonal: 1 / |a_ii|, and 1 where a_ii = 0."""
+    d = np.abs(np.asarray(diag, dtype=np.float64))
+    return np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 1.0)
 
 
 def cheb_coeffs(lmin, lmax, degree):

@@ -1029,6 +1029,85 @@ int ehyb_bicgstab_update_step(int n, const double* p_dev, const double* sh_dev, 
 int ehyb_bicgstab_direction_step(int n, const double* r_dev, const double* v_dev, const double* inv_diag_dev, double* p_dev,
                                  double* s_dev, int cur, double thr, void* stream);
 
+/*
+ * MINRES (Paige-Saunders) for a SYMMETRIC, possibly indefinite A x = b on the plan's matrix, entirely on the device -- the
+ * solver for [H A^T; A 0] (ehyb_gen_kkt3d), where CG is not a method and BiCGSTAB pays two multiplies and can break down.  The
+ * matrix must be symmetric; as for ehyb_cg the library does not check.  It runs on symmetric pair storage (cfg.sym_pairs).
+ * inv_diag_dev: an optional POSITIVE diagonal preconditioner M^-1 = diag(inv_diag) in the permuted numbering -- MINRES needs an
+ * SPD preconditioner, so a caller passes 1 / |a_ii|, and 1 where a_ii = 0; NULL = none.  Arguments, stream, check_every and
+ * outputs as ehyb_bicgstab: x_dev holds the initial guess on entry and the solution on return, stream NULL = a private stream,
+ * check_every <= 0 = 10 (odd values rounded up to even), outputs may be NULL, the plan must cover all rows.
+ * Stored per column: x, two Lanczos residuals, two directions, z and q.  ra: the current residual, rb: the one before,
+ * z = M^-1 ra; start: ra = b - A x0, beta_1^2 = ra.z, bb = b.M^-1 b (0: 1 in its place), the carried state
+ * (dbar, eps, phibar, cs, sn, beta_old) = (0, 0, beta_1, -1, 0, 0).  Per iteration:
+ *   q = A z;  alpha = (z.q) / beta^2;  r_new = q / beta - (alpha / beta) ra - (beta / beta_old) rb  (written over rb; the rb term
+ *   is absent in the first iteration, which beta_old = 0 marks);  z = M^-1 r_new;  beta_new^2 = r_new.z
+ *   delta = cs dbar + sn alpha;  gbar = sn dbar - cs alpha;  eps' = sn beta_new;  dbar' = -cs beta_new;
+ *   gamma = sqrt(gbar^2 + beta_new^2);  cs' = gbar / gamma;  sn' = beta_new / gamma;  phi = cs' phibar;  phibar' = sn' phibar
+ *   v = M^-1 ra / beta;  w_new = (v - eps wb - delta wa) / gamma  (written over wb);  x += phi w_new;  beta_old' = beta
+ * and (ra, rb), (wa, wb) swap roles.  One multiply (walks alternating) and three vector kernels per iteration -- dot, lanczos,
+ * update --; an even and an odd iteration are replayed from one hipGraph (cfg.graphs = 2: plain launches; cfg.cg_fused_dot is
+ * ignored).  Sums are re-added from per-workgroup partials in a fixed order; the state is carried in two copies per column,
+ * one per parity: an iteration of parity c reads copy c and workgroup 0 of its update kernel writes copy c ^ 1, so no launch
+ * reads a word that it writes.  (beta_old is carried because beta_new^2 is written to the slot that held beta_old^2.)
+ * Stopping and breakdown are decided on the device, by the rules of ehyb_bicgstab.  Converged: phibar^2 <= rtol^2 bb; phibar is
+ * the recurrence for ||r|| in the M^-1 norm, the norm of bb (both 2-norms without a preconditioner), and rel_residual =
+ * phibar / sqrt(bb).  The test is made at the start (0 iterations) and after every update: the update kernel leaves the status
+ * alone, the dot kernel of the next iteration sees the same phibar and sets it, and at max_iter the host applies the same test
+ * to what it read.  Breakdown: a non-finite bb, beta_1^2, z.q, beta_new^2 or gamma, a negative beta^2 (the preconditioner is not
+ * positive), a beta_1^2 <= 0 or a zero gamma short of convergence -- the convergence test comes first.  (beta_new = 0 with
+ * gamma != 0 is the last update: phibar' = 0.)  The kernel that meets a breakdown changes nothing and every later one returns at
+ * once: x is the last iterate whose update had finite scalars, iters_done the device's counter.  With plain storage x, iters_done
+ * and rel_residual are the same bits for every check_every, for graphs and plain launches, for a given or a private stream, and
+ * from run to run.  A breakdown returns EHYB_ERR_ARG ("breakdown" in ehyb_last_error) after every output is written; so does a
+ * NaN in b or x0, with x unchanged.  EHYB_ERR_ARG for a null plan, b or x, max_iter < 0, a negative or NaN rtol or a plan not over
+ * all rows; EHYB_ERR_STATE on a plan never uploaded -- all before any device work.
+ *
+ * ehyb_minres_multi: k INDEPENDENT such solves that share the multiply (ehyb_spmm of the k columns of z) and run the three
+ * vector kernels up to four columns wide.  B, X, ldb, ldx, k, iters_done, rel_residual as ehyb_bicgstab_multi; every column has
+ * its own slots, state copies, status word and counter, and a column whose status is set is skipped by every vector kernel while
+ * the others go on.  With plain storage column j equals ehyb_minres on b_j bit for bit -- x, iters_done and rel_residual -- for
+ * every k, every check_every, graphs and plain launches, and whatever the other columns do, but for rows the residual splits
+ * into several segments (ehyb_spmm); with symmetric pair storage or a panel-form residual up to the order of summation.  If any
+ * column broke down the call returns EHYB_ERR_ARG after every output is written.  EHYB_ERR_ARG for k < 1, ldb or ldx < n, then
+ * what ehyb_minres rejects, in this order; then EHYB_ERR_STATE -- all before any device work.
+ *
+ * The four vector kernels as building blocks, one launch each with slot_doubles / 2 workgroups, as the ehyb_bicgstab_*_step
+ * calls.  s_dev: `slots` slots of `slot_doubles` doubles and tail_doubles more behind them: at double state_doubles * c +
+ * state_* of the tail the state of parity c, at double flags_at the two ints of the flags (flag_status, flag_iters).  beta^2
+ * number c (0/1) lives in slot slot_beta0 + c; cur (0/1, masked with & 1) is the parity of the iteration.  thr = rtol^2.
+ * Every step but init returns at once, writing nothing, when the status is not status_running on entry; a step that sets the
+ * status writes nothing else.
+ *   init     r = b - q, z = M^-1 r; partials of r.z (slot beta0) and of b.M^-1 b.  Takes no tail: the caller plants the first
+ *            state (phibar = sqrt of the sum of slot beta0) and the flags.
+ *   dot      phibar[cur]^2 <= thr bb (bb = 0: 1): converged.  Else partials of z.q
+ *   lanczos  a non-finite z.q, beta^2[cur] or alpha / beta, a beta^2[cur] <= 0, a non-finite beta / beta_old: breakdown.  Else
+ *            r_new over rb, z = M^-1 r_new, partials of beta^2[cur ^ 1]
+ *   update   the same conditions on z.q and beta^2[cur], a negative or non-finite beta^2[cur ^ 1], a zero or non-finite gamma,
+ *            a non-finite delta or phi: breakdown.  Else w_new over wb, x += phi w_new, state copy cur ^ 1, counter + 1
+ * All asynchronous on `stream`.
+ */
+int ehyb_minres(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, double* x_dev, int max_iter, double rtol,
+                int check_every, void* stream, int* iters_done, double* rel_residual);
+int ehyb_minres_multi(ehyb_plan* plan, const double* inv_diag_dev, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
+                      int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+typedef struct ehyb_minres_slots {
+    int32_t slots, slot_doubles;
+    int32_t slot_bb, slot_zq, slot_beta0;
+    int32_t tail_doubles, state_doubles;
+    int32_t state_dbar, state_eps, state_phibar, state_cs, state_sn, state_beta_old;
+    int32_t flags_at, flag_status, flag_iters, flag_count;
+    int32_t status_running, status_converged, status_breakdown;
+} ehyb_minres_slots;
+int ehyb_minres_layout(ehyb_minres_slots* out);
+int ehyb_minres_init_step(int n, const double* b_dev, const double* q_dev, const double* inv_diag_dev, double* r_dev, double* z_dev,
+                          double* s_dev, void* stream);
+int ehyb_minres_dot_step(int n, const double* z_dev, const double* q_dev, double* s_dev, int cur, double thr, void* stream);
+int ehyb_minres_lanczos_step(int n, const double* q_dev, const double* ra_dev, double* rb_dev, const double* inv_diag_dev,
+                             double* z_dev, double* s_dev, int cur, void* stream);
+int ehyb_minres_update_step(int n, const double* ra_dev, const double* inv_diag_dev, const double* wa_dev, double* wb_dev,
+                            double* x_dev, double* s_dev, int cur, void* stream);
+
 /* -------------------------------------------- harness pieces (solver_test.c) */
 
 /*
