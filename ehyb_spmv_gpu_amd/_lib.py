@@ -132,6 +132,22 @@ class MinresSlots(C.Structure):
         return {n: int(getattr(self, n)) for n in _MINRES_SLOT_NAMES}
 
 
+_GMRES_SLOT_NAMES = [
+    "slots", "slot_doubles", "slot_bb", "slot_ww", "slot_c0", "max_restart", "tail_doubles",
+    "flags_at", "flag_status", "flag_iters", "flag_count",
+    "cycle_at", "rho_at", "bb_at", "cs_at", "sn_at", "gt_at", "g_at", "h_at", "h_stride", "r_at", "r_stride",
+    "status_running", "status_converged", "status_breakdown",
+]
+
+
+class GmresSlots(C.Structure):
+    """ehyb_gmres_slots (include/ehyb.h): the slot and tail layout behind the ehyb_gmres_*_step building blocks"""
+    _fields_ = [(n, C.c_int32) for n in _GMRES_SLOT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in _GMRES_SLOT_NAMES}
+
+
 # every symbol include/*.h declares with C linkage: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -256,6 +272,13 @@ SIGNATURES = {
     "ehyb_minres_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
     "ehyb_minres_lanczos_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_minres_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
+    "ehyb_gmres_layout": (C.c_int, [_P(GmresSlots)]),
+    "ehyb_gmres_start_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_gmres_dots_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp]),
+    "ehyb_gmres_update_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "ehyb_gmres_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "ehyb_gmres_solve_x_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

@@ -1,0 +1,630 @@
+// Device-resident restarted GMRES(m) for unsymmetric systems on top of the EHYB plan (ehyb_gmres), right-preconditioned with
+// M = diag(A): the method for the systems on which ehyb_bicgstab breaks down or diverges.  Unlike every other solver here it
+// keeps a GROWING set of vectors: the Arnoldi basis V, column-major, m + 1 columns with a leading dimension of n rounded up
+// to even, so that every column is 16-byte aligned.  Beside it two fixed vectors: z = M^-1 v_j, the multiply's input, and w,
+// its output.
+//
+// A cycle: w = A x;  start: w = b - w, partials of w.w (= r.r) and b.b;  next(-1): v_0 = w / sqrt(r.r), z = M^-1 v_0;
+// then per step j = 0 .. m-1 one multiply and 2 * passes + 1 vector kernels
+//   w = A z                                                   (ehyb_spmv_walk, walks alternating)
+//   per pass:  dots    partials of c_i = v_i . w, i <= j, all from the same w: the columns in register groups of 8
+//              update  w -= sum c_i v_i;  workgroup 0: h_i (+)= c_i;  on the last pass the partials of w.w
+//   next(j)    h_{j+1} = sqrt(w.w); the Hessenberg column through the rotations 0 .. j-1, the new rotation, g, the counter
+//              and the stop tests;  v_{j+1} = w / h_{j+1},  z = M^-1 v_{j+1}
+// and at the end  solve_x: R y = g by back substitution, x += M^-1 (sum y_i v_i) over the J steps the device counted.
+// The host knows j for every launch of a cycle, so j and the column count are kernel arguments and a whole cycle is one linear
+// hipGraph, replayed per cycle; a last partial cycle is issued as plain launches.  The host looks once per cycle.
+//
+// Sums come from per-workgroup partials re-added in a fixed order (vec_reduce.h); no atomics.  What no sum gives back lives in
+// the tail behind the slots: the rotations cs, sn, R (64 x 64, column-major), g~ (the unrotated right-hand side, g~_0 = beta)
+// and g (the rotated one), one Hessenberg column per pass, rho, b.b, and three ints: status, counter, the counter at the cycle
+// start.  Every workgroup of next() makes the whole decision for itself from the same words (so all take the same branch) and
+// workgroup 0 alone writes the tail -- always to words that the launch does not read: step j reads cs, sn of i < j and g~_j and
+// writes cs_j, sn_j, g_j, g~_{j+1} and column j of R; pass p of update reads Hessenberg copy p - 1 and writes copy p.  (The one
+// exception is the house's: the counter, which only workgroup 0 touches.)  Once the status is set every kernel but solve_x
+// returns at once; solve_x applies the steps counted in the cycle whatever the status.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "ehyb_internal.h"
+#include "solve_loop.h"
+
+using namespace ehyb;
+
+namespace {
+
+constexpr int kM = EHYB_GMRES_MAX_RESTART;  // steps per cycle at most
+constexpr int kCols = kM + 1;               // basis columns at most
+constexpr int kGroup = 8;                   // basis columns per register group
+
+// partial slots, kMaxGrid doubles each; c_i lives in slot G_C0 + i.  G_WW holds r.r after start and w.w after the last update.
+enum { G_BB = 0, G_WW = 1, G_C0 = 2, G_COUNT = G_C0 + kCols };
+// the tail, in doubles.  T_FLAGS: the ints status and counter; T_CYCLE: the int counter at the cycle start.
+enum {
+    T_FLAGS = 0,
+    T_CYCLE = 1,
+    T_RHO = 2,
+    T_BB = 3,
+    T_CS = 4,
+    T_SN = T_CS + kM,
+    T_GT = T_SN + kM,
+    T_G = T_GT + kCols,
+    T_H = T_G + kM,
+    T_R = T_H + 2 * kCols,
+    T_COUNT = T_R + kM * kM
+};
+enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
+enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
+// what next() decides: go on; converged (counted, but for j = -1); breakdown before the step counts; breakdown after it counted
+enum { D_GO = 0, D_CONVERGED = 1, D_BREAK_EARLY = 2, D_BREAK_COUNTED = 3 };
+
+__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+
+__device__ __forceinline__ double* gslot(double* s, int which) { return s + (size_t)which * kMaxGrid; }
+__device__ __forceinline__ const double* gslot(const double* s, int which) { return s + (size_t)which * kMaxGrid; }
+
+// the status as the workgroup found it on entry, the same in every thread (workgroup 0 of the launch may set it later)
+__device__ __forceinline__ bool running(const double* tail)
+{
+    __shared__ int st;
+    if (threadIdx.x == 0) st = __atomic_load_n(&((const int*)(tail + T_FLAGS))[F_STATUS], __ATOMIC_RELAXED);
+    __syncthreads();
+    return uniform(st == ST_RUNNING);
+}
+
+__device__ __forceinline__ double2 load2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+__device__ __forceinline__ void store2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
+
+// ------------------------------------------------------------------ the vector kernels
+// Every kernel but start walks PAIRS of elements: pair p = (2p, 2p + 1) with p = block * 256 + thread, stride grid * 256, one
+// 16-byte access per vector and pair; for an odd n the last element is a pair of one and goes through 8-byte accesses.
+
+// w = b - w (w = A x on entry); partials of w.w and b.b
+__global__ __launch_bounds__(kThreads) void gmres_start_kernel(int n, const double* __restrict__ b, double* __restrict__ w,
+                                                               double* __restrict__ s, const double* tail)
+{
+    if (!running(tail)) return;
+    double sums[2] = {0.0, 0.0};
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const double bi = b[i], ri = bi - w[i];
+        w[i] = ri;
+        sums[0] = fma(ri, ri, sums[0]);
+        sums[1] = fma(bi, bi, sums[1]);
+    }
+    block_sum_n(sums);
+    if (threadIdx.x == 0) {
+        gslot(s, G_WW)[blockIdx.x] = sums[0];
+        gslot(s, G_BB)[blockIdx.x] = sums[1];
+    }
+}
+
+// one register group: columns g0 .. g0 + m - 1 (m <= 8; FULL: m = 8, no tests in the loop) against w
+template <bool FULL>
+__device__ __forceinline__ void dots_group(int n, size_t ld, const double* __restrict__ V, const double* __restrict__ w, int g0, int m,
+                                           double* __restrict__ s)
+{
+    double acc[kGroup];
+#pragma unroll
+    for (int c = 0; c < kGroup; ++c) acc[c] = 0.0;
+    const double* v0 = V + (size_t)g0 * ld;
+    const int stride = (int)gridDim.x * kThreads;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        if (i + 1 < (size_t)n) {
+            const double2 wv = load2(w + i);
+            double2 vv[kGroup];
+#pragma unroll
+            for (int c = 0; c < kGroup; ++c)
+                if (FULL || c < m) vv[c] = load2(v0 + (size_t)c * ld + i);
+#pragma unroll
+            for (int c = 0; c < kGroup; ++c)
+                if (FULL || c < m) acc[c] = fma(vv[c].y, wv.y, fma(vv[c].x, wv.x, acc[c]));
+        } else {
+            const double wi = w[i];
+#pragma unroll
+            for (int c = 0; c < kGroup; ++c)
+                if (FULL || c < m) acc[c] = fma(v0[(size_t)c * ld + i], wi, acc[c]);
+        }
+    }
+    block_sum_n(acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < kGroup; ++c)
+            if (FULL || c < m) gslot(s, G_C0 + g0 + c)[blockIdx.x] = acc[c];
+    }
+}
+
+// partials of c_i = v_i . w for i < cnt
+__global__ __launch_bounds__(kThreads) void gmres_dots_kernel(int n, long long ld, const double* __restrict__ V, const double* __restrict__ w,
+                                                              int cnt, double* __restrict__ s, const double* tail)
+{
+    if (!running(tail)) return;
+    int g0 = 0;
+    for (; g0 + kGroup <= cnt; g0 += kGroup) dots_group<true>(n, (size_t)ld, V, w, g0, kGroup, s);
+    if (g0 < cnt) dots_group<false>(n, (size_t)ld, V, w, g0, cnt - g0, s);
+}
+
+// w -= sum_{i < cnt} c_i v_i with c_i re-added from the partials; workgroup 0: Hessenberg copy `pass` = copy pass - 1 + c
+// (pass 0: c); last: the partials of w.w
+__global__ __launch_bounds__(kThreads) void gmres_update_kernel(int n, long long ld_, const double* __restrict__ V, double* __restrict__ w,
+                                                                int cnt, double* __restrict__ s, double* tail, int pass, int last)
+{
+    if (!running(tail)) return;
+    __shared__ double c_sh[kCols + kGroup];
+    for (int g0 = 0; g0 < cnt; g0 += kGroup) {
+        double sums[kGroup];
+#pragma unroll
+        for (int c = 0; c < kGroup; ++c) sums[c] = g0 + c < cnt ? partials_of(gslot(s, G_C0 + g0 + c)) : 0.0;
+        block_sum_n(sums);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int c = 0; c < kGroup; ++c) c_sh[g0 + c] = sums[c];
+        }
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && (int)threadIdx.x < cnt) {
+        const double c = c_sh[threadIdx.x];
+        tail[T_H + pass * kCols + threadIdx.x] = pass > 0 ? tail[T_H + (pass - 1) * kCols + threadIdx.x] + c : c;
+    }
+    const size_t ld = (size_t)ld_;
+    const int stride = (int)gridDim.x * kThreads;
+    double ww = 0.0;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        if (i + 1 < (size_t)n) {
+            double2 wv = load2(w + i);
+            int c0 = 0;
+            for (; c0 + kGroup <= cnt; c0 += kGroup) {
+                double2 vv[kGroup];
+#pragma unroll
+                for (int c = 0; c < kGroup; ++c) vv[c] = load2(V + (size_t)(c0 + c) * ld + i);
+#pragma unroll
+                for (int c = 0; c < kGroup; ++c) {
+                    const double ci = c_sh[c0 + c];
+                    wv.x = fma(-ci, vv[c].x, wv.x);
+                    wv.y = fma(-ci, vv[c].y, wv.y);
+                }
+            }
+            for (; c0 < cnt; ++c0) {
+                const double2 v = load2(V + (size_t)c0 * ld + i);
+                const double ci = c_sh[c0];
+                wv.x = fma(-ci, v.x, wv.x);
+                wv.y = fma(-ci, v.y, wv.y);
+            }
+            store2(w + i, wv);
+            ww = fma(wv.y, wv.y, fma(wv.x, wv.x, ww));
+        } else {
+            double wi = w[i];
+            for (int c0 = 0; c0 < cnt; ++c0) wi = fma(-c_sh[c0], V[(size_t)c0 * ld + i], wi);
+            w[i] = wi;
+            ww = fma(wi, wi, ww);
+        }
+    }
+    if (last) put_partial(ww, gslot(s, G_WW));
+}
+
+// j = -1, the cycle start: w.w = r.r and b.b from the partials; a non-finite one: breakdown; r.r <= thr bb: converged; else
+// beta = sqrt(r.r), g~_0 = beta, v_0 = w / beta.  Workgroup 0 also notes the counter at the cycle start, rho = r.r and bb.
+// j >= 0: h_{j+1} = sqrt(w.w); h_0 .. h_j from Hessenberg copy passes - 1; a non-finite h: breakdown.  The rotations 0 .. j-1 on
+// the column, gamma = hypot(h_j, h_{j+1}); zero or non-finite: breakdown.  cs_j, sn_j, column j of R, g~_{j+1} = -sn_j g~_j,
+// g_j = cs_j g~_j, rho = g~_{j+1}^2, counter + 1.  Then g~_{j+1}^2 <= thr bb: converged; the unrotated h_{j+1} = 0: breakdown;
+// else v_{j+1} = w / h_{j+1}.  With every new v: z = M^-1 v.
+__global__ __launch_bounds__(kThreads) void gmres_next_kernel(int n, long long ld_, double* __restrict__ V, const double* __restrict__ w,
+                                                              const double* __restrict__ dinv, double* __restrict__ z,
+                                                              const double* __restrict__ s, double* tail, int j, int passes, double thr)
+{
+    if (!running(tail)) return;
+    double sums[2];
+    sums[0] = partials_of(gslot(s, G_WW));
+    sums[1] = j < 0 ? partials_of(gslot(s, G_BB)) : 0.0;
+    block_sum_n(sums);
+    __shared__ double h_sh[kCols], cs_sh[kM], sn_sh[kM], out_sh[8];
+    __shared__ int code_sh;
+    if (j >= 0) {
+        const int t = threadIdx.x;
+        if (t <= j) h_sh[t] = tail[T_H + (passes - 1) * kCols + t];
+        if (t < j) {
+            cs_sh[t] = tail[T_CS + t];
+            sn_sh[t] = tail[T_SN + t];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int code = D_GO;
+        const double ww = sums[0];
+        double hn = sqrt(ww), gamma = 0.0, cs = 0.0, sn = 0.0, gfin = 0.0, gnext = 0.0, bb = 0.0;
+        if (j < 0) {
+            const double bb0 = sums[1];
+            bb = bb0 > 0 ? bb0 : (bb0 == 0 ? 1.0 : bb0);
+            if (!isfinite(bb0) || !isfinite(ww))
+                code = D_BREAK_EARLY;
+            else if (ww <= thr * bb)
+                code = D_CONVERGED;
+        } else {
+            bool finite = isfinite(ww);
+            for (int i = 0; i <= j; ++i) finite = finite && isfinite(h_sh[i]);
+            if (!finite) {
+                code = D_BREAK_EARLY;
+            } else {
+                for (int i = 0; i < j; ++i) {
+                    const double a = h_sh[i], b = h_sh[i + 1], t = fma(cs_sh[i], a, sn_sh[i] * b);
+                    h_sh[i + 1] = fma(-sn_sh[i], a, cs_sh[i] * b);
+                    h_sh[i] = t;
+                }
+                gamma = hypot(h_sh[j], hn);
+                if (gamma == 0 || !isfinite(gamma)) {
+                    code = D_BREAK_EARLY;
+                } else {
+                    cs = h_sh[j] / gamma;
+                    sn = hn / gamma;
+                    const double gt = tail[T_GT + j];
+                    gnext = -sn * gt;
+                    gfin = cs * gt;
+                    bb = tail[T_BB];
+                    if (gnext * gnext <= thr * bb)
+                        code = D_CONVERGED;
+                    else if (hn == 0)
+                        code = D_BREAK_COUNTED;
+                }
+            }
+        }
+        out_sh[0] = hn;
+        out_sh[1] = gamma;
+        out_sh[2] = cs;
+        out_sh[3] = sn;
+        out_sh[4] = gfin;
+        out_sh[5] = gnext;
+        out_sh[6] = bb;
+        code_sh = code;
+    }
+    __syncthreads();
+    const int code = __builtin_amdgcn_readfirstlane(code_sh);
+    const double hn = out_sh[0];
+    if (blockIdx.x == 0) {
+        int* flags = (int*)(tail + T_FLAGS);
+        if (j >= 0 && code != D_BREAK_EARLY) {
+            if ((int)threadIdx.x < j) tail[T_R + (size_t)j * kM + threadIdx.x] = h_sh[threadIdx.x];
+            if (threadIdx.x == 0) {
+                tail[T_R + (size_t)j * kM + j] = out_sh[1];
+                tail[T_CS + j] = out_sh[2];
+                tail[T_SN + j] = out_sh[3];
+                tail[T_G + j] = out_sh[4];
+                tail[T_GT + j + 1] = out_sh[5];
+                tail[T_RHO] = out_sh[5] * out_sh[5];
+                flags[F_ITERS] += 1;
+            }
+        }
+        if (threadIdx.x == 0) {
+            if (j < 0) {
+                ((int*)(tail + T_CYCLE))[0] = flags[F_ITERS];
+                tail[T_RHO] = sums[0];
+                tail[T_BB] = out_sh[6];
+                if (code == D_GO) tail[T_GT] = hn;
+            }
+            if (code != D_GO) __atomic_store_n(&flags[F_STATUS], code == D_CONVERGED ? ST_CONVERGED : ST_BREAKDOWN, __ATOMIC_RELAXED);
+        }
+    }
+    if (code != D_GO) return;
+    const size_t ld = (size_t)ld_;
+    double* v = V + (size_t)(j + 1) * ld;
+    const int stride = (int)gridDim.x * kThreads;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        if (i + 1 < (size_t)n) {
+            const double2 wv = load2(w + i);
+            double2 vv;
+            vv.x = wv.x / hn;
+            vv.y = wv.y / hn;
+            store2(v + i, vv);
+            if (dinv) {
+                const double2 d = load2(dinv + i);
+                vv.x *= d.x;
+                vv.y *= d.y;
+            }
+            store2(z + i, vv);
+        } else {
+            const double vi = w[i] / hn;
+            v[i] = vi;
+            z[i] = dinv ? vi * dinv[i] : vi;
+        }
+    }
+}
+
+// J = counter - counter at the cycle start; R y = g[0 .. J) by back substitution (column by column, every workgroup for itself,
+// the same order in each); x += M^-1 (sum_{i < J} y_i v_i), the sum in rising i.  Does not look at the status: the steps before
+// a stop are applied.
+__global__ __launch_bounds__(kThreads) void gmres_solve_x_kernel(int n, long long ld_, const double* __restrict__ V,
+                                                                 const double* __restrict__ dinv, double* __restrict__ x,
+                                                                 const double* __restrict__ tail)
+{
+    __shared__ double r_sh[kM * kM], g_sh[kM], y_sh[kM];
+    __shared__ int j_sh;
+    if (threadIdx.x == 0) j_sh = ((const int*)(tail + T_FLAGS))[F_ITERS] - ((const int*)(tail + T_CYCLE))[0];
+    __syncthreads();
+    const int J = __builtin_amdgcn_readfirstlane(j_sh);
+    if (J <= 0 || J > kM) return;
+    for (int k = threadIdx.x; k < J * kM; k += kThreads) r_sh[k] = tail[T_R + k];
+    if ((int)threadIdx.x < J) g_sh[threadIdx.x] = tail[T_G + threadIdx.x];
+    __syncthreads();
+    for (int i = J - 1; i >= 0; --i) {
+        const double yi = g_sh[i] / r_sh[i * kM + i];
+        if ((int)threadIdx.x < i) g_sh[threadIdx.x] = fma(-r_sh[i * kM + threadIdx.x], yi, g_sh[threadIdx.x]);
+        if ((int)threadIdx.x == kThreads - 1) y_sh[i] = yi;
+        __syncthreads();
+    }
+    const size_t ld = (size_t)ld_;
+    const int stride = (int)gridDim.x * kThreads;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        if (i + 1 < (size_t)n) {
+            double2 acc = {0.0, 0.0};
+            int c0 = 0;
+            for (; c0 + kGroup <= J; c0 += kGroup) {
+                double2 vv[kGroup];
+#pragma unroll
+                for (int c = 0; c < kGroup; ++c) vv[c] = load2(V + (size_t)(c0 + c) * ld + i);
+#pragma unroll
+                for (int c = 0; c < kGroup; ++c) {
+                    const double yi = y_sh[c0 + c];
+                    acc.x = fma(yi, vv[c].x, acc.x);
+                    acc.y = fma(yi, vv[c].y, acc.y);
+                }
+            }
+            for (; c0 < J; ++c0) {
+                const double2 v = load2(V + (size_t)c0 * ld + i);
+                acc.x = fma(y_sh[c0], v.x, acc.x);
+                acc.y = fma(y_sh[c0], v.y, acc.y);
+            }
+            if (dinv) {
+                const double2 d = load2(dinv + i);
+                acc.x *= d.x;
+                acc.y *= d.y;
+            }
+            double2 xv = load2(x + i);
+            xv.x += acc.x;
+            xv.y += acc.y;
+            store2(x + i, xv);
+        } else {
+            double acc = 0.0;
+            for (int c0 = 0; c0 < J; ++c0) acc = fma(y_sh[c0], V[(size_t)c0 * ld + i], acc);
+            if (dinv) acc *= dinv[i];
+            x[i] += acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the driver
+struct DeviceArray {
+    double* p = nullptr;
+    ~DeviceArray()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
+struct CycleGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    ~CycleGraph()
+    {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+};
+
+struct Launcher {
+    int grid, n;
+    long long ld;
+    hipStream_t st;
+    double *V, *w, *z, *s, *tail;
+    const double* dinv;
+
+    void start(const double* b) const { hipLaunchKernelGGL(gmres_start_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, w, s, tail); }
+    void dots(int cnt) const { hipLaunchKernelGGL(gmres_dots_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, cnt, s, tail); }
+    void update(int cnt, int pass, int last) const
+    {
+        hipLaunchKernelGGL(gmres_update_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, cnt, s, tail, pass, last);
+    }
+    void next(int j, int passes, double thr) const
+    {
+        hipLaunchKernelGGL(gmres_next_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, dinv, z, s, tail, j, passes, thr);
+    }
+    void solve_x(double* x) const { hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, dinv, x, tail); }
+};
+
+int gmres_solve(ehyb_plan* P, const double* dinv, const double* b, double* x, int m, int passes, int max_iter, double rtol, void* stream,
+                int* iters_done, double* rel_residual)
+{
+    const int n = P->host.n_cols;
+    const size_t ld = (size_t)n + (n & 1);
+    SolveLoop L(n, 0);
+    double *w, *z, *s;
+    HIP_TRY(L.begin(stream, {&w, &z}, ld, &s, G_COUNT, T_COUNT));
+    DeviceArray V;
+    HIP_TRY(hipMalloc((void**)&V.p, std::max<size_t>(1, ld * (size_t)(m + 1)) * sizeof(double)));
+    const hipStream_t st = L.st;
+    double* tail = s + (size_t)G_COUNT * kMaxGrid;
+    const Launcher K{L.grid, n, (long long)ld, st, V.p, w, z, s, tail, dinv};
+    const double thr = rtol * rtol;
+    HIP_TRY(hipMemsetAsync(tail, 0, (size_t)T_COUNT * sizeof(double), st));
+
+    // one cycle of `steps` steps; the multiplies walk last to first, then alternate
+    auto cycle = [&](int steps) -> int {
+        int rc = ehyb_spmv_walk(P, x, w, st, EHYB_WALK_LAST_TO_FIRST);
+        if (rc != EHYB_OK) return rc;
+        K.start(b);
+        K.next(-1, passes, thr);
+        for (int j = 0; j < steps; ++j) {
+            rc = ehyb_spmv_walk(P, z, w, st, j & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
+            if (rc != EHYB_OK) return rc;
+            for (int p = 0; p < passes; ++p) {
+                K.dots(j + 1);
+                K.update(j + 1, p, p == passes - 1);
+            }
+            K.next(j, passes, thr);
+        }
+        K.solve_x(x);
+        return EHYB_OK;
+    };
+
+    // a full cycle is captured once and replayed; cfg.graphs = 2 keeps the plain launches, and so does a capture that fails
+    CycleGraph G;
+    if (P->cfg.graphs != 2 && max_iter >= m && hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        const int erc = cycle(m);
+        const hipError_t eend = hipStreamEndCapture(st, &G.graph);
+        if (erc != EHYB_OK || eend != hipSuccess || hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess) G.exec = nullptr;
+        (void)hipGetLastError();
+    }
+    double head[4] = {0, 0, 0, 0};  // flags, cycle, rho, bb as the device left them
+    int f[F_COUNT] = {ST_RUNNING, 0};
+    int issued = 0;
+    do {
+        const int steps = std::min(m, max_iter - issued);
+        if (steps == m && G.exec) {
+            HIP_TRY(hipGraphLaunch(G.exec, st));
+        } else {
+            const int rc = cycle(steps);
+            if (rc != EHYB_OK) return rc;
+        }
+        issued += steps;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(head, tail, sizeof(head), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(f, &head[T_FLAGS], sizeof(f));
+    } while (f[F_STATUS] == ST_RUNNING && issued < max_iter);
+    if (iters_done) *iters_done = f[F_ITERS];
+    if (rel_residual) *rel_residual = std::sqrt(head[T_RHO] / head[T_BB]);
+    if (f[F_STATUS] != ST_BREAKDOWN) return EHYB_OK;
+    EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres: breakdown after %d iterations (a non-finite b.b, r.r or Hessenberg entry, a zero or non-finite gamma, "
+                            "or h_{j+1} = 0 short of convergence: a singular system)",
+              f[F_ITERS]);
+}
+
+}  // namespace
+
+extern "C" int ehyb_gmres(ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes, int max_iter,
+                          double rtol, void* stream, int* iters_done, double* rel_residual)
+{
+    int rc = solve_args("ehyb_gmres", P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    if (restart < 0 || restart > kM || ortho_passes < 0 || ortho_passes > 2)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres: restart %d (0 .. %d), ortho_passes %d (0 .. 2)", restart, kM, ortho_passes);
+    if ((rc = solve_uploaded("ehyb_gmres", P)) != EHYB_OK) return rc;
+    return gmres_solve(P, dinv, b, x, restart == 0 ? 30 : restart, ortho_passes == 1 ? 1 : 2, max_iter, rtol, stream, iters_done,
+                       rel_residual);
+}
+
+// ------------------------------------------------------------------ building blocks for a caller that owns the loop
+// The five vector kernels one launch each, for a caller that issues the multiplies itself (and for tests that look at one kernel
+// at a time) -- the analogue of ehyb_minres_*_step.  s: `slots` slots of `slot_doubles` doubles and tail_doubles more behind them
+// (ehyb_gmres_layout); every launch uses slot_doubles / 2 workgroups.  Asynchronous on `stream`.
+extern "C" int ehyb_gmres_layout(ehyb_gmres_slots* out)
+{
+    if (!out) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres_layout: null argument");
+    out->slots = G_COUNT;
+    out->slot_doubles = kMaxGrid;
+    out->slot_bb = G_BB;
+    out->slot_ww = G_WW;
+    out->slot_c0 = G_C0;
+    out->max_restart = kM;
+    out->tail_doubles = T_COUNT;
+    out->flags_at = T_FLAGS;
+    out->flag_status = F_STATUS;
+    out->flag_iters = F_ITERS;
+    out->flag_count = F_COUNT;
+    out->cycle_at = T_CYCLE;
+    out->rho_at = T_RHO;
+    out->bb_at = T_BB;
+    out->cs_at = T_CS;
+    out->sn_at = T_SN;
+    out->gt_at = T_GT;
+    out->g_at = T_G;
+    out->h_at = T_H;
+    out->h_stride = kCols;
+    out->r_at = T_R;
+    out->r_stride = kM;
+    out->status_running = ST_RUNNING;
+    out->status_converged = ST_CONVERGED;
+    out->status_breakdown = ST_BREAKDOWN;
+    return EHYB_OK;
+}
+
+namespace {
+
+constexpr int kStepGrid = kMaxGrid / 2;
+
+inline double* step_tail(double* s) { return s + (size_t)G_COUNT * kMaxGrid; }
+
+// the basis and the vectors walked in pairs: an even leading dimension >= n and 16-byte aligned pointers (NULL passes: the
+// caller lists what it requires in check_step)
+inline int check_pairs(const char* who, int n, int64_t ld, std::initializer_list<const void*> aligned)
+{
+    bool ok = ld >= n && (ld & 1) == 0;
+    for (const void* a : aligned) ok = ok && ((uintptr_t)a & 15) == 0;
+    if (!ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: the leading dimension must be even and >= n, the vectors 16-byte aligned", who);
+    return EHYB_OK;
+}
+
+}  // namespace
+
+extern "C" int ehyb_gmres_start_step(int n, const double* b, double* w, double* s, void* stream)
+{
+    const int rc = check_step("ehyb_gmres_start_step", n, {b, w, s});
+    if (rc != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_start_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, b, w, s, step_tail(s));
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_gmres_dots_step(int n, int64_t ld, const double* V, const double* w, int count, double* s, void* stream)
+{
+    int rc = check_step("ehyb_gmres_dots_step", n, {V, w, s});
+    if (rc != EHYB_OK) return rc;
+    if (count < 1 || count > kCols) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres_dots_step: bad arguments (count %d, 1 .. %d)", count, kCols);
+    if ((rc = check_pairs("ehyb_gmres_dots_step", n, ld, {V, w})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_dots_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, w, count, s,
+                       step_tail(s));
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_gmres_update_step(int n, int64_t ld, const double* V, double* w, int count, double* s, int pass, int last, void* stream)
+{
+    int rc = check_step("ehyb_gmres_update_step", n, {V, w, s});
+    if (rc != EHYB_OK) return rc;
+    if (count < 1 || count > kCols || pass < 0 || pass > 1)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres_update_step: bad arguments (count %d, 1 .. %d; pass %d, 0 or 1)", count, kCols, pass);
+    if ((rc = check_pairs("ehyb_gmres_update_step", n, ld, {V, w})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_update_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, w, count, s,
+                       step_tail(s), pass, last != 0);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_gmres_next_step(int n, int64_t ld, double* V, const double* w, const double* dinv, double* z, double* s, int j,
+                                    int passes, double thr, void* stream)
+{
+    int rc = check_step("ehyb_gmres_next_step", n, {V, w, z, s});
+    if (rc != EHYB_OK) return rc;
+    if (j < -1 || j >= kM || passes < 1 || passes > 2)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres_next_step: bad arguments (j %d, -1 .. %d; passes %d, 1 or 2)", j, kM - 1, passes);
+    if ((rc = check_pairs("ehyb_gmres_next_step", n, ld, {V, w, dinv, z})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_next_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, w, dinv, z, s,
+                       step_tail(s), j, passes, thr);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_gmres_solve_x_step(int n, int64_t ld, const double* V, const double* dinv, double* x, double* s, void* stream)
+{
+    int rc = check_step("ehyb_gmres_solve_x_step", n, {V, x, s});
+    if (rc != EHYB_OK) return rc;
+    if ((rc = check_pairs("ehyb_gmres_solve_x_step", n, ld, {V, dinv, x})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, dinv, x,
+                       step_tail(s));
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}

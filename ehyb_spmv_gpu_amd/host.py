@@ -579,6 +579,14 @@ class Plan:
         allow_breakdown: then a broken column holds its last good iterate."""
         return self._solve("ehyb_minres_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
+    def gmres(self, b, x0=None, restart=30, ortho_passes=2, max_iter=1000, rtol=1e-10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_gmres: restarted GMRES(restart) for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag
+        is given -- for the systems on which bicgstab breaks down or diverges; restart 0 = 30, at most 64; ortho_passes 1 or 2
+        (classical Gram-Schmidt once or twice); b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative
+        residual).  A breakdown raises EhybError, unless allow_breakdown: then x is the last good iterate and the counts are
+        those of the device."""
+        return self._solve("ehyb_gmres", b, x0, inv_diag, (int(restart), int(ortho_passes), max_iter, rtol), stream, allow_breakdown)
+
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)

@@ -1108,6 +1108,82 @@ int ehyb_minres_lanczos_step(int n, const double* q_dev, const double* ra_dev, d
 int ehyb_minres_update_step(int n, const double* ra_dev, const double* inv_diag_dev, const double* wa_dev, double* wb_dev,
                             double* x_dev, double* s_dev, int cur, void* stream);
 
+/*
+ * Restarted GMRES(restart) for a general (unsymmetric) A x = b on the plan's matrix, entirely on the device, right-preconditioned
+ * with M = diag(A) -- the solver for the systems on which ehyb_bicgstab breaks down or diverges: its residual never grows, and it
+ * breaks down only on a singular system.  inv_diag_dev, b_dev, x_dev, stream and the outputs as ehyb_bicgstab: inv_diag_dev NULL =
+ * no preconditioner, x_dev holds the initial guess on entry and the solution on return, stream NULL = a private stream, outputs may
+ * be NULL, the plan must cover all rows.  restart: 0 = 30, else 1 .. EHYB_GMRES_MAX_RESTART.  ortho_passes: 0 or 2 = classical
+ * Gram-Schmidt applied twice (the default), 1 = one pass.  There is no check_every: the host looks once per restart cycle.
+ * Stored: the basis V, column-major, restart + 1 columns with a leading dimension of n rounded up to even; z = M^-1 v_j, the
+ * multiply's input; w, its output.  bb = b.b (0: 1 in its place), thr = rtol^2; every rule is decided on the device.
+ *   Cycle start: w = A x; w = b - w; rr = w.w.  A non-finite bb or rr: breakdown (x unchanged if this is the first cycle).
+ *     rr <= thr bb: converged.  Else beta = sqrt(rr), v_0 = w / beta, g~_0 = beta.
+ *   Step j = 0 .. restart - 1: w = A (M^-1 v_j).  Per pass: c_i = v_i.w for i <= j, all from the same w; w -= sum c_i v_i;
+ *     h_i += c_i.  h_{j+1} = sqrt(w.w).  Any non-finite h: breakdown.  The rotations i = 0 .. j-1 on the column:
+ *     t = cs_i h_i + sn_i h_{i+1}; h_{i+1} = -sn_i h_i + cs_i h_{i+1}; h_i = t.  gamma = hypot(h_j, h_{j+1}); zero or non-finite:
+ *     breakdown.  cs_j = h_j / gamma, sn_j = h_{j+1} / gamma, R[0 .. j, j] = (h_0 .. h_{j-1}, gamma), g~_{j+1} = -sn_j g~_j,
+ *     g_j = cs_j g~_j; the step counts (counter + 1).  Then, in this order: g~_{j+1}^2 <= thr bb: converged; the unrotated
+ *     h_{j+1} = 0: breakdown (a singular system); else v_{j+1} = w / h_{j+1}, a true division.
+ *   Cycle end -- after `restart` steps, at convergence, at a breakdown, or when the counter reaches max_iter --, with J steps
+ *     counted in the cycle: R y = g[0 .. J) by back substitution, x += M^-1 (sum y_i v_i).  Steps before a breakdown are applied:
+ *     x is always the last iterate with finite scalars.
+ * iters_done is the device's counter (never above max_iter), rel_residual = sqrt(rho / bb) with rho the latest of rr at a cycle
+ * start and g~_{j+1}^2 after a step.  A breakdown, or a NaN in b or x0 (x then unchanged), returns EHYB_ERR_ARG ("breakdown" in
+ * ehyb_last_error) after every output is written.
+ * One multiply (walks alternating) and 2 * passes + 1 vector kernels per step -- dots, update per pass, then next.  The host knows
+ * j for every launch of a cycle, so a whole cycle is captured once as a linear hipGraph and replayed per cycle (cfg.graphs = 2:
+ * plain launches); a last partial cycle, when max_iter is not a multiple of restart, is issued as plain launches.  After a stop
+ * inside a cycle the remaining vector kernels of the cycle return at once; its multiplies still run.  Sums are re-added from
+ * per-workgroup partials in a fixed order, no atomics; no launch reads a word that it writes (but the counter, which one
+ * workgroup owns); the rotation state is written by one workgroup only.  With plain storage x, iters_done and rel_residual are
+ * the same bits from run to run, for a given or a private stream, and for graphs and plain launches; with symmetric pair storage
+ * or a panel-form residual up to the order of summation.  The solver only calls the multiply, so every plan form works.
+ * EHYB_ERR_ARG for what ehyb_bicgstab rejects, in its order (a null plan, b or x, max_iter < 0, a negative or NaN rtol, a plan
+ * not over all rows), then for a restart outside 0 .. EHYB_GMRES_MAX_RESTART or ortho_passes outside 0 .. 2; then EHYB_ERR_STATE
+ * on a plan never uploaded -- all before any device work.
+ *
+ * The five vector kernels as building blocks, one launch each with slot_doubles / 2 workgroups, as the ehyb_minres_*_step calls.
+ * s_dev: `slots` slots of `slot_doubles` doubles and tail_doubles more behind them (ehyb_gmres_layout).  c_i lives in slot
+ * slot_c0 + i; slot_ww holds the partials of r.r after start and of w.w after the last update.  The tail, in doubles: at
+ * flags_at the ints status (flag_status) and counter (flag_iters); at cycle_at the int counter at the cycle start; rho_at, bb_at;
+ * cs_at + i, sn_at + i, g_at + i (i < max_restart); gt_at + i: g~_i (i <= max_restart); h_at + p h_stride + i: the Hessenberg
+ * column after pass p; r_at + j r_stride + i: R[i, j].  V_dev: basis column i at V_dev + i ld, ld even and >= n; V_dev, w_dev,
+ * z_dev, x_dev and inv_diag_dev 16-byte aligned.  Every step but solve_x returns at once, writing nothing, when the status is not
+ * status_running on entry.
+ *   start    w = b - w (w = A x on entry); partials of w.w (slot_ww) and b.b (slot_bb)
+ *   dots     partials of c_i = v_i.w for i < count (1 .. max_restart + 1), the columns in register groups of 8
+ *   update   w -= sum_{i < count} c_i v_i, c_i from the partials; Hessenberg copy `pass` (0 / 1) = copy pass - 1 + c (pass 0: c);
+ *            last != 0: the partials of w.w
+ *   next     j = -1: the cycle start's tests on slot_ww and slot_bb; v_0 = w / sqrt(w.w), z = M^-1 v_0; g~_0, rho, bb and the
+ *            counter at the cycle start.  j = 0 .. max_restart - 1: step j's column from Hessenberg copy passes - 1 and slot_ww,
+ *            rotation, g, R, rho, counter and tests as stated above; v_{j+1} = w / h_{j+1} into column j + 1, z = M^-1 v_{j+1}
+ *   solve_x  J = counter - counter at the cycle start (J <= 0: nothing); R y = g[0 .. J), x += M^-1 (sum_{i < J} y_i v_i).  Does
+ *            not look at the status: the steps counted before a stop are applied.
+ * EHYB_ERR_ARG for n < 0, a null pointer that would be used, a count, pass, j or passes outside its range, an odd ld or one
+ * below n, a misaligned vector.  All asynchronous on `stream`.
+ */
+#define EHYB_GMRES_MAX_RESTART 64
+int ehyb_gmres(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, double* x_dev, int restart, int ortho_passes,
+               int max_iter, double rtol, void* stream, int* iters_done, double* rel_residual);
+typedef struct ehyb_gmres_slots {
+    int32_t slots, slot_doubles;
+    int32_t slot_bb, slot_ww, slot_c0;
+    int32_t max_restart, tail_doubles;
+    int32_t flags_at, flag_status, flag_iters, flag_count;
+    int32_t cycle_at, rho_at, bb_at, cs_at, sn_at, gt_at, g_at, h_at, h_stride, r_at, r_stride;
+    int32_t status_running, status_converged, status_breakdown;
+} ehyb_gmres_slots;
+int ehyb_gmres_layout(ehyb_gmres_slots* out);
+int ehyb_gmres_start_step(int n, const double* b_dev, double* w_dev, double* s_dev, void* stream);
+int ehyb_gmres_dots_step(int n, int64_t ld, const double* V_dev, const double* w_dev, int count, double* s_dev, void* stream);
+int ehyb_gmres_update_step(int n, int64_t ld, const double* V_dev, double* w_dev, int count, double* s_dev, int pass, int last,
+                           void* stream);
+int ehyb_gmres_next_step(int n, int64_t ld, double* V_dev, const double* w_dev, const double* inv_diag_dev, double* z_dev,
+                         double* s_dev, int j, int passes, double thr, void* stream);
+int ehyb_gmres_solve_x_step(int n, int64_t ld, const double* V_dev, const double* inv_diag_dev, double* x_dev, double* s_dev,
+                            void* stream);
+
 /* -------------------------------------------- harness pieces (solver_test.c) */
 
 /*
