@@ -14,6 +14,7 @@ from .host import (  # noqa: F401
     EHYB_PART_MULTILEVEL,
     EHYB_WINDOW_HALO,
     EHYB_WINDOW_REFERENCE,
+    KERNEL_TABLES,
     DeviceBuffer,
     EhybError,
     Matrix,
@@ -24,6 +25,7 @@ from .host import (  # noqa: F401
     device_count,
     entry_order,
     host_threads,
+    kernel_table,
     make_config,
     minres_inv_diag,
     partition_graph,

@@ -201,6 +201,12 @@ SIGNATURES = {
     "ehyb_spmm": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int]),
     "ehyb_spmm_max_k": (C.c_int, [_vp, _ip]),
     "ehyb_plan_tune": (C.c_int, [_vp, _vp, _vp, C.c_int, _dp, _dp]),
+    "ehyb_debug_ell_stamps": (C.c_int, [_vp, _vp, _vp, _P(C.c_ulonglong)]),
+    "ehyb_debug_ell_stamps_probe": (C.c_int, [_vp, _vp, _vp, _P(C.c_ulonglong), C.c_int]),
+    "ehyb_debug_panel_times": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _dp, _dp]),
+    "ehyb_debug_kernel_table": (C.c_int, [C.c_int, _P(C.c_int32), C.c_int, _ip]),
+    "ehyb_debug_launched": (C.c_int, [_vp, C.c_int, _P(C.c_uint8), C.c_int]),
+    "ehyb_debug_launched_clear": (C.c_int, [_vp]),
     "ehyb_spmv_part": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "ehyb_plan_col_segs": (C.c_int, [_vp, _ip]),
     "ehyb_gather": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),

@@ -383,7 +383,10 @@ int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y,
         EHYB_FAIL(EHYB_ERR_ARG, "window launch: cfg.val_f32 serves one column, the LDS slab counter and no stamps (%d columns%s%s)", k,
                   dyn ? "" : ", cfg.ell_variant = 3", stamps ? ", a stamped or probe launch" : "");
     const void* fn = nullptr;
-    for (const EllKernel& e : ell_kernels()) {
+    const std::vector<EllKernel>& table = ell_kernels();
+    size_t row = 0;
+    for (; row < table.size(); ++row) {
+        const EllKernel& e = table[row];
         if (e.f32 == f32 && e.threads == P->cfg.threads && e.k == k && e.dyn == dyn && e.stamp == (stamps != nullptr) && e.inl == inl && e.sym == H.sym) {
             fn = e.fn;
             break;
@@ -399,6 +402,7 @@ int ehyb::launch_window(ehyb_plan* P, const double* x, long long ldx, double* y,
     else
         ell_walk(P, walk, n_items, lds, &A);
     void* args[] = {&A, &ldx, &ldy};  // (the one-vector kernel takes A alone)
+    P->mark_launched(EHYB_KERNELS_WINDOW, row);
     (void)hipLaunchKernel(fn, dim3(n_items), dim3(P->cfg.threads), args, lds, st);  // as <<< >>>: a failed launch is the last error
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
@@ -458,18 +462,24 @@ static const std::vector<PanelKernel>& panel_kernels()
     return all;
 }
 
-// (each pass is looked up by the fields it has)
-static const void* panel_scale_kernel(int threads, int k, bool dpp, bool probe)
+// (each pass is looked up by the fields it has)  -> the table row, -1: not built
+static int panel_scale_kernel(int threads, int k, bool dpp, bool probe)
 {
-    for (const PanelKernel& e : panel_kernels())
-        if (e.pass == 1 && e.threads == threads && e.k == k && e.dpp == dpp && e.probe == probe) return e.fn;
-    return nullptr;
+    const std::vector<PanelKernel>& table = panel_kernels();
+    for (size_t row = 0; row < table.size(); ++row) {
+        const PanelKernel& e = table[row];
+        if (e.pass == 1 && e.threads == threads && e.k == k && e.dpp == dpp && e.probe == probe) return (int)row;
+    }
+    return -1;
 }
-static const void* panel_reduce_kernel(int k, bool nt)
+static int panel_reduce_kernel(int k, bool nt)
 {
-    for (const PanelKernel& e : panel_kernels())
-        if (e.pass == 2 && e.k == k && e.nt == nt) return e.fn;
-    return nullptr;
+    const std::vector<PanelKernel>& table = panel_kernels();
+    for (size_t row = 0; row < table.size(); ++row) {
+        const PanelKernel& e = table[row];
+        if (e.pass == 2 && e.k == k && e.nt == nt) return (int)row;
+    }
+    return -1;
 }
 
 // Dynamic LDS of a pass-1 launch: k interleaved panel images, the waves' piece accumulators (LDS sums only) and the word in which
@@ -512,14 +522,15 @@ static int launch_panel_scale(ehyb_plan* P, const double* x, long long ldx, int 
             else if (item_begin == 0) rev = (P->panel_parity.fetch_xor(1, std::memory_order_relaxed) ^ 1) & 1;
             else rev = P->panel_parity.load(std::memory_order_relaxed) & 1;
         }
-        const void* fn = panel_scale_kernel(threads, k, dpp, probe != 0);
-        if (!fn) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 1 not built for %d threads, %d columns%s", threads, k, probe ? " with probes" : "");
+        const int row = panel_scale_kernel(threads, k, dpp, probe != 0);
+        if (row < 0) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 1 not built for %d threads, %d columns%s", threads, k, probe ? " with probes" : "");
         const int2* items = (const int2*)P->d_pb_items1 + item_begin;
         const int4* units = (const int4*)P->d_pb_units1;
         int panel_cols = H.pb_panel_cols;
         void* args1[] = {&items, &units, &P->d_pb_val, &P->d_pb_colf, &P->d_pb_chunk, &P->d_pb_jump, &x, &P->d_pb_partial, &panel_cols, &probe, &xcd, &queue, &n_items, &rev};
         void* argsk[] = {&items, &units, &P->d_pb_val, &P->d_pb_colf, &P->d_pb_chunk, &P->d_pb_jump, &x, &ldx, &P->d_pb_partial, &panel_cols, &xcd, &queue, &n_items, &rev};
-        (void)hipLaunchKernel(fn, dim3(grid), dim3(threads), k == 1 ? args1 : argsk, panel_scale_lds_bytes(H, k, dpp, threads), st);
+        P->mark_launched(EHYB_KERNELS_PANEL, (size_t)row);
+        (void)hipLaunchKernel(panel_kernels()[(size_t)row].fn, dim3(grid), dim3(threads), k == 1 ? args1 : argsk, panel_scale_lds_bytes(H, k, dpp, threads), st);
     }
     HIP_TRY(hipGetLastError());  // (as <<< >>>: a failed launch is the last error)
     return EHYB_OK;
@@ -554,12 +565,13 @@ static int launch_panel_reduce(ehyb_plan* P, double* y, long long ldy, int k, hi
         // (cfg.er_nt: 0 = by the size of what pass 2 reads -- 8 B per column and 2 B of row word per partial sum -- against half the
         // Infinity Cache, 1 / 2 = always / never)
         const bool nt = P->cfg.er_nt == 1 || (P->cfg.er_nt == 0 && H.pb_partials * (8 * k + 2) > kInfinityCache / 2);
-        const void* fn = panel_reduce_kernel(k, nt);
-        if (!fn || (k > 1 && probe)) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 2 not built for %d columns%s", k, probe ? " with probes" : "");
+        const int row = panel_reduce_kernel(k, nt);
+        if (row < 0 || (k > 1 && probe)) EHYB_FAIL(EHYB_ERR_ARG, "panel pass 2 not built for %d columns%s", k, probe ? " with probes" : "");
         const int4* units = (const int4*)P->d_pb_units2 + first;
         void* args1[] = {&units, &P->d_pb_partial, &P->d_pb_row, &y, &probe};
         void* argsk[] = {&units, &P->d_pb_partial, &P->d_pb_row, &y, &ldy};
-        (void)hipLaunchKernel(fn, dim3(n_units), dim3(512), k == 1 ? args1 : argsk, panel_reduce_lds_bytes(H, k), st);
+        P->mark_launched(EHYB_KERNELS_PANEL, (size_t)row);
+        (void)hipLaunchKernel(panel_kernels()[(size_t)row].fn, dim3(n_units), dim3(512), k == 1 ? args1 : argsk, panel_reduce_lds_bytes(H, k), st);
     }
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
@@ -574,25 +586,52 @@ int ehyb::launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y
     return rc != EHYB_OK ? rc : launch_panel_reduce(P, y, ldy, k, st, 0, PANEL_ROWS_ALL);
 }
 
+// ---- CSR residual
+// Every instantiation of the row-segment kernel (256 threads): one vector and K = 2..kSpmmMaxK, adding to what the window launch
+// wrote or ASSIGNing (the direct shape: it does everything), and the one-vector kernels of cfg.val_f32.
+struct ErKernel { int k; bool assign, f32; const void* fn; };
+
+template <bool ASSIGN>
+static void add_er_kernels(std::vector<ErKernel>* v)
+{
+    v->insert(v->end(), {{1, ASSIGN, false, (const void*)ehyb_er_kernel<256, ASSIGN>}, {2, ASSIGN, false, (const void*)ehyb_er_k_kernel<256, ASSIGN, 2>},
+                         {3, ASSIGN, false, (const void*)ehyb_er_k_kernel<256, ASSIGN, 3>}, {4, ASSIGN, false, (const void*)ehyb_er_k_kernel<256, ASSIGN, 4>}});
+}
+
+static const std::vector<ErKernel>& er_kernels()
+{
+    static const std::vector<ErKernel> all = [] {
+        std::vector<ErKernel> v;
+        add_er_kernels<false>(&v), add_er_kernels<true>(&v);
+        v.insert(v.end(), {{1, false, true, (const void*)ehyb_er_f32_kernel<256, false>}, {1, true, true, (const void*)ehyb_er_f32_kernel<256, true>}});  // (same arguments: d_er_val holds floats)
+        return v;
+    }();
+    return all;
+}
+
 int ehyb::launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st)
 {
     const HostLayout& H = P->host;
     if (H.er_bins[3] == 0) return EHYB_OK;
     const int n_blocks = (int)(H.er_blocks.size() / 4);
     if (P->cfg.er_threads != 256) EHYB_FAIL(EHYB_ERR_ARG, "residual workgroup size %d not built (256)", P->cfg.er_threads);
-    const void* fn[2][kSpmmMaxK] = {
-        {(const void*)ehyb_er_kernel<256, false>, (const void*)ehyb_er_k_kernel<256, false, 2>, (const void*)ehyb_er_k_kernel<256, false, 3>,
-         (const void*)ehyb_er_k_kernel<256, false, 4>},
-        {(const void*)ehyb_er_kernel<256, true>, (const void*)ehyb_er_k_kernel<256, true, 2>, (const void*)ehyb_er_k_kernel<256, true, 3>,
-         (const void*)ehyb_er_k_kernel<256, true, 4>}};
-    const void* launch = fn[H.direct][k - 1];  // ASSIGN: the direct shape
-    if (P->cfg.val_f32 == 1) {
-        if (k > 1) EHYB_FAIL(EHYB_ERR_ARG, "residual launch: cfg.val_f32 serves one column, not %d", k);
-        launch = H.direct ? (const void*)ehyb_er_f32_kernel<256, true> : (const void*)ehyb_er_f32_kernel<256, false>;  // (same arguments: d_er_val holds floats)
+    const bool f32 = P->cfg.val_f32 == 1;
+    if (f32 && k > 1) EHYB_FAIL(EHYB_ERR_ARG, "residual launch: cfg.val_f32 serves one column, not %d", k);
+    const void* launch = nullptr;
+    const std::vector<ErKernel>& table = er_kernels();
+    size_t row = 0;
+    for (; row < table.size(); ++row) {
+        const ErKernel& e = table[row];
+        if (e.k == k && e.assign == (H.direct != 0) && e.f32 == f32) {  // ASSIGN: the direct shape
+            launch = e.fn;
+            break;
+        }
     }
+    if (!launch) EHYB_FAIL(EHYB_ERR_ARG, "residual launch not built for %d columns", k);
     const int4* blocks = (const int4*)P->d_er_blocks;
     void* args1[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &y};
     void* argsk[] = {&blocks, &P->d_er_seg_ptr, &P->d_er_seg_row, &P->d_er_col, &P->d_er_val, &x, &ldx, &y, &ldy};
+    P->mark_launched(EHYB_KERNELS_ER_CSR, row);
     (void)hipLaunchKernel(launch, dim3(n_blocks), dim3(256), k == 1 ? args1 : argsk, 0, st);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
@@ -939,6 +978,52 @@ int ehyb_debug_panel_times(ehyb_plan* P, const double* x, double* y, int iters, 
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
     return rc;
+}
+
+// Diagnostic (tests/kernel_census_cases.py): the three kernel tables as rows of ints, and a plan's launch log (see ehyb.h).
+int ehyb_debug_kernel_table(int which, int32_t* rows, int cap, int* n_rows)
+{
+    clear_error();
+    if (!n_rows || cap < 0 || (cap > 0 && !rows)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_kernel_table: bad arguments");
+    std::vector<int32_t> out;
+    if (which == EHYB_KERNELS_WINDOW) {
+        for (const EllKernel& e : ell_kernels()) out.insert(out.end(), {e.threads, e.k, e.dyn, e.stamp, e.inl, e.sym, e.f32});
+    } else if (which == EHYB_KERNELS_PANEL) {
+        for (const PanelKernel& e : panel_kernels()) out.insert(out.end(), {e.pass, e.threads, e.k, e.dpp, e.probe, e.nt});
+    } else if (which == EHYB_KERNELS_ER_CSR) {
+        for (const ErKernel& e : er_kernels()) out.insert(out.end(), {e.k, e.assign, e.f32});
+    } else {
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_kernel_table: table %d (EHYB_KERNELS_WINDOW, _PANEL, _ER_CSR)", which);
+    }
+    const int width = which == EHYB_KERNELS_WINDOW ? EHYB_KERNEL_ROW_WINDOW : (which == EHYB_KERNELS_PANEL ? EHYB_KERNEL_ROW_PANEL : EHYB_KERNEL_ROW_ER_CSR);
+    const int n = (int)(out.size() / (size_t)width);
+    if (n > kKernelTableCap) EHYB_FAIL(EHYB_ERR_INTERNAL, "ehyb_debug_kernel_table: table %d has %d rows, the launch log of a plan %d", which, n, kKernelTableCap);
+    *n_rows = n;
+    std::copy(out.begin(), out.begin() + (size_t)std::min(n, cap) * (size_t)width, rows);
+    return EHYB_OK;
+}
+
+static int kernel_table_rows(int which)
+{
+    return which == EHYB_KERNELS_WINDOW ? (int)ell_kernels().size() : which == EHYB_KERNELS_PANEL ? (int)panel_kernels().size() : which == EHYB_KERNELS_ER_CSR ? (int)er_kernels().size() : -1;
+}
+
+int ehyb_debug_launched(const ehyb_plan* P, int which, uint8_t* out, int cap)
+{
+    clear_error();
+    const int n = kernel_table_rows(which);
+    if (!P || !out || n < 0 || cap < n || n > kKernelTableCap) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_launched: bad arguments (table %d has %d rows, room for %d)", which, n, cap);
+    for (int i = 0; i < n; ++i) out[i] = __atomic_load_n(&P->launched[which][i], __ATOMIC_RELAXED);
+    return EHYB_OK;
+}
+
+int ehyb_debug_launched_clear(ehyb_plan* P)
+{
+    clear_error();
+    if (!P) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_launched_clear: null plan");
+    for (int t = 0; t < kKernelTables; ++t)
+        for (int i = 0; i < kKernelTableCap; ++i) __atomic_store_n(&P->launched[t][i], (uint8_t)0, __ATOMIC_RELAXED);
+    return EHYB_OK;
 }
 
 int ehyb_plan_upload(ehyb_plan* P)

@@ -388,6 +388,11 @@ inline uint64_t mix64(uint64_t z)
     return z ^ (z >> 31);
 }
 
+// The kernel tables of ehyb_hip.hip (EHYB_KERNELS_*: window, panel passes, CSR residual) and the rows a plan's launch log has
+// room for per table (ehyb_debug_kernel_table refuses a table that outgrew it: 96, 22 and 10 rows today).
+constexpr int kKernelTables = 3;
+constexpr int kKernelTableCap = 128;
+
 }  // namespace ehyb
 
 // The plan object behind the opaque handle.
@@ -435,5 +440,12 @@ struct ehyb_plan {
     // threads that multiply with one plan on their own streams (ELL-only plans: include/ehyb.h) each draw a direction
     std::atomic<int> launch_parity{0};
     std::atomic<int> panel_parity{0};
+    // launch log (ehyb_debug_launched): one byte per row of the three kernel tables of ehyb_hip.hip, set by the launch that looked
+    // the row up -- a relaxed byte store, no lock and no allocation on the launch path; every thread stores the same 1
+    uint8_t launched[ehyb::kKernelTables][ehyb::kKernelTableCap] = {};
+    void mark_launched(int which, size_t row)
+    {
+        if (row < (size_t)ehyb::kKernelTableCap) __atomic_store_n(&launched[which][row], (uint8_t)1, __ATOMIC_RELAXED);
+    }
 };
 inline int ehyb::plan_spmm_width(const ehyb_plan* P) { return P->cfg.val_f32 == 1 ? 1 : spmm_width(P->host); }

@@ -60,6 +60,26 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+# the kernel tables of the library (EHYB_KERNELS_* of ehyb.h, in that order) and the fields of a row of each
+KERNEL_TABLES = {
+    "window": ("threads", "k", "dyn", "stamp", "inl", "sym", "f32"),
+    "panel": ("pass", "threads", "k", "dpp", "probe", "nt"),
+    "er_csr": ("k", "assign", "f32"),
+}
+
+
+def kernel_table(name):
+    """ehyb_debug_kernel_table -> the rows of table "window", "panel" or "er_csr" as tuples of ints (KERNEL_TABLES[name] names
+    the fields), in table order.  Needs no device."""
+    lib = _lib.load()
+    which, width = list(KERNEL_TABLES).index(name), len(KERNEL_TABLES[name])
+    n = C.c_int(0)
+    _check(lib.ehyb_debug_kernel_table(which, None, 0, C.byref(n)), "ehyb_debug_kernel_table")
+    rows = np.zeros((n.value, width), dtype=np.int32)
+    _check(lib.ehyb_debug_kernel_table(which, _ptr(rows, C.c_int32), n.value, C.byref(n)), "ehyb_debug_kernel_table")
+    return [tuple(int(v) for v in r) for r in rows]
+
+
 def _view(ptr, count, dtype):
     if count == 0:
         return np.zeros(0, dtype=dtype)
@@ -440,6 +460,20 @@ class Plan:
         a, b = C.c_double(0), C.c_double(0)
         _check(self.lib.ehyb_plan_tune(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), reps, C.byref(a), C.byref(b)), "ehyb_plan_tune")
         return a.value, b.value
+
+    def launched(self):
+        """ehyb_debug_launched -> {"window" / "panel" / "er_csr": set of the rows of kernel_table() this plan's launches took since
+        the plan was made or launched_clear()}, each row a tuple of the table's fields"""
+        out = {}
+        for which, name in enumerate(KERNEL_TABLES):
+            rows = kernel_table(name)
+            log = np.zeros(len(rows), dtype=np.uint8)
+            _check(self.lib.ehyb_debug_launched(self.h, which, _ptr(log, C.c_uint8), len(log)), "ehyb_debug_launched")
+            out[name] = {rows[i] for i in np.flatnonzero(log)}
+        return out
+
+    def launched_clear(self):
+        _check(self.lib.ehyb_debug_launched_clear(self.h), "ehyb_debug_launched_clear")
 
     def spmv_part(self, x_dev, y_dev, stream, seg_begin, seg_end, flags):
         """ehyb_spmv_part: flags 1 = the ELL launch first, 2 = the closing pass (EHYB_PART_FIRST / _LAST)."""

@@ -616,6 +616,40 @@ int ehyb_spmv_phase(ehyb_plan* plan, const double* x_dev, double* y_dev, void* s
 int ehyb_plan_tune(ehyb_plan* plan, const double* x_dev, double* y_dev, int reps, double* span_before_us, double* span_after_us);
 
 /*
+ * DIAGNOSTICS (tools/, tests/): no part of the product's contract beyond what is said here.
+ * ehyb_debug_ell_stamps        one launch of the STAMPED instantiation of the plan's one-vector window kernel (not cfg.val_f32) on
+ *                              the null stream, synchronous.  y is written as by the window launch of ehyb_spmv; out_host receives 4
+ *                              words per item (stats.n_items of them): entry / window staged / exit wall-clock ticks (100 MHz) and
+ *                              the XCC id (ehyb_plan_tune masks it with 15).  An item without a segment stages nothing.
+ * ehyb_debug_ell_stamps_probe  the same launch with the staging replaced (triple_gather 1: every window entry from three vectors,
+ *                              2: no halo gather) -- for timing only, y is WRONG by design.
+ * ehyb_debug_panel_times       mean time in ms of each pass of a panel-form residual alone, `iters` launches each between HIP events
+ *                              on the null stream; probe != 0 switches steps of pass 1 off (y wrong by design).
+ * THE KERNEL TABLES.  The library builds three tables of kernel instantiations and every launch looks its kernel up in one:
+ *   EHYB_KERNELS_WINDOW   EHYB_KERNEL_ROW_WINDOW = 7 ints per row:  threads, k, dyn, stamp, inl, sym, f32 -- workgroup size; columns
+ *                         per pass; 1 = LDS slab counter, 0 = static round-robin (cfg.ell_variant = 3); stamped (above); inline
+ *                         residual; symmetric pairs; cfg.val_f32
+ *   EHYB_KERNELS_PANEL    EHYB_KERNEL_ROW_PANEL = 6:  pass, threads, k, dpp, probe, nt -- pass 1 or 2; workgroup size; columns; 1 =
+ *                         register-scan sums, 0 = LDS sums (cfg.er_sums = 2); the timing probes; pass 2's streaming hint (cfg.er_nt).
+ *                         A field its pass does not have holds one value.
+ *   EHYB_KERNELS_ER_CSR   EHYB_KERNEL_ROW_ER_CSR = 3:  k, assign, f32 -- columns; 1 = the direct shape (assigns), 0 = adds; cfg.val_f32
+ * ehyb_debug_kernel_table      the rows of table `which`: *n_rows = their number, the first min(cap, *n_rows) rows are written to
+ *                              `rows` (cap rows of the table's width; rows may be NULL with cap 0).  Host only: needs no device.
+ * ehyb_debug_launched          the plan's LAUNCH LOG of table `which`: out[i] = 1 iff a launch of this plan took row i since the plan
+ *                              was made or the log last cleared; cap >= the table's rows (EHYB_ERR_ARG otherwise).  A launch marks
+ *                              its row with one byte store before it enqueues the kernel; a launch that finds nothing to do (no
+ *                              item, no residual) marks nothing.  ehyb_debug_launched_clear zeroes all three logs.
+ */
+enum { EHYB_KERNELS_WINDOW = 0, EHYB_KERNELS_PANEL = 1, EHYB_KERNELS_ER_CSR = 2 };
+enum { EHYB_KERNEL_ROW_WINDOW = 7, EHYB_KERNEL_ROW_PANEL = 6, EHYB_KERNEL_ROW_ER_CSR = 3 };
+int ehyb_debug_ell_stamps(ehyb_plan* plan, const double* x_dev, double* y_dev, unsigned long long* out_host);
+int ehyb_debug_ell_stamps_probe(ehyb_plan* plan, const double* x_dev, double* y_dev, unsigned long long* out_host, int triple_gather);
+int ehyb_debug_panel_times(ehyb_plan* plan, const double* x_dev, double* y_dev, int iters, int probe, double* ms_scale, double* ms_reduce);
+int ehyb_debug_kernel_table(int which, int32_t* rows, int cap, int* n_rows);
+int ehyb_debug_launched(const ehyb_plan* plan, int which, uint8_t* out, int cap);
+int ehyb_debug_launched_clear(ehyb_plan* plan);
+
+/*
  * The multiply in PARTS, for a caller that receives x segment by segment (multi-GPU, ehyb_plan_create_host_segs):
  *   flags & EHYB_PART_FIRST   the ELL launch (window columns: all inside column segment 0) runs first;
  *   column segments [seg_begin, seg_end): pass 1 of the panel-form residual over the panels of those segments

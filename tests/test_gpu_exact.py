@@ -205,9 +205,15 @@ def test_panel_times_probes_launch_and_leave_the_product(E, O, gpu, er_sums, thr
     lib.ehyb_debug_panel_times.restype = C.c_int
     lib.ehyb_debug_panel_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     dx, dy = E.DeviceBuffer(c.n).upload(c.xp), E.DeviceBuffer(c.n).upload(y0)
-    for probe in (0, 2, 0):                     # (panel_sweep.py --probes, then the product again)
+    plan.launched_clear()
+    dpp = int(er_sums != 2)
+    for probe, probed in ((0, 0), (2, 1), (0, 0)):                     # (panel_sweep.py --probes, then the product again)
         a, b = C.c_double(), C.c_double()
         assert lib.ehyb_debug_panel_times(plan.h, C.c_void_p(dx.ptr), C.c_void_p(dy.ptr), 1, probe, C.byref(a), C.byref(b)) == 0, probe
+        # the launch log (rows of E.kernel_table("panel"): pass, threads, k, dpp, probe, nt): pass 1 in its plain and then its PROBE
+        # instantiation, pass 2 -- whose probe is an argument, not an instantiation -- cached (these partial sums are far below the cache)
+        assert (1, threads, 1, dpp, probed, 0) in plan.launched()["panel"], (probe, plan.launched())
+    assert plan.launched() == dict(window=set(), er_csr=set(), panel={(1, threads, 1, dpp, 0, 0), (1, threads, 1, dpp, 1, 0), (2, 512, 1, 1, 0, 0)})
     _sync(E)
     assert_exact(dy.download(), c.y_ref_p, f"er_sums={er_sums} threads={threads} after the probes")
     dx.free(), dy.free()

@@ -8,24 +8,28 @@ matrix float(a_ij), per accumulator in the fp64 kernel's order.  So
     and x (np.array_equal), the solvers' iterates included; with symmetric pairs up to the order of the LDS adds.
 Without the feature every test here fails at make_config(val_f32=1).
 
-Which exact test launches which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> (the plan's cfg.threads, stats["er_inline"] > 0,
-stats["sym_pairs"] > 0; test_val_f32_host.py pins the seeds' share of the table from host-only plans):
+Which exact test launches which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> (the plan's cfg.threads, stats["er_inline"] > 0, and
+symmetric pair STORAGE: cfg.sym_pairs = 1 with halo windows, whether or not the matrix had a pair to store; test_val_f32_host.py
+pins the seeds' share of the table from host-only plans, and _assert_launch_log holds every plan's launch log -- what really ran,
+Plan.launched() -- against it.  Until the log existed this table went by stats["sym_pairs"] > 0 and had seeds 115, 122, 123, 127
+and 129, whose matrices pair nowhere, under SYM = no: they launch the SYM kernel.):
 
   THREADS  INLINE_ER  SYM    test_exact_random_plan_f32 (seeds)      named
-  256      no         no     102 107 109 115 122 123 128 135 137     refwindow-t256-lds1024
-  256      no         yes    134
+  256      no         no     102 107 109 128 135 137                 refwindow-t256-lds1024
+  256      no         yes    115 122 123 134
   256      yes        no     108
   256      yes        yes    120                                     test_inline_residual_with_symmetric_pairs_f32[256-*]
-  512      no         no     104 114 129 136                         halo-t512-lds64
-  512      no         yes    131                                     sym-fem-3dof-t512-lds20480
+  512      no         no     104 114 136                             halo-t512-lds64
+  512      no         yes    129 131                                 sym-fem-3dof-t512-lds20480
   512      yes        no     101
   512      yes        yes    --                                      test_inline_residual_with_symmetric_pairs_f32[512-*]
-  1024     no         no     100 111 118 121 127 130                 refwindow-t1024-lds20480, csr-split-*, relative-columns
-  1024     no         yes    138                                     sym-fem-3dof, sym-*-accidental-pairs
+  1024     no         no     100 111 118 121 130                     refwindow-t1024-lds20480, csr-split-*, relative-columns
+  1024     no         yes    127 138                                 sym-fem-3dof, sym-*-accidental-pairs
   1024     yes        no     110 117 124                             halo-t1024-lds20480, inline-residual
   1024     yes        yes    --                                      test_inline_residual_with_symmetric_pairs_f32[1024-*]
-(named: ids of test_exact_named_path_f32 unless a test is named.  test_rounded_random_plan_f32 runs the same seeds on tie values,
-where the accidental pairs of seeds 134 and 138 are gone: those two take the arm without pairs there.)"""
+(named: ids of test_exact_named_path_f32 unless a test is named.  A plan with an inline residual also launches the arm of its row
+with INLINE_ER = no, in phase 1 of a multiply in phases.  test_rounded_random_plan_f32 runs the same seeds on tie values, where the
+accidental pairs of seeds 134 and 138 are gone: the storage, and so the arm, stays.)"""
 import ctypes as C
 
 import numpy as np
@@ -33,6 +37,7 @@ import pytest
 import scipy.sparse as sp
 
 from exact_cases import assert_exact, exact_reference, integer_values, nonfinite_reference, value_class
+from kernel_census_cases import f32_window_row
 from range_cases import family
 from test_gpu_exact import (FEM, PATHS, REFILL_PLANS, RMAT11, ExactCase, _device_set_values, _integer_spd, _sync, all_ways, is_direct,
                             multiply)
@@ -45,6 +50,25 @@ F32_PATHS = [p for p in PATHS if p[2].get("er_mode") != 2]
 assert len(F32_PATHS) == 14 and not any("panel" in p[0] or "windowless" in p[0] for p in F32_PATHS)
 
 
+def _assert_launch_log(plan, cfg, n, what):
+    """The plan's launch log against window_arm, after multiplies in one launch sequence AND in phases 1 + 2: the window launches
+    since the plan was made took the fp32 row window_arm names (kernel_census_cases.f32_window_row) -- the log is what ran,
+    window_arm what this file believes ran -- and the CSR residual its fp32 kernel, assigning in the direct shape.  A plan with an
+    inline residual multiplies in phases WITHOUT it: phase 1 is the window kernel of the same form with no inline residual, phase 2
+    the CSR residual kernel."""
+    st, log = plan.stats, plan.launched()
+    arm = window_arm(cfg, st)
+    inline, sym = st["er_inline"] > 0, int(cfg.sym_pairs) == 1 and int(cfg.window_mode) == 2      # (the storage, not the pairs found)
+    rows = {f32_window_row((cfg.threads, inline, sym)), f32_window_row((cfg.threads, False, sym))}
+    if arm is not None:
+        assert f32_window_row(arm) in log["window"] and log["window"] == rows, (what, arm, log["window"])
+    else:                                       # no ELL entry: no launch, or one over windows that hold none
+        assert log["window"] <= rows, (what, log["window"])
+    # (the direct shape assigns every row, also of a matrix without an entry: one segment per row)
+    er = {(1, 1, 1)} if is_direct(plan, n) else ({(1, 0, 1)} if st["nnz_er"] > 0 else set())
+    assert log["er_csr"] == er and log["panel"] == set(), (what, log)
+
+
 @pytest.mark.parametrize("name,gen,kw,sym,taken", F32_PATHS, ids=[p[0] for p in F32_PATHS])
 def test_exact_named_path_f32(E, O, gpu, name, gen, kw, sym, taken):
     """Integer values +-1..7 (fp32 holds them) against an x fp32 cannot hold: every way of multiplying is the exact product."""
@@ -54,6 +78,7 @@ def test_exact_named_path_f32(E, O, gpu, name, gen, kw, sym, taken):
     assert taken(plan, c.n), (name, plan.stats)
     assert plan.device_value_bytes[0] == 4 * len(plan.array("ell_val")) and plan.spmm_max_k == 1
     all_ways(E, plan, c.xp, c.y_ref_p, name + " val_f32")
+    _assert_launch_log(plan, cfg, c.n, name)
     plan.destroy()
 
 
@@ -91,6 +116,7 @@ def test_exact_random_plan_f32(E, O, gpu, seed):
     plan = _checked_f32_plan(E, m, cfg, str(kw))
     print(f"seed {seed}: n={m.n} nnz={m.nnz} window arm {window_arm(cfg, plan.stats)}")
     _multiplies(E, plan, m.n, E.vector_reorder(x, m.reorder_list), E.vector_reorder(y_ref, m.reorder_list), str(kw))
+    _assert_launch_log(plan, cfg, m.n, f"seed {seed}")
     plan.destroy()
 
 
@@ -160,6 +186,8 @@ def test_inline_residual_with_symmetric_pairs_f32(E, O, gpu, threads, triples):
         assert not coded.any()
     all_ways(E, plan, c.xp, c.y_ref_p, f"{kw} integers")
     _alternating_walk_and_a_graph(E, plan, c.n, c.xp, c.y_ref_p, f"{kw} integers")
+    assert plan.launched()["window"] == {(threads, 1, 1, 0, 1, 1, 1), (threads, 1, 1, 0, 0, 1, 1)}      # (the second: phase 1 of phases 1 + 2)
+    _assert_launch_log(plan, cfg, c.n, str(kw))
     plan.destroy()
     t = TieCase(E, FEM, cfg, True)
     plan = _checked_f32_plan(E, t.m, cfg, str(kw))

@@ -79,5 +79,9 @@ def fuzz_case_f32(E, O, seed, **more):
 
 
 def window_arm(cfg, stats):
-    """which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> a plan's window launch is, None without a window launch"""
-    return (int(cfg.threads), stats["er_inline"] > 0, stats["sym_pairs"] > 0) if stats["nnz_ell"] > 0 else None
+    """which ehyb_ell_f32_kernel<THREADS, INLINE_ER, SYM> a plan's window launch is, None without an ELL entry.  SYM is the
+    STORAGE (cfg.sym_pairs = 1 with halo windows: layout.cpp), not whether the matrix had a pair to store: a plan of a matrix
+    without one (a diagonal matrix, values that pair nowhere) still launches the SYM kernel, as the launch log shows
+    (test_gpu_val_f32._assert_launch_log)."""
+    sym = int(cfg.sym_pairs) == 1 and int(cfg.window_mode) == 2
+    return (int(cfg.threads), stats["er_inline"] > 0, sym) if stats["nnz_ell"] > 0 else None
