@@ -285,6 +285,13 @@ SIGNATURES = {
     "ehyb_gmres_update_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "ehyb_gmres_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp]),
     "ehyb_gmres_solve_x_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "ehyb_eigsh": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _vp, C.c_int64, _vp, _ip, _ip, _ip, _ip,
+                             _dp]),
+    "ehyb_eigsh_basis": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip]),
+    "ehyb_sym_eig": (C.c_int, [C.c_int, _dp, C.c_int, _dp, _dp]),
+    "ehyb_eigsh_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_eigsh_scale_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_eigsh_rotate_step": (C.c_int, [C.c_int, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

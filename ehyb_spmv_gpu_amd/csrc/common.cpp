@@ -384,6 +384,66 @@ void ehyb_matrix_free(matrixCOO* m)
     memset(m, 0, sizeof *m);
 }
 
+// The eigenpairs of a dense symmetric matrix by cyclic Jacobi (the projected problem of ehyb_eigsh): sweeps over p < q in a fixed
+// order, the rotation that annihilates a_pq in Rutishauser's form (t the smaller root, so every angle is at most 45 degrees), an
+// entry dropped once it no longer changes either diagonal neighbour in fp64.  No square of an entry is formed -- theta is a
+// ratio --, so a matrix scaled by 2^200 or 2^-200 goes through like the unscaled one.  The order of operations is fixed: the same
+// input gives the same bits.
+int ehyb_sym_eig(int m, const double* T, int ldt, double* evals, double* Y)
+{
+    clear_error();
+    if (m < 1 || m > EHYB_EIGSH_MAX_BASIS + 1 || !T || ldt < m || !evals || !Y)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_sym_eig: bad arguments (m %d, 1 .. %d; ldt %d)", m, EHYB_EIGSH_MAX_BASIS + 1, ldt);
+    std::vector<double> A((size_t)m * m), Q((size_t)m * m, 0.0);
+    for (int j = 0; j < m; ++j)
+        for (int i = 0; i <= j; ++i) {
+            const double v = T[(size_t)j * ldt + i];
+            if (!std::isfinite(v)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_sym_eig: entry (%d, %d) is not finite", i, j);
+            A[(size_t)j * m + i] = A[(size_t)i * m + j] = v;
+        }
+    for (int i = 0; i < m; ++i) Q[(size_t)i * m + i] = 1.0;
+    auto a = [&](int i, int j) -> double& { return A[(size_t)j * m + i]; };
+    for (int sweep = 0; sweep < 100; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p + 1 < m; ++p)
+            for (int q = p + 1; q < m; ++q) {
+                const double apq = a(p, q);
+                if (apq == 0.0) continue;
+                const double app = a(p, p), aqq = a(q, q), g = std::fabs(apq);
+                if (std::fabs(app) + g == std::fabs(app) && std::fabs(aqq) + g == std::fabs(aqq)) {
+                    a(p, q) = a(q, p) = 0.0;
+                    continue;
+                }
+                const double theta = (aqq - app) / (2.0 * apq), tt = theta * theta;
+                const double t = std::isfinite(tt) ? (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(tt + 1.0)) : 0.5 / theta;
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                a(p, p) = app - t * apq;
+                a(q, q) = aqq + t * apq;
+                a(p, q) = a(q, p) = 0.0;
+                for (int k = 0; k < m; ++k) {
+                    if (k != p && k != q) {
+                        const double akp = a(k, p), akq = a(k, q);
+                        a(k, p) = a(p, k) = c * akp - s * akq;
+                        a(k, q) = a(q, k) = s * akp + c * akq;
+                    }
+                    const double qkp = Q[(size_t)p * m + k], qkq = Q[(size_t)q * m + k];
+                    Q[(size_t)p * m + k] = c * qkp - s * qkq;
+                    Q[(size_t)q * m + k] = s * qkp + c * qkq;
+                }
+                rotated = true;
+            }
+        if (!rotated) break;
+    }
+    std::vector<int> order(m);
+    for (int i = 0; i < m; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return a(x, x) < a(y, y); });
+    for (int i = 0; i < m; ++i) {
+        evals[i] = a(order[i], order[i]);
+        memcpy(Y + (size_t)i * m, &Q[(size_t)order[i] * m], (size_t)m * sizeof(double));
+    }
+    return EHYB_OK;
+}
+
 }  // extern "C"
 
 // C++-linkage names of reordering.h (reference reordering.h:6-10).

@@ -621,6 +621,44 @@ class Plan:
         those of the device."""
         return self._solve("ehyb_gmres", b, x0, inv_diag, (int(restart), int(ortho_passes), max_iter, rtol), stream, allow_breakdown)
 
+    def eigsh(self, nev, which="LA", basis=0, max_restarts=300, tol=1e-10, scale=None, v0=None, vectors=True, allow_breakdown=False,
+              stream=0):
+        """ehyb_eigsh: the nev (1 .. 16) largest ("LA") or smallest ("SA") algebraic eigenvalues of the plan's symmetric matrix
+        and their eigenvectors by thick-restart Lanczos on the device; with `scale` of S A S, S = diag(scale).  basis 0 =
+        min(max(2 nev + 1, 20), 64), at most 64; scale, v0 (None: the start vector of lambda_max) and the vectors in the
+        permuted numbering.  -> (evals (found,), evecs (found, n) or None, info) with info = {"found", "nconv", "multiplies",
+        "restarts", "resid" (found,)}; nconv < found means max_restarts ran out.  A multiple eigenvalue is found once.  A
+        breakdown (a non-finite quantity) raises EhybError, unless allow_breakdown: then found = nconv = 0 and evals, evecs are empty."""
+        n, nev = self.n, int(nev)
+        ldv = n + (n & 1)
+        ds = None if scale is None else DeviceBuffer(n).upload(scale)
+        d0 = None if v0 is None else DeviceBuffer(n).upload(v0)
+        dv = None
+        if vectors:
+            dv = DeviceBuffer(max(nev, 1) * ldv).upload(np.zeros(max(nev, 1) * ldv))
+        evals, resid = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        found, nconv, mult, rest = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self.lib.ehyb_eigsh(self.h, C.c_void_p(ds.ptr) if ds else None, C.c_void_p(d0.ptr) if d0 else None, nev,
+                                 {"LA": 0, "SA": 1}[which], int(basis), int(max_restarts), tol, _ptr(evals, C.c_double),
+                                 C.c_void_p(dv.ptr) if dv else None, ldv, C.c_void_p(stream), C.byref(found), C.byref(nconv),
+                                 C.byref(mult), C.byref(rest), _ptr(resid, C.c_double))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, "ehyb_eigsh")
+        f = found.value
+        info = {"found": f, "nconv": nconv.value, "multiplies": mult.value, "restarts": rest.value, "resid": resid[:f].copy()}
+        X = dv.download().reshape(-1, ldv)[:f, :n].copy() if dv else None
+        return evals[:f].copy(), X, info
+
+    def spectrum_bounds(self, inv_diag=None, tol=1e-4, stream=0):
+        """(lmin, lmax) of D^-1 A (inv_diag None: of A) from two eigsh calls with scale = sqrt(inv_diag): the smallest and the
+        largest Ritz value at relative residual tol.  Ritz values approach the ends of the spectrum FROM INSIDE: lmin is never
+        below the smallest eigenvalue and lmax never above the largest (in exact arithmetic), each off by at most tol * |lmax|.
+        A caller that needs an enclosing interval widens it by that margin."""
+        scale = None if inv_diag is None else np.sqrt(np.asarray(inv_diag, dtype=np.float64))
+        lo = self.eigsh(1, "SA", tol=tol, scale=scale, vectors=False, stream=stream)[0]
+        hi = self.eigsh(1, "LA", tol=tol, scale=scale, vectors=False, stream=stream)[0]
+        return float(lo[0]), float(hi[0])
+
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)

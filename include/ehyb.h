@@ -1218,6 +1218,84 @@ int ehyb_gmres_next_step(int n, int64_t ld, double* V_dev, const double* w_dev, 
 int ehyb_gmres_solve_x_step(int n, int64_t ld, const double* V_dev, const double* inv_diag_dev, double* x_dev, double* s_dev,
                             void* stream);
 
+/*
+ * The nev largest or smallest (algebraic) eigenvalues of the plan's SYMMETRIC matrix and their eigenvectors, by thick-restart
+ * Lanczos with full reorthogonalisation (classical Gram-Schmidt twice: the two passes of ehyb_gmres), the vectors on the device.
+ * With scale_dev the operator is S A S, S = diag(scale) -- scale = 1 / sqrt(diag) gives the spectrum of D^-1 A.  The host looks
+ * once per restart cycle: it solves the projected problem (at most 64 x 64, ehyb_sym_eig), decides convergence and uploads the
+ * rotation.  Ritz values approach the ends of the spectrum from inside.  A MULTIPLE eigenvalue is found ONCE: this is Lanczos
+ * from one start vector, whose Krylov space holds one vector of every eigenspace; no locking and no block version exist.
+ *   nev 1 .. EHYB_EIGSH_MAX_NEV; which EHYB_EIG_LARGEST / _SMALLEST; basis 0 = min(max(2 nev + 1, 20), 64), else
+ *   nev + 2 .. EHYB_EIGSH_MAX_BASIS; the effective basis m = min(basis, n); keep = nev + (m - nev) / 2 (ehyb_eigsh_basis).
+ *   Start vector: v0_dev, NULL = that of ehyb_lambda_max, v_i = 1 + (i mod 7) / 8; normalised to v_0.  A zero or non-finite
+ *     norm: breakdown.
+ *   Step j (the basis holds v_0 .. v_j; k kept vectors, 0 in the first cycle; j = k .. m - 1): z = scale o v_j, w = A z,
+ *     w = scale o w (the scalings only with scale_dev).  Twice: c_i = v_i.w for i <= j, all from the same w; w -= sum c_i v_i;
+ *     h_i += c_i.  beta^2 = w.w.  Column j of the projected matrix: T[i, j] = T[j, i] = h_i.  Any non-finite h or beta^2:
+ *     breakdown.  beta^2 <= 2^-90 (h.h + beta^2) -- the orthogonalisation removed all but 2^-45 of w --: an invariant subspace;
+ *     the step counts, the cycle ends with J = j + 1 basis vectors and beta = 0, no v_{j+1} is written.  Else
+ *     v_{j+1} = w / beta, a true division.
+ *   Cycle end, J basis vectors (m unless invariant), on the host: the eigenpairs (theta, Y) of T[:J, :J], sorted from the wanted
+ *     end (falling for LARGEST, rising for SMALLEST); res_i = |beta Y[J-1, i]|; want = min(nev, J); nconv = the number of
+ *     leading pairs with res_i <= tol max_l |theta_l|, counting stops at the first that fails.  Stop when nconv == want, the
+ *     subspace was invariant, or max_restarts restarts have been made.
+ *   Restart: kk = min(keep, J - 1); new v_i = sum_l Y[l, i] v_l for i < kk, new v_kk = old v_J; T = diag(theta_0 .. theta_{kk-1});
+ *     the next cycle starts at j = kk and its first column re-measures the arrow entries c_i ~ beta Y[J-1, i] through the full
+ *     orthogonalisation: the host never plants them.
+ * Outputs: evals[i] = theta_i for i < want; evecs_dev column i (at evecs_dev + i ldv) = sum_l Y[l, i] v_l, unit length, in the
+ * permuted numbering; resid[i] = res_i; *found = want; *nconv, *multiplies (the number of A z), *restarts.  Host outputs may be
+ * NULL, evecs_dev may be NULL (values only); ldv even and >= n, evecs_dev, scale_dev and v0_dev 16-byte aligned.  stream NULL = a
+ * private stream.  EHYB_OK also when nconv < nev after max_restarts (as the solvers at max_iter) and when an invariant subspace
+ * holds fewer than nev pairs.  A non-finite quantity: EHYB_ERR_ARG with "breakdown" in ehyb_last_error after every output is
+ * written -- found = nconv = 0, evecs_dev untouched.
+ * Per step: one multiply (walks alternating), with scale_dev one streaming kernel w = scale o w, then dots, update, dots, update
+ * (the kernels of ehyb_gmres on its slots and tail) and next.  The first cycle (j = 0 .. m - 1) and a cycle after a short restart
+ * (kk < keep) are plain launches; the steady cycle (j = keep .. m - 1) is captured once as a linear hipGraph and replayed
+ * (cfg.graphs = 2: plain launches).  After a stop inside a cycle the remaining vector kernels return at once.  A restart is one
+ * launch of the rotation kernel into a second buffer of keep + 1 columns and one device-to-device copy back; the final Ritz
+ * vectors are the same kernel writing into evecs_dev.  The host arithmetic is deterministic and every device sum is re-added
+ * from per-workgroup partials in a fixed order: with plain storage every output is the same bits from run to run, for graphs and
+ * plain launches, for a given or a private stream; with symmetric pair storage or a panel-form residual up to the order of
+ * summation.  The solver only calls the multiply, so every plan form works, cfg.val_f32 included.
+ * EHYB_ERR_ARG, in this order and before any device work: a null plan; nev, which, basis outside their ranges or
+ * max_restarts < 0; a negative or NaN tol; a plan not over all rows; an odd ldv or one below n with a non-NULL evecs_dev; a
+ * misaligned evecs_dev, scale_dev or v0_dev.  Then EHYB_ERR_STATE on a plan never uploaded.
+ *
+ * ehyb_eigsh_basis (host only): *m = the effective basis for (nev, basis, n), *keep = nev + max(m - nev, 0) / 2; either may be
+ * NULL.  No argument check.
+ *
+ * ehyb_sym_eig (host only, no device): the eigenpairs of the dense symmetric m x m matrix T (column-major, leading dimension
+ * ldt, only the upper triangle i <= j is read), 1 <= m <= EHYB_EIGSH_MAX_BASIS + 1.  evals rising; Y column-major with leading
+ * dimension m, orthonormal, column i the vector of evals[i].  Cyclic Jacobi in a fixed order: the same input gives the same bits.
+ * EHYB_ERR_ARG for m out of range, ldt < m, a null pointer or a non-finite entry.
+ *
+ * The three new kernels one launch each with slot_doubles / 2 workgroups, on the slots and tail of ehyb_gmres_layout; vectors and
+ * leading dimensions as the ehyb_gmres_*_step calls.  next and scale return at once, writing nothing, when the status is not
+ * status_running; rotate does not look at it.
+ *   next    j = -1: w.w from slot_ww; zero or non-finite: status_breakdown; else gt_at + 0 = sqrt(w.w), v_0 = w / sqrt(w.w) into
+ *           column 0, z = scale o v_0 (scale_dev NULL: z = v_0).  j = 0 .. 63: beta^2 from slot_ww, h_0 .. h_j from Hessenberg
+ *           copy 1; the rules of step j above: R[0 .. j, j] = h, gt_at + j + 1 = beta (0 if invariant), counter + 1; invariant
+ *           sets status_converged, breakdown sets status_breakdown and writes nothing else; else column j + 1 and z.
+ *   scale   w = scale o w
+ *   rotate  dst[:, c] = sum_{l < mc} Y[l, c] src[:, l] for c < kc, the sum in rising l; mc 1 .. 65, kc 1 .. 64; Y_dev column-major
+ *           with leading dimension mc; src and dst must not overlap, each with its own even leading dimension >= n.
+ * EHYB_ERR_ARG for n < 0, a null pointer that would be used, j, mc or kc outside its range, an odd leading dimension or one
+ * below n, a misaligned vector.  All asynchronous on `stream`.
+ */
+#define EHYB_EIGSH_MAX_BASIS 64
+#define EHYB_EIGSH_MAX_NEV 16
+enum { EHYB_EIG_LARGEST = 0, EHYB_EIG_SMALLEST = 1 };
+int ehyb_eigsh(ehyb_plan* plan, const double* scale_dev, const double* v0_dev, int nev, int which, int basis, int max_restarts,
+               double tol, double* evals, double* evecs_dev, int64_t ldv, void* stream, int* found, int* nconv, int* multiplies,
+               int* restarts, double* resid);
+int ehyb_eigsh_basis(int nev, int basis, int n, int* m, int* keep);
+int ehyb_sym_eig(int m, const double* T, int ldt, double* evals, double* Y);
+int ehyb_eigsh_next_step(int n, int64_t ld, double* V_dev, const double* w_dev, const double* scale_dev, double* z_dev,
+                         double* s_dev, int j, void* stream);
+int ehyb_eigsh_scale_step(int n, const double* scale_dev, double* w_dev, double* s_dev, void* stream);
+int ehyb_eigsh_rotate_step(int n, int64_t ld_src, const double* src_dev, int64_t ld_dst, double* dst_dev, const double* Y_dev,
+                           int mc, int kc, void* stream);
+
 /* -------------------------------------------- harness pieces (solver_test.c) */
 
 /*
