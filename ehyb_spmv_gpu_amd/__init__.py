@@ -15,6 +15,7 @@ from .host import (  # noqa: F401
     EHYB_WINDOW_HALO,
     EHYB_WINDOW_REFERENCE,
     KERNEL_TABLES,
+    Coarse,
     DeviceBuffer,
     EhybError,
     Matrix,

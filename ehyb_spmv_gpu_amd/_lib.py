@@ -264,6 +264,18 @@ SIGNATURES = {
                                       C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_cheb_start_step": (C.c_int, [C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_cheb_step": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_coarse_map": (C.c_int, [_mp, C.c_int, C.c_int, _P(C.c_int32), _ip]),
+    "ehyb_coarse_create_host": (C.c_int, [_mp, _P(C.c_int32), C.c_int, _P(_vp)]),
+    "ehyb_coarse_create_raw": (C.c_int, [C.c_int, _P(C.c_int32), C.c_int, _dp, _P(_vp)]),
+    "ehyb_coarse_upload": (C.c_int, [_vp]),
+    "ehyb_coarse_destroy": (None, [_vp]),
+    "ehyb_coarse_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
+    "ehyb_coarse_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ehyb_pcg_coarse": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_pcg_coarse_multi": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_coarse_restrict_step": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ehyb_coarse_solve_step": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ehyb_coarse_prolong_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_bicgstab_layout": (C.c_int, [_P(BicgstabSlots)]),
     "ehyb_bicgstab_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),

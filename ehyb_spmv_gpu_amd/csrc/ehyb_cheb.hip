@@ -25,6 +25,7 @@
 
 #include "cg_shared.h"
 #include "ehyb_internal.h"
+#include "pcg_loop.h"
 #include "solve_loop.h"
 
 using namespace ehyb;
@@ -199,8 +200,6 @@ __global__ __launch_bounds__(kThreads) void lambda_step_kernel(int n, double* __
     }
 }
 
-inline int walk_of(int index) { return (index & 1) ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST; }
-
 // in this order, all EHYB_ERR_ARG: the degree, the bounds, the polynomial's plan
 int cheb_args(const char* who, const ehyb_plan* P, const ehyb_plan* poly, int degree, double lmin, double lmax)
 {
@@ -214,120 +213,48 @@ int cheb_args(const char* who, const ehyb_plan* P, const ehyb_plan* poly, int de
     return EHYB_OK;
 }
 
-// The one driver: k solves that share Q = A P and the polynomial's multiplies (ehyb_spmm with explicit walks; its pass of width 1
-// is ehyb_spmv_walk).  The arguments are checked (ehyb_pcg_cheb, ehyb_pcg_cheb_multi).
+// The one driver: the loop of pcg_loop.h with the polynomial as its preconditioner, whose multiplies are ehyb_spmm with explicit
+// walks too.  The arguments are checked (ehyb_pcg_cheb, ehyb_pcg_cheb_multi).
 int cheb_solve(const char* who, ehyb_plan* P, ehyb_plan* poly, const double* dinv, const double* B, int64_t ldb, double* X, int64_t ldx,
                int k, int degree, double lmin, double lmax, int max_iter, double rtol, int check_every, void* stream, int* iters_done,
                double* rel_residual)
 {
     const int n = P->host.n_cols;
-    SolveLoop L(n, check_every);
-    const int grid = L.grid;
-    double *R, *Pd, *Q, *D, *Z, *W, *s;
-    HIP_TRY(L.begin(stream, {&R, &Pd, &Q, &D, &Z, &W}, (size_t)n * k, &s, (size_t)k * A_COUNT, (k + 1) / 2));  // the active flags behind the slots
-    int* active = (int*)(s + (size_t)k * A_COUNT * kMaxGrid);
-    const hipStream_t st = L.st;
-
-    int rc;
-    if (!(lmax > 0)) {
-        double lam = 0.0;
-        if ((rc = ehyb_lambda_max(poly, dinv, 20, st, &lam)) != EHYB_OK) return rc;
-        lmax = 1.1 * lam;
-    }
-    if (!(lmin > 0)) lmin = lmax / 30.0;
+    double *D, *W;
     double coef0, ca[EHYB_CHEB_MAX_DEGREE], cb[EHYB_CHEB_MAX_DEGREE];
-    if ((rc = ehyb_cheb_coeffs(lmin, lmax, degree, &coef0, ca, cb)) != EHYB_OK) return rc;  // (lmin >= an estimated lmax ends here)
-
+    auto prepare = [&](const PcgState& S) -> int {
+        int rc;
+        if (!(lmax > 0)) {
+            double lam = 0.0;
+            if ((rc = ehyb_lambda_max(poly, dinv, 20, S.st, &lam)) != EHYB_OK) return rc;
+            lmax = 1.1 * lam;
+        }
+        if (!(lmin > 0)) lmin = lmax / 30.0;
+        return ehyb_cheb_coeffs(lmin, lmax, degree, &coef0, ca, cb);  // (lmin >= an estimated lmax ends here)
+    };
     // The multiplies of an iteration state their walks, alternating along the sequence each plan sees: with one plan for both,
-    // 1 + degree multiplies per iteration; with two, one on the plan and degree on the polynomial's.  it = -1: the set-up, whose
-    // last multiply walks against the first of iteration 0, which then starts on what it left in the caches.
+    // 1 + degree multiplies per iteration; with two, one on the plan and degree on the polynomial's.
     const bool same = poly == P;
     auto plan_walk = [&](int it) { return walk_of(same ? it * (degree + 1) : it); };
     auto poly_walk = [&](int it, int j) { return walk_of(same ? it * (degree + 1) + j : it * degree + j - 1); };
-    // Z = M^-1 R for the live columns, the partials of r.z in slot number rz
-    auto precondition = [&](int it, int rz) -> int {
+    // Z = M^-1 R for the live columns, the partials of r.z in slot number rz; t shares the vector of q
+    auto precondition = [&](const PcgState& S, int it, int rz) -> int {
         for_each_group(k, [&](auto K, int c0) {
-            hipLaunchKernelGGL(cheb_multi_start_kernel<decltype(K)::value>, dim3(grid), dim3(kThreads), 0, st, n, R, dinv, coef0, D, Z, s,
-                               active, c0, degree == 0 ? rz : -1);
+            hipLaunchKernelGGL(cheb_multi_start_kernel<decltype(K)::value>, dim3(S.grid), dim3(kThreads), 0, S.st, n, S.R, dinv, coef0, D, S.Z,
+                               S.s, S.active, c0, degree == 0 ? rz : -1);
         });
         for (int j = 1; j <= degree; ++j) {
-            const int e = ehyb_spmm(poly, D, n, Q, n, k, st, poly_walk(it, j));  // T = A~ D in q's vector, frozen columns included
+            const int e = ehyb_spmm(poly, D, n, S.Q, n, k, S.st, poly_walk(it, j));  // T = A~ D in q's vector, frozen columns included
             if (e != EHYB_OK) return e;
             for_each_group(k, [&](auto K, int c0) {
-                hipLaunchKernelGGL(cheb_multi_step_kernel<decltype(K)::value>, dim3(grid), dim3(kThreads), 0, st, n, j == 1 ? R : W, Q, dinv,
-                                   ca[j - 1], cb[j - 1], W, D, Z, R, s, active, c0, j == degree ? rz : -1);
+                hipLaunchKernelGGL(cheb_multi_step_kernel<decltype(K)::value>, dim3(S.grid), dim3(kThreads), 0, S.st, n, j == 1 ? S.R : W, S.Q,
+                                   dinv, ca[j - 1], cb[j - 1], W, D, S.Z, S.R, S.s, S.active, c0, j == degree ? rz : -1);
             });
         }
         return EHYB_OK;
     };
-
-    if ((rc = ehyb_spmm(P, X, ldx, Q, n, k, st, plan_walk(-1))) != EHYB_OK) return rc;  // Q = A X0
-    for (int j = 0; j < k; ++j)  // r = b - q, p = r; partials of r.r (twice) and b.b
-        cg_launch_init(grid, st, n, B + (size_t)j * ldb, Q + (size_t)j * n, nullptr, R + (size_t)j * n, Pd + (size_t)j * n,
-                       s + (size_t)j * A_COUNT * kMaxGrid);
-    HIP_TRY(L.read());
-    std::vector<double> bb(k), rs(k);
-    std::vector<int> live(k), iters(k, 0);
-    int n_live = 0;
-    for (int j = 0; j < k; ++j) {
-        const double bb0 = L.sum(j * A_COUNT + A_BB);
-        bb[j] = bb0 > 0 ? bb0 : 1.0;
-        rs[j] = L.sum(j * A_COUNT + A_RR);
-        live[j] = std::sqrt(rs[j] / bb[j]) > rtol;  // (NaN: frozen at once, reported as a breakdown)
-        n_live += live[j];
-    }
-    HIP_TRY(hipMemcpyAsync(active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
-    // p = z = M^-1 r; a column frozen from the start keeps p = 0 (the multiplies go over it)
-    for (double* v : {D, Z, W}) HIP_TRY(hipMemsetAsync(v, 0, (size_t)n * k * sizeof(double), st));
-    if ((rc = precondition(-1, 0)) != EHYB_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(Pd, Z, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, st));
-
-    int it = 0;
-    rc = L.run(
-        P, max_iter, it, [&] { return n_live > 0; },
-        [&](int cur, bool) -> int {
-            // the plain launches (cfg.graphs = 2, the odd last iteration) are the captured ones
-            int e = ehyb_spmm(P, Pd, n, Q, n, k, st, plan_walk(cur));  // Q = A P, frozen columns included (their q is not read)
-            if (e != EHYB_OK) return e;
-            for_each_group(k, [&](auto K, int c0) {
-                cg_launch_dot(decltype(K)::value, grid, st, n, Pd, Q, s, active, c0);
-                cg_launch_update(decltype(K)::value, grid, st, n, Pd, Q, nullptr, X, ldx, R, s, active, c0, cur);
-            });
-            if ((e = precondition(cur, cur ^ 1)) != EHYB_OK) return e;
-            for_each_group(k, [&](auto K, int c0) { cg_launch_direction(decltype(K)::value, grid, st, n, Z, nullptr, Pd, s, active, c0, cur); });
-            return EHYB_OK;
-        },
-        [&](int cur) -> int {
-            bool changed = false;
-            for (int j = 0; j < k; ++j) {
-                if (!live[j]) continue;
-                rs[j] = L.sum(j * A_COUNT + A_RR);
-                const double rz = L.sum(j * A_COUNT + A_RZ0 + 2 * cur);
-                // breakdown of this column (frozen, the others go on): a NaN, or -- short of convergence -- an r.z that is
-                // not positive: the polynomial was not positive on the spectrum (lmax below the largest eigenvalue)
-                if (!(rs[j] == rs[j]) || !(rz == rz) || (std::sqrt(rs[j] / bb[j]) > rtol && !(rz > 0))) rs[j] = NAN;
-                if (!(std::sqrt(rs[j] / bb[j]) > rtol)) {
-                    live[j] = 0;
-                    iters[j] = it;
-                    --n_live;
-                    changed = true;
-                }
-            }
-            if (changed && n_live > 0) HIP_TRY(hipMemcpyAsync(active, live.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st));
-            return EHYB_OK;
-        });
-    if (rc != EHYB_OK) return rc;
-    bool broke = false;
-    for (int j = 0; j < k; ++j) {
-        if (live[j]) iters[j] = it;
-        if (iters_done) iters_done[j] = iters[j];
-        if (rel_residual) rel_residual[j] = std::sqrt(rs[j] / bb[j]);
-        broke = broke || !(rs[j] == rs[j]);
-    }
-    if (broke)
-        EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown%s (is the matrix symmetric positive definite, and lmax an upper bound?)", who,
-                  k > 1 ? " in a column" : "");
-    return EHYB_OK;
+    return pcg_solve(who, "is the matrix symmetric positive definite, and lmax an upper bound?", P, B, ldb, X, ldx, k, max_iter, rtol,
+                     check_every, stream, iters_done, rel_residual, {{&D, (size_t)n * k}, {&W, (size_t)n * k}}, prepare, plan_walk, precondition);
 }
 
 }  // namespace

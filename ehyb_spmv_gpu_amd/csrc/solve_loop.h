@@ -114,6 +114,8 @@ public:
         if (e == hipSuccess && (e = alloc(s, h.size())) == hipSuccess) s_ = *s;
         return e;
     }
+    // one more vector of the solve's, of a length of its own
+    hipError_t more(double** p, size_t count) { return alloc(p, std::max<size_t>(1, count)); }
 
     // every launch so far checked, the slots copied into h, the stream drained
     hipError_t read()

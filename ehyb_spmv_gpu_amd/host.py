@@ -585,6 +585,18 @@ class Plan:
         return self._solve("ehyb_pcg_cheb_multi", B, X0, inv_diag, (int(degree), lmin, lmax, max_iter, rtol, check_every), stream,
                            allow_breakdown, multi=True, inner=poly_plan or self, counters=1)
 
+    def cg_coarse(self, b, coarse, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_pcg_coarse: CG on this plan with the two-level preconditioner z = inv_diag .* r + P E^-1 P^T r of `coarse` (a Coarse
+        of the reordered matrix this plan was built from).  -> (x, iterations, relative residual).  A breakdown raises
+        EhybError, unless allow_breakdown: then the residual is NaN."""
+        return self._solve("ehyb_pcg_coarse", b, x0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, inner=coarse, counters=1)
+
+    def cg_coarse_multi(self, B, coarse, X0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_pcg_coarse_multi: k independent cg_coarse solves that share every multiply; B, X0 (k, n), column j solved as
+        cg_coarse(B[j]) would -- with plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,))."""
+        return self._solve("ehyb_pcg_coarse_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True,
+                           inner=coarse, counters=1)
+
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
         b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative residual).  A breakdown raises EhybError,
@@ -662,6 +674,84 @@ class Plan:
     def destroy(self):
         if self.h:
             self.lib.ehyb_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+COARSE_ARRAYS = {"map": (0, np.int32), "row_ptr": (1, np.int32), "rows": (2, np.int32), "E": (3, np.float64), "Einv": (4, np.float64)}
+
+
+class Coarse:
+    """ehyb_coarse: the aggregate coarse space of Plan.cg_coarse for a reordered matrix -- the matrix the plan was built from.
+    map None: ehyb_coarse_map(matrix, agg_rows, dof) (agg_rows 0: chosen from the size); otherwise the caller's (n,) map, in the
+    permuted numbering like everything here.  upload=False keeps it on the host (no GPU needed)."""
+
+    def __init__(self, matrix, agg_rows=0, dof=1, map=None, upload=True):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self.n = matrix.n
+        if map is None:
+            map, nc = np.empty(max(self.n, 1), dtype=np.int32), C.c_int(0)
+            _check(self.lib.ehyb_coarse_map(C.byref(matrix.c), int(agg_rows), int(dof), _ptr(map, C.c_int32), C.byref(nc)), "ehyb_coarse_map")
+            map, nc = map[:self.n], nc.value
+        else:
+            map = np.ascontiguousarray(map, dtype=np.int32)
+            assert map.shape == (self.n,), (map.shape, self.n)
+            nc = int(map.max()) + 1 if self.n else 0
+        _check(self.lib.ehyb_coarse_create_host(C.byref(matrix.c), _ptr(map, C.c_int32), nc, C.byref(self.h)), "ehyb_coarse_create_host")
+        self.nc = nc
+        if upload:
+            self.upload()
+
+    @classmethod
+    def raw(cls, n, map, einv, upload=True):
+        """ehyb_coarse_create_raw: an object from a map and a caller's E^-1 (nc, nc) -- for tests of the kernels."""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.n = _lib.load(), C.c_void_p(), int(n)
+        map = np.ascontiguousarray(map, dtype=np.int32)
+        einv = np.ascontiguousarray(einv, dtype=np.float64)
+        self.nc = einv.shape[0]
+        assert map.shape == (self.n,) and einv.shape == (self.nc, self.nc)
+        _check(self.lib.ehyb_coarse_create_raw(self.n, _ptr(map, C.c_int32), self.nc, _ptr(einv, C.c_double), C.byref(self.h)),
+               "ehyb_coarse_create_raw")
+        if upload:
+            self.upload()
+        return self
+
+    def upload(self):
+        _check(self.lib.ehyb_coarse_upload(self.h), "ehyb_coarse_upload")
+        return self
+
+    def array(self, name):
+        """ehyb_coarse_host_array: "map" (n,), "row_ptr" (nc + 1,), "rows" (n,), "E" and "Einv" (nc, nc) -- copies"""
+        which, dtype = COARSE_ARRAYS[name]
+        p, cnt = C.c_void_p(), C.c_int64()
+        _check(self.lib.ehyb_coarse_host_array(self.h, which, C.byref(p), C.byref(cnt)), "ehyb_coarse_host_array")
+        if cnt.value == 0 or not p.value:
+            return np.zeros(0, dtype=dtype)
+        buf = (C.c_char * (cnt.value * np.dtype(dtype).itemsize)).from_address(p.value)
+        out = np.frombuffer(buf, dtype=dtype, count=cnt.value).copy()
+        return out.reshape(self.nc, self.nc) if name in ("E", "Einv") else out
+
+    def apply(self, r, inv_diag=None, stream=0):
+        """ehyb_coarse_apply: z = inv_diag .* r + P E^-1 P^T r for a host vector r (permuted numbering) -> z"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape == (self.n,)
+        dr, dz = DeviceBuffer(self.n).upload(r), DeviceBuffer(self.n)
+        dd = None if inv_diag is None else DeviceBuffer(self.n).upload(inv_diag)
+        _check(self.lib.ehyb_coarse_apply(self.h, C.c_void_p(dd.ptr) if dd else None, C.c_void_p(dr.ptr), C.c_void_p(dz.ptr), C.c_void_p(stream)),
+               "ehyb_coarse_apply")
+        _check(self.lib.ehyb_dev_sync(), "ehyb_dev_sync")
+        return dz.download()
+
+    def destroy(self):
+        if self.h:
+            self.lib.ehyb_coarse_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

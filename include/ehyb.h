@@ -1001,6 +1001,87 @@ int ehyb_cheb_step(int n, const double* w_in_dev, const double* t_dev, const dou
                    double* w_out_dev, double* d_dev, double* z_dev, const double* r_dev, double* s_dev, int rz, void* stream);
 
 /*
+ * Two-level PCG with an aggregate coarse space: what removes the low end of the spectrum of D^-1 A, which no polynomial in A
+ * reaches cheaply.  P is piecewise constant over aggregates of rows (Nicolaides' coarse grid correction, the two-level form of
+ * aggregation AMG), E = P^T A P is dense (nc x nc, nc <= EHYB_COARSE_MAX) and inverted once on the host, and
+ *   z = M^-1 r = D^-1 r + P E^-1 P^T r          (D^-1 = inv_diag, NULL: the identity)
+ * costs three small streaming kernels per iteration and no multiply.  The additive form only: z = c + D^-1 (r - A c) costs one
+ * more multiply and gave the same iteration counts to within 3 in a prototype.
+ *
+ * Everything lives in the numbering of the matrix after ehyb_matrix_reorder -- the matrix the plan was built from, with its
+ * partBoundary.  The host calls need no GPU; their results do not depend on the number of OpenMP threads (they run on the
+ * calling thread's OpenMP setting, capped by ehyb_host_threads()).
+ *
+ * ehyb_coarse_map: the default map, map_out[i] in [0, *nc_out) for every row i (map_out: n int32 of the caller's).
+ *   Growth.  For each partition [pb[p], pb[p+1]) in turn: the seed is the lowest row not yet in an aggregate; grow breadth-first
+ *   from it over the entries of the visited rows in stored order, skipping columns outside the partition and rows already taken,
+ *   until the aggregate holds agg_rows rows or the queue is empty; repeat until the partition is used up.
+ *   Fragments.  Visit the partition's aggregates in order of rising size as grown, ties by number.  One that now holds fewer
+ *   than agg_rows / 4 rows (4 rows < agg_rows) joins the aggregate of the same partition that its rows' entries point into most
+ *   often (ties: the lowest number) and takes its rows along; one with no such neighbour stays.  The survivors keep their order.
+ *   agg_rows <= 0: max(128, ceil(n dof / 1536)) -- the growth leaves about 5-10 % more aggregates than n / agg_rows, and the
+ *   headroom keeps nc below EHYB_COARSE_MAX.
+ *   dof > 1: the unknown of row i is the pair (aggregate, old(i) mod dof), old(i) the row's index before the reorder
+ *   (reorderList inverted): one constant per displacement component of a dof-unknowns-per-node FEM matrix.  Only pairs that
+ *   hold a row are numbered, in order of (aggregate, component).
+ *   No aggregate crosses a partition boundary, so an unknown's rows lie within a few thousand consecutive indices.
+ *   EHYB_ERR_ARG: a null pointer, dof < 1, a matrix without partition data, or nc > EHYB_COARSE_MAX -- the message names an
+ *   agg_rows that would fit.
+ * ehyb_coarse_create_host: the object for any map (nc in 1 .. EHYB_COARSE_MAX, every entry in range, no unknown empty: else
+ *   EHYB_ERR_ARG).  E_cd = sum of a_ij over map[i] = c, map[j] = d: row c takes the entries of its rows, rows rising, in stored
+ *   order; the lower triangle is mirrored, so E is symmetric bit for bit (the matrix is taken to be symmetric).  E = L L^T in
+ *   fp64, E^-1 = L^-T L^-1 stored full, its lower triangle computed and mirrored; a sum's terms are dealt to eight running
+ *   sums by their index and these added pairwise.  A pivot that is not a positive finite number: EHYB_ERR_ARG, "not positive
+ *   definite" in ehyb_last_error.
+ * ehyb_coarse_upload: MAP, ROW_PTR, ROWS and EINV to the device (EHYB_ERR_NO_DEVICE without one).  ehyb_coarse_destroy releases
+ *   both sides; NULL is allowed.
+ * ehyb_coarse_host_array: which = EHYB_COARSE_MAP int32[n], _ROW_PTR int32[nc + 1], _ROWS int32[n] (the transpose of MAP: the
+ *   rows of unknown c are ROWS[ROW_PTR[c] .. ROW_PTR[c + 1]), rising), _E double[nc * nc], _EINV double[nc * nc] (row-major).
+ *
+ * ehyb_coarse_apply: z = M^-1 r, three launches on the stream.  One apply at a time per object (it owns T and C).
+ *   restrict  T[c] = sum of r over the rows of unknown c        one wave per unknown
+ *   solve     C = E^-1 T                                        one wave per row, T staged in LDS
+ *   prolong   z[i] = inv_diag[i] r[i] + C[map[i]]               and, inside a solve, the partials of r.z
+ *   Every sum runs in a fixed order, without atomics.
+ * ehyb_pcg_coarse: x_dev, b_dev, stream, check_every, outputs and stopping as ehyb_pcg_cheb -- it is the same loop with another
+ *   preconditioner.  Per iteration: q = A p, p.q, the update kernel of ehyb_pcg without a preconditioner, restrict, solve,
+ *   prolong (which leaves the partials of r.z), the direction kernel p = z + beta p.  The multiplies state their walks,
+ *   alternating; an even and an odd iteration are replayed from one hipGraph, cfg.graphs = 2 issues the same launches
+ *   unrecorded.  With plain storage x, iters_done and rel_residual are the same bits from run to run, for graphs and plain
+ *   launches, on any stream.  Breakdown (EHYB_ERR_ARG, "breakdown" in ehyb_last_error, after every output is written,
+ *   rel_residual NaN): r.r or r.z NaN at a check point, or an r.z <= 0 there short of convergence.
+ *   In this order: EHYB_ERR_ARG for what ehyb_pcg rejects, then for a null coarse object or one with another number of rows;
+ *   EHYB_ERR_STATE for a plan, then a coarse object, that was never uploaded.  All before any device work.
+ * ehyb_pcg_coarse_multi is ehyb_pcg_multi with this preconditioner (k < 1 and ldb, ldx < n are rejected first); the kernels take
+ *   up to four columns per launch and share the index loads and the rows of E^-1.  With plain storage column j equals
+ *   ehyb_pcg_coarse on b_j bit for bit -- it is the same driver.
+ * ehyb_coarse_restrict_step / _solve_step / _prolong_step: the three kernels one launch at a time with the grids the solver
+ *   uses (prolong: slot_doubles / 2 workgroups, as ehyb_cheb_start_step).  t_dev and c_dev hold nc doubles.  rz = -1: no sum,
+ *   s_dev is not touched; rz = 0 / 1: the partials of r.z go to r.z slot number rz of ehyb_cg_layout.
+ * ehyb_coarse_create_raw (for tests of the kernels): an object from a map and a caller's E^-1 (nc * nc doubles, row-major)
+ *   for n rows; its _E array is empty.
+ */
+#define EHYB_COARSE_MAX 2048
+enum { EHYB_COARSE_MAP = 0, EHYB_COARSE_ROW_PTR = 1, EHYB_COARSE_ROWS = 2, EHYB_COARSE_E = 3, EHYB_COARSE_EINV = 4 };
+typedef struct ehyb_coarse ehyb_coarse;
+int  ehyb_coarse_map(const matrixCOO* m, int agg_rows, int dof, int32_t* map_out, int* nc_out);
+int  ehyb_coarse_create_host(const matrixCOO* m, const int32_t* map, int nc, ehyb_coarse** out);
+int  ehyb_coarse_upload(ehyb_coarse* c);
+void ehyb_coarse_destroy(ehyb_coarse* c);
+int  ehyb_coarse_host_array(const ehyb_coarse* c, int which, const void** ptr, int64_t* count);
+int  ehyb_coarse_apply(ehyb_coarse* c, const double* inv_diag_dev, const double* r_dev, double* z_dev, void* stream);
+int  ehyb_pcg_coarse(ehyb_plan* plan, ehyb_coarse* c, const double* inv_diag_dev, const double* b_dev, double* x_dev, int max_iter,
+                     double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+int  ehyb_pcg_coarse_multi(ehyb_plan* plan, ehyb_coarse* c, const double* inv_diag_dev, const double* B_dev, int64_t ldb, double* X_dev,
+                           int64_t ldx, int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done,
+                           double* rel_residual);
+int  ehyb_coarse_restrict_step(ehyb_coarse* c, const double* r_dev, double* t_dev, void* stream);
+int  ehyb_coarse_solve_step(ehyb_coarse* c, const double* t_dev, double* c_dev, void* stream);
+int  ehyb_coarse_prolong_step(ehyb_coarse* c, const double* r_dev, const double* inv_diag_dev, const double* c_dev, double* z_dev,
+                              double* s_dev, int rz, void* stream);
+int  ehyb_coarse_create_raw(int n, const int32_t* map, int nc, const double* einv, ehyb_coarse** out);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
