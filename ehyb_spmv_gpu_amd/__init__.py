@@ -14,6 +14,7 @@ from .host import (  # noqa: F401
     EHYB_PART_MULTILEVEL,
     EHYB_WINDOW_HALO,
     EHYB_WINDOW_REFERENCE,
+    KERNEL_TABLE_T,
     KERNEL_TABLES,
     Coarse,
     DeviceBuffer,
@@ -27,6 +28,7 @@ from .host import (  # noqa: F401
     entry_order,
     host_threads,
     kernel_table,
+    kernel_table_t,
     make_config,
     minres_inv_diag,
     partition_graph,

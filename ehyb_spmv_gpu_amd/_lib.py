@@ -195,6 +195,10 @@ SIGNATURES = {
     "ehyb_spmv": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_spmv_phase": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
     "ehyb_spmv_walk": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "ehyb_spmv_t": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ehyb_spmv_t_supported": (C.c_int, [_vp]),
+    "ehyb_debug_kernel_table_t": (C.c_int, [_P(C.c_int32), C.c_int, _ip]),
+    "ehyb_debug_launched_t": (C.c_int, [_vp, _P(C.c_uint8), C.c_int]),
     "ehyb_spmv_graph_create": (C.c_int, [_vp, _vp, _vp, C.c_int, _P(_vp)]),
     "ehyb_graph_launch": (C.c_int, [_vp, _vp]),
     "ehyb_graph_destroy": (None, [_vp]),
@@ -291,6 +295,7 @@ SIGNATURES = {
     "ehyb_minres_lanczos_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_minres_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
+    "ehyb_gmres_t": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
     "ehyb_gmres_layout": (C.c_int, [_P(GmresSlots)]),
     "ehyb_gmres_start_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_gmres_dots_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp]),

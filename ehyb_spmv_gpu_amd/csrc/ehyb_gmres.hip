@@ -2,7 +2,8 @@
 // M = diag(A): the method for the systems on which ehyb_bicgstab breaks down or diverges.  Unlike every other solver here it
 // keeps a GROWING set of vectors: the Arnoldi basis V, column-major, m + 1 columns with a leading dimension of n rounded up
 // to even, so that every column is 16-byte aligned.  Beside it two fixed vectors: z = M^-1 v_j, the multiply's input, and w,
-// its output.
+// its output.  ehyb_gmres_t is the same driver with one flag set: every multiply is ehyb_spmv_t, the system solved A^T x = b (the
+// diagonal of A^T is A's: M stays); its multiplies add with atomics, so its outputs are reproducible up to summation order only.
 //
 // A cycle: w = A x;  start: w = b - w, partials of w.w (= r.r) and b.b;  next(-1): v_0 = w / sqrt(r.r), z = M^-1 v_0;
 // then per step j = 0 .. m-1 one multiply and 2 * passes + 1 vector kernels
@@ -274,8 +275,9 @@ struct Launcher {
     void solve_x(double* x) const { hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, dinv, x, tail); }
 };
 
-int gmres_solve(ehyb_plan* P, const double* dinv, const double* b, double* x, int m, int passes, int max_iter, double rtol, void* stream,
-                int* iters_done, double* rel_residual)
+// transposed: every multiply is ehyb_spmv_t (A^T x = b; no walk: the transposed launch has none)
+int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double* b, double* x, int m, int passes, int max_iter, double rtol,
+                void* stream, int* iters_done, double* rel_residual)
 {
     const int n = P->host.n_cols;
     const size_t ld = (size_t)n + (n & 1);
@@ -290,14 +292,15 @@ int gmres_solve(ehyb_plan* P, const double* dinv, const double* b, double* x, in
     const double thr = rtol * rtol;
     HIP_TRY(hipMemsetAsync(tail, 0, (size_t)T_COUNT * sizeof(double), st));
 
+    const auto multiply = [&](const double* in, double* out, int walk) { return transposed ? ehyb_spmv_t(P, in, out, st) : ehyb_spmv_walk(P, in, out, st, walk); };
     // one cycle of `steps` steps; the multiplies walk last to first, then alternate
     auto cycle = [&](int steps) -> int {
-        int rc = ehyb_spmv_walk(P, x, w, st, EHYB_WALK_LAST_TO_FIRST);
+        int rc = multiply(x, w, EHYB_WALK_LAST_TO_FIRST);
         if (rc != EHYB_OK) return rc;
         K.start(b);
         K.next(-1, passes, thr);
         for (int j = 0; j < steps; ++j) {
-            rc = ehyb_spmv_walk(P, z, w, st, j & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
+            rc = multiply(z, w, j & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
             if (rc != EHYB_OK) return rc;
             for (int p = 0; p < passes; ++p) {
                 K.dots(j + 1);
@@ -337,9 +340,23 @@ int gmres_solve(ehyb_plan* P, const double* dinv, const double* b, double* x, in
     if (iters_done) *iters_done = f[F_ITERS];
     if (rel_residual) *rel_residual = std::sqrt(head[T_RHO] / head[T_BB]);
     if (f[F_STATUS] != ST_BREAKDOWN) return EHYB_OK;
-    EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres: breakdown after %d iterations (a non-finite b.b, r.r or Hessenberg entry, a zero or non-finite gamma, "
+    EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown after %d iterations (a non-finite b.b, r.r or Hessenberg entry, a zero or non-finite gamma, "
                             "or h_{j+1} = 0 short of convergence: a singular system)",
-              f[F_ITERS]);
+              transposed ? "ehyb_gmres_t" : "ehyb_gmres", f[F_ITERS]);
+}
+
+// the checks of both entry points, in the order ehyb.h states, then the solve
+int gmres_entry(const char* who, bool transposed, ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes,
+                int max_iter, double rtol, void* stream, int* iters_done, double* rel_residual)
+{
+    int rc = solve_args(who, P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK) return rc;
+    if (restart < 0 || restart > kM || ortho_passes < 0 || ortho_passes > 2)
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: restart %d (0 .. %d), ortho_passes %d (0 .. 2)", who, restart, kM, ortho_passes);
+    if (transposed && (rc = ehyb_spmv_t_supported(P)) != EHYB_OK) return rc;  // (the form is named in ehyb_last_error)
+    if ((rc = solve_uploaded(who, P)) != EHYB_OK) return rc;
+    return gmres_solve(P, transposed, dinv, b, x, restart == 0 ? 30 : restart, ortho_passes == 1 ? 1 : 2, max_iter, rtol, stream, iters_done,
+                       rel_residual);
 }
 
 }  // namespace
@@ -347,13 +364,13 @@ int gmres_solve(ehyb_plan* P, const double* dinv, const double* b, double* x, in
 extern "C" int ehyb_gmres(ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes, int max_iter,
                           double rtol, void* stream, int* iters_done, double* rel_residual)
 {
-    int rc = solve_args("ehyb_gmres", P, b && x, max_iter, rtol);
-    if (rc != EHYB_OK) return rc;
-    if (restart < 0 || restart > kM || ortho_passes < 0 || ortho_passes > 2)
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_gmres: restart %d (0 .. %d), ortho_passes %d (0 .. 2)", restart, kM, ortho_passes);
-    if ((rc = solve_uploaded("ehyb_gmres", P)) != EHYB_OK) return rc;
-    return gmres_solve(P, dinv, b, x, restart == 0 ? 30 : restart, ortho_passes == 1 ? 1 : 2, max_iter, rtol, stream, iters_done,
-                       rel_residual);
+    return gmres_entry("ehyb_gmres", false, P, dinv, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
+}
+
+extern "C" int ehyb_gmres_t(ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes, int max_iter,
+                            double rtol, void* stream, int* iters_done, double* rel_residual)
+{
+    return gmres_entry("ehyb_gmres_t", true, P, dinv, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
 }
 
 // ------------------------------------------------------------------ building blocks for a caller that owns the loop

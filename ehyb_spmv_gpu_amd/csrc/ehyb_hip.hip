@@ -289,6 +289,9 @@ static EllArgs ell_args(ehyb_plan* P, const double* x, double* y, unsigned long 
     return A;
 }
 
+// (the transposed window launch, ehyb_spmv_t.hip, takes the same arguments)
+EllArgs ehyb::window_launch_args(ehyb_plan* P, const double* x, double* y) { return ell_args(P, x, y, nullptr, nullptr); }
+
 // The walk of a launch: walk >= 0 the caller's explicit direction (ehyb_spmv_walk, ehyb_spmm), -1 the plan's own alternation.
 // (automatic: where the stream does not fit the cache but the cache is still a fair share of it -- the walk from the short slabs
 // up costs the tail of a workgroup a few per cent: audikw_1-like, 439 MB, 83.5 -> 76.0 us; every entry stored, 729 MB, 143.3 ->
@@ -1023,6 +1026,7 @@ int ehyb_debug_launched_clear(ehyb_plan* P)
     if (!P) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_launched_clear: null plan");
     for (int t = 0; t < kKernelTables; ++t)
         for (int i = 0; i < kKernelTableCap; ++i) __atomic_store_n(&P->launched[t][i], (uint8_t)0, __ATOMIC_RELAXED);
+    for (int i = 0; i < kKernelTableTCap; ++i) __atomic_store_n(&P->launched_t[i], (uint8_t)0, __ATOMIC_RELAXED);
     return EHYB_OK;
 }
 
@@ -1121,6 +1125,7 @@ int ehyb_plan_upload(ehyb_plan* P)
     for (const EllKernel& e : ell_kernels())
         if (!e.stamp) HIP_TRY(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));  // (a stamped launch opts in itself)
     for (const PanelKernel& e : panel_kernels()) HIP_TRY(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if ((rc = spmv_t_opt_in_lds()) != EHYB_OK) return rc;
     P->uploaded = true;
     return EHYB_OK;
 }

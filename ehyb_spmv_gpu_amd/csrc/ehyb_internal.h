@@ -392,6 +392,9 @@ inline uint64_t mix64(uint64_t z)
 // room for per table (ehyb_debug_kernel_table refuses a table that outgrew it: 96, 22 and 10 rows today).
 constexpr int kKernelTables = 3;
 constexpr int kKernelTableCap = 128;
+// The table of the transposed multiply (ehyb_spmv_t.hip, ehyb_debug_kernel_table_t: 7 rows) has a launch log of its own
+constexpr int kKernelTableTCap = 8;
+int spmv_t_opt_in_lds();  // ehyb_spmv_t.hip: the transposed window kernels opt in to the full LDS (ehyb_plan_upload)
 
 }  // namespace ehyb
 
@@ -446,6 +449,12 @@ struct ehyb_plan {
     void mark_launched(int which, size_t row)
     {
         if (row < (size_t)ehyb::kKernelTableCap) __atomic_store_n(&launched[which][row], (uint8_t)1, __ATOMIC_RELAXED);
+    }
+    // the same for the table of the transposed multiply (ehyb_debug_launched_t)
+    uint8_t launched_t[ehyb::kKernelTableTCap] = {};
+    void mark_launched_t(size_t row)
+    {
+        if (row < (size_t)ehyb::kKernelTableTCap) __atomic_store_n(&launched_t[row], (uint8_t)1, __ATOMIC_RELAXED);
     }
 };
 inline int ehyb::plan_spmm_width(const ehyb_plan* P) { return P->cfg.val_f32 == 1 ? 1 : spmm_width(P->host); }

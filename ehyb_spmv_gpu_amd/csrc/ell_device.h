@@ -671,4 +671,7 @@ int launch_window(ehyb_plan* P, const double* x, long long ldx, double* y, long 
 int launch_panel_k(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st, int walk);
 // The CSR-segment residual launch for k columns (none where the plan has no CSR segments)
 int launch_er_csr(ehyb_plan* P, const double* x, long long ldx, double* y, long long ldy, int k, hipStream_t st);
+// The kernel arguments of a one-vector window launch that walks first to last: the device arrays, the window capacity, the item
+// and XCD maps and the rule for which slabs are read with plain loads.  The transposed launch (ehyb_spmv_t.hip) takes the same.
+EllArgs window_launch_args(ehyb_plan* P, const double* x, double* y);
 }  // namespace ehyb

@@ -80,6 +80,21 @@ def kernel_table(name):
     return [tuple(int(v) for v in r) for r in rows]
 
 
+# the fields of a row of the transposed multiply's own table (ehyb_debug_kernel_table_t): kind 0 = window, 1 = residual
+KERNEL_TABLE_T = ("kind", "threads", "inl")
+
+
+def kernel_table_t():
+    """ehyb_debug_kernel_table_t -> the rows of the transposed multiply's kernel table as tuples of ints (KERNEL_TABLE_T names
+    the fields), in table order.  Needs no device."""
+    lib = _lib.load()
+    n = C.c_int(0)
+    _check(lib.ehyb_debug_kernel_table_t(None, 0, C.byref(n)), "ehyb_debug_kernel_table_t")
+    rows = np.zeros((n.value, len(KERNEL_TABLE_T)), dtype=np.int32)
+    _check(lib.ehyb_debug_kernel_table_t(_ptr(rows, C.c_int32), n.value, C.byref(n)), "ehyb_debug_kernel_table_t")
+    return [tuple(int(v) for v in r) for r in rows]
+
+
 def _view(ptr, count, dtype):
     if count == 0:
         return np.zeros(0, dtype=dtype)
@@ -434,6 +449,31 @@ class Plan:
         _check(self.lib.ehyb_spmv_phase(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), C.c_void_p(stream), phase),
                "ehyb_spmv")
 
+    def spmv_t(self, x_dev, y_dev, stream=0):
+        """Asynchronous y = A^T x on device pointers (ints), on this plan of A (ehyb_spmv_t): y is zeroed in-stream, then every
+        contribution is an atomic add.  Raises EhybError (code 1, the form named) on a plan spmv_t_supported refuses."""
+        _check(self.lib.ehyb_spmv_t(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), C.c_void_p(stream)), "ehyb_spmv_t")
+
+    @property
+    def spmv_t_supported(self):
+        """ehyb_spmv_t_supported: plain storage over all rows with fp64 values and no panel-form residual.  Host only; the reason
+        of a False is in ehyb_last_error (spmv_t_refusal)."""
+        return self.lib.ehyb_spmv_t_supported(self.h) == 0
+
+    @property
+    def spmv_t_refusal(self):
+        """(status, message) of ehyb_spmv_t_supported: (0, "") or (1, the form that is not served)"""
+        rc = self.lib.ehyb_spmv_t_supported(self.h)
+        return rc, (self.lib.ehyb_last_error().decode(errors="replace") if rc else "")
+
+    def launched_t(self):
+        """ehyb_debug_launched_t -> the set of rows of kernel_table_t() this plan's transposed launches took since the plan was
+        made or launched_clear()"""
+        rows = kernel_table_t()
+        log = np.zeros(len(rows), dtype=np.uint8)
+        _check(self.lib.ehyb_debug_launched_t(self.h, _ptr(log, C.c_uint8), len(log)), "ehyb_debug_launched_t")
+        return {rows[i] for i in np.flatnonzero(log)}
+
     def spmm(self, x_dev, y_dev, k, ldx=None, ldy=None, stream=0, walk=None):
         """Asynchronous Y[:, j] = A X[:, j], j < k, on device pointers (ints; column j at X + j*ldx, Y + j*ldy; None = n) --
         ehyb_spmm: ceil(k / spmm_max_k) passes over the matrix, a panel-form residual's two passes as wide as the window launch.
@@ -632,6 +672,12 @@ class Plan:
         residual).  A breakdown raises EhybError, unless allow_breakdown: then x is the last good iterate and the counts are
         those of the device."""
         return self._solve("ehyb_gmres", b, x0, inv_diag, (int(restart), int(ortho_passes), max_iter, rtol), stream, allow_breakdown)
+
+    def gmres_t(self, b, x0=None, restart=30, ortho_passes=2, max_iter=1000, rtol=1e-10, inv_diag=None, allow_breakdown=False, stream=0):
+        """ehyb_gmres_t: gmres for the adjoint system A^T x = b on this plan of A (every multiply a spmv_t); arguments and
+        results as gmres, inv_diag the same vector (A^T has A's diagonal).  Reproducible up to the order of summation only.
+        Raises EhybError (code 1) before any launch on a plan spmv_t_supported refuses."""
+        return self._solve("ehyb_gmres_t", b, x0, inv_diag, (int(restart), int(ortho_passes), max_iter, rtol), stream, allow_breakdown)
 
     def eigsh(self, nev, which="LA", basis=0, max_restarts=300, tol=1e-10, scale=None, v0=None, vectors=True, allow_breakdown=False,
               stream=0):

@@ -545,6 +545,40 @@ int ehyb_graph_launch(ehyb_graph* graph, void* stream);
 void ehyb_graph_destroy(ehyb_graph* graph);
 
 /*
+ * THE TRANSPOSED MULTIPLY y = A^T x on the plan A already has, in the permuted numbering: no second plan, no second reorder, no
+ * second copy of the matrix on the device.  x_dev holds n_rows doubles, y_dev n_cols (the matrix is square).  Asynchronous on
+ * `stream`; may be captured in a hipGraph.  y is ASSIGNED: the call first zeroes y in-stream (a memset node in a captured graph),
+ * and every contribution to it is then an fp64 atomic add.  x_dev == y_dev is rejected (EHYB_ERR_ARG).
+ *   Window plans: the work items, segments, item map and the plain / non-temporal split of the value stream are those of
+ *   ehyb_spmv's window launch.  The LDS window of a partition (own rows plus halo) holds accumulators instead of x: a lane loads
+ *   x[its row] once per slab and adds value * x[row] to the window column of each of its entries (ds_add_f64; lanes that share a
+ *   column list -- the unknowns of a node -- are summed across lanes first, one add for three), pair, relative and triple-coded
+ *   column words alike; the window is then added to y (global_atomic_add_f64), own columns and halo columns.  An
+ *   inline residual adds its products straight to y[column].  x is not staged: the LDS of the launch is that of ehyb_spmv.
+ *   A CSR residual and the direct shape: every lane of the row-segment kernel adds value * x[row] to y[column]; on a window plan
+ *   this launch follows the window launch, on a direct-shape plan it is the whole multiply.
+ * Served: plain storage over all rows with fp64 values.  Refused with EHYB_ERR_ARG before any device work, y untouched and the
+ * form named in ehyb_last_error: symmetric pair storage (for a symmetric matrix A^T = A: call ehyb_spmv; the form's LDS has no
+ * room for halo accumulators), a residual in panel form, cfg.val_f32 = 1, a plan not over all rows, a plan with column segments --
+ * checked in this order, after null pointers and x == y.  Then EHYB_ERR_STATE on a plan never uploaded.
+ * ehyb_spmv_t_supported applies the same rule on the host (EHYB_OK or EHYB_ERR_ARG with the form named); it works on a plan that
+ * was never uploaded.
+ * Contract.
+ *   Order.  The LDS and global adds arrive in an order that varies from run to run: a result is reproducible only up to the order
+ *   of summation, as with symmetric pair storage under ehyb_spmv.  Where every product and partial sum is exact (integer data) it
+ *   is bit-exact.  A column that receives nothing, or only zeros, is +0.0.
+ *   Range.  Subnormal values, x entries, products and sums are kept (ds_add_f64 and global_atomic_add_f64 keep them on gfx950).
+ *   Non-finite values.  A non-finite MATRIX value reaches exactly the columns of the rows that store it.  A non-finite x[i] makes
+ *   every column that row i stores non-finite (a NaN is never lost; an infinity may come out as NaN).  Through padding slots
+ *   (value 0.0: 0 * inf and 0 * NaN are NaN) it may additionally turn NaN the columns 0 to 2 of row i's window -- in a slab with
+ *   relative columns: column i itself --, and with an inline residual y[0].  This is the transposed image of the rule under
+ *   ehyb_spmv.  With every x finite no padding slot changes a result.
+ * One multiply at a time per y; several host threads may multiply with one plan on their own streams and vectors.
+ */
+int ehyb_spmv_t(ehyb_plan* plan, const double* x_dev, double* y_dev, void* stream);
+int ehyb_spmv_t_supported(const ehyb_plan* plan);
+
+/*
  * SEVERAL VECTORS per pass over the matrix: Y[:, j] = A X[:, j] for j < k.  X, Y: device pointers, column j at X + j*ldx and
  * Y + j*ldy (column-major: a torch.empty(k, n) is this layout with ld = n); ldx >= n_cols, ldy >= the plan's row_end (n_rows for a
  * plan of every row).  Only rows [row_begin, row_end) of each Y column are written; nothing between the columns is read or written.
@@ -648,6 +682,17 @@ int ehyb_debug_panel_times(ehyb_plan* plan, const double* x_dev, double* y_dev, 
 int ehyb_debug_kernel_table(int which, int32_t* rows, int cap, int* n_rows);
 int ehyb_debug_launched(const ehyb_plan* plan, int which, uint8_t* out, int cap);
 int ehyb_debug_launched_clear(ehyb_plan* plan);
+/*
+ * The kernels of the transposed multiply (ehyb_spmv_t) have a table and a launch log of their own; the three tables above do not
+ * list them.  EHYB_KERNEL_ROW_T = 3 ints per row: kind, threads, inl -- EHYB_KERNEL_T_WINDOW (the transposed window kernel) or
+ * EHYB_KERNEL_T_RESIDUAL (the transposed row-segment kernel: CSR residual and direct shape); workgroup size; inline residual.
+ * ehyb_debug_kernel_table_t and ehyb_debug_launched_t work as their namesakes above (host only / one byte per row, cap >= the
+ * table's rows); ehyb_debug_launched_clear zeroes this log too.
+ */
+enum { EHYB_KERNEL_T_WINDOW = 0, EHYB_KERNEL_T_RESIDUAL = 1 };
+enum { EHYB_KERNEL_ROW_T = 3 };
+int ehyb_debug_kernel_table_t(int32_t* rows, int cap, int* n_rows);
+int ehyb_debug_launched_t(const ehyb_plan* plan, uint8_t* out, int cap);
 
 /*
  * The multiply in PARTS, for a caller that receives x segment by segment (multi-GPU, ehyb_plan_create_host_segs):
@@ -1281,6 +1326,16 @@ int ehyb_minres_update_step(int n, const double* ra_dev, const double* inv_diag_
 #define EHYB_GMRES_MAX_RESTART 64
 int ehyb_gmres(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, double* x_dev, int restart, int ortho_passes,
                int max_iter, double rtol, void* stream, int* iters_done, double* rel_residual);
+/*
+ * The same solver for the ADJOINT system A^T x = b on the plan of A: every argument, rule, output and error as ehyb_gmres, every
+ * multiply an ehyb_spmv_t.  The diagonal of A^T is that of A, so inv_diag_dev means the same.  A cycle stays one hipGraph (the
+ * multiply's memset node and launches in it).  What ehyb_spmv_t refuses (symmetric pair storage, a residual in panel form,
+ * cfg.val_f32, column segments) is refused here with EHYB_ERR_ARG and the form named, after ehyb_gmres's own argument checks and
+ * before any device work.  The multiply adds with atomics, so x, iters_done and rel_residual are reproducible only up to the order
+ * of summation, from run to run and between graphs and plain launches.
+ */
+int ehyb_gmres_t(ehyb_plan* plan, const double* inv_diag_dev, const double* b_dev, double* x_dev, int restart, int ortho_passes,
+                 int max_iter, double rtol, void* stream, int* iters_done, double* rel_residual);
 typedef struct ehyb_gmres_slots {
     int32_t slots, slot_doubles;
     int32_t slot_bb, slot_ww, slot_c0;
