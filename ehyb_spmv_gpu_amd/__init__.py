@@ -19,6 +19,7 @@ from .host import (  # noqa: F401
     Coarse,
     DeviceBuffer,
     EhybError,
+    Fsai,
     Matrix,
     Plan,
     SpmvGraph,
@@ -26,6 +27,7 @@ from .host import (  # noqa: F401
     cheb_coeffs,
     device_count,
     entry_order,
+    fsai_factor_step,
     host_threads,
     kernel_table,
     kernel_table_t,

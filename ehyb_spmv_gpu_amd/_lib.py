@@ -280,6 +280,17 @@ SIGNATURES = {
     "ehyb_coarse_restrict_step": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_coarse_solve_step": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_coarse_prolong_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_fsai_create_host": (C.c_int, [_mp, C.c_int, _cfgp, C.c_int, _P(_vp)]),
+    "ehyb_fsai_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
+    "ehyb_fsai_plans": (C.c_int, [_vp, _P(_vp), _P(_vp)]),
+    "ehyb_fsai_upload": (C.c_int, [_vp]),
+    "ehyb_fsai_destroy": (None, [_vp]),
+    "ehyb_fsai_set_values": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int, _vp]),
+    "ehyb_fsai_apply": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ehyb_pcg_fsai": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_pcg_fsai_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_fsai_factor_step": (C.c_int, [C.c_int, _P(C.c_int32), _P(C.c_int32), _dp, _i64p, _P(C.c_int32), _dp, _ip, _vp]),
+    "ehyb_fsai_tt_step": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp]),
     "ehyb_bicgstab_layout": (C.c_int, [_P(BicgstabSlots)]),
     "ehyb_bicgstab_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),

@@ -555,12 +555,12 @@ class Plan:
                                         C.byref(r) if per_kernel else None), "ehyb_spmv_bench")
         return {"ms_total": t.value, "ms_ell_avg": e.value, "ms_er_avg": r.value}
 
-    def _solve(self, name, B, X0, inv_diag, scalars, stream=0, allow_breakdown=False, multi=False, inner=None, counters=None):
+    def _solve(self, name, B, X0, inv_diag, scalars, stream=0, allow_breakdown=False, multi=False, inner=None, counters=None, diag=True):
         """One call of the solver `name`: B, X0 (zeros if None) and the optional inv_diag staged on the device; the arguments in
         the one-vector shape or (multi) the (ldb, ldx, k) one, `scalars` between the vectors and the stream; `inner`: the second
         plan of ehyb_pcg_refine, which also reports two integer counters instead of one, or of ehyb_pcg_cheb (counters=1).  A
         failure raises EhybError, unless
-        allow_breakdown and the error text says breakdown.  -> (X, counters ...): scalars from a one-vector call, (k,) arrays
+        allow_breakdown and the error text says breakdown.  diag=False: the solver takes no inv_diag argument (ehyb_pcg_fsai).  -> (X, counters ...): scalars from a one-vector call, (k,) arrays
         and X (k, n) from a multi one."""
         n, k = self.n, 1
         B = np.ascontiguousarray(np.atleast_2d(B) if multi else B, dtype=np.float64)
@@ -573,7 +573,7 @@ class Plan:
         dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
         counts, rel = np.zeros((counters or (1 if inner is None else 2), k), dtype=np.int32), np.zeros(k, dtype=np.float64)
         vectors = (C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k) if multi else (C.c_void_p(db.ptr), C.c_void_p(dx.ptr))
-        rc = getattr(self.lib, name)(self.h, *(() if inner is None else (inner.h,)), C.c_void_p(dd.ptr) if dd else None, *vectors,
+        rc = getattr(self.lib, name)(self.h, *(() if inner is None else (inner.h,)), *((C.c_void_p(dd.ptr) if dd else None,) if diag else ()), *vectors,
                                      *scalars, C.c_void_p(stream), *(_ptr(c, C.c_int) for c in counts), _ptr(rel, C.c_double))
         if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
             raise EhybError(rc, name)
@@ -636,6 +636,19 @@ class Plan:
         cg_coarse(B[j]) would -- with plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,))."""
         return self._solve("ehyb_pcg_coarse_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True,
                            inner=coarse, counters=1)
+
+    def cg_fsai(self, b, fsai, x0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_pcg_fsai: CG on this plan with the preconditioner z = G^T (G r) of `fsai` (an Fsai of the reordered matrix this plan
+        was built from; there is no inv_diag: G carries the scaling).  -> (x, iterations, relative residual).  A breakdown raises
+        EhybError, unless allow_breakdown: then the residual is NaN."""
+        return self._solve("ehyb_pcg_fsai", b, x0, None, (max_iter, rtol, check_every), stream, allow_breakdown, inner=fsai, counters=1, diag=False)
+
+    def cg_fsai_multi(self, B, fsai, X0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_pcg_fsai_multi: k independent cg_fsai solves that share every multiply; B, X0 (k, n), column j solved as
+        cg_fsai(B[j]) would -- with plain storage and transpose="plan" bit for bit.  -> (X (k, n), iterations (k,), relative
+        residuals (k,))."""
+        return self._solve("ehyb_pcg_fsai_multi", B, X0, None, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True, inner=fsai,
+                           counters=1, diag=False)
 
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
@@ -805,6 +818,118 @@ class Coarse:
             self.destroy()
         except Exception:
             pass
+
+
+FSAI_ARRAYS = {"row_ptr": (0, np.int64), "cols": (1, np.int32), "vals": (2, np.float64), "counts": (3, np.int64)}
+FSAI_MAX_ROW = 64             # EHYB_FSAI_MAX_ROW
+
+
+class _BorrowedPlan(Plan):
+    """a plan that belongs to another object (Fsai.plans): stats and arrays, never destroyed from here"""
+
+    def __init__(self, handle, n):
+        self.lib, self.h, self.n, self.rows = _lib.load(), C.c_void_p(handle), n, (0, n)
+
+    def destroy(self):
+        self.h = C.c_void_p()
+
+
+class Fsai:
+    """ehyb_fsai: the factorised sparse approximate inverse of Plan.cg_fsai for a reordered symmetric matrix -- the matrix the plan
+    was built from.  row_cap 0: EHYB_FSAI_MAX_ROW (64) columns per row of G at the most; cfg: the configuration of G's plan(s)
+    (None: the defaults; val_f32 = 1 keeps the preconditioner in fp32); transpose "plan": a second plan built from G^T
+    (reproducible bit for bit), "spmv_t": ehyb_spmv_t on the plan of G.  upload=False keeps it on the host (no GPU needed)."""
+
+    def __init__(self, matrix, row_cap=0, cfg=None, transpose="plan", upload=True):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self.n = matrix.n
+        self.nnz_a = matrix.nnz
+        self.transpose = transpose
+        _check(self.lib.ehyb_fsai_create_host(C.byref(matrix.c), int(row_cap), C.byref(cfg) if cfg else None, {"plan": 0, "spmv_t": 1}[transpose],
+                                              C.byref(self.h)), "ehyb_fsai_create_host")
+        if upload:
+            self.upload()
+
+    def upload(self):
+        _check(self.lib.ehyb_fsai_upload(self.h), "ehyb_fsai_upload")
+        return self
+
+    def array(self, name):
+        """ehyb_fsai_host_array: "row_ptr" (n + 1,) int64, "cols" and "vals" (nnz(G),) -- G in CSR form as the host computed it --,
+        "counts" (2,) -- copies"""
+        which, dtype = FSAI_ARRAYS[name]
+        p, cnt = C.c_void_p(), C.c_int64()
+        _check(self.lib.ehyb_fsai_host_array(self.h, which, C.byref(p), C.byref(cnt)), "ehyb_fsai_host_array")
+        if cnt.value == 0 or not p.value:
+            return np.zeros(0, dtype=dtype)
+        buf = (C.c_char * (cnt.value * np.dtype(dtype).itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=dtype, count=cnt.value).copy()
+
+    @property
+    def capped_rows(self):
+        return int(self.array("counts")[0])
+
+    @property
+    def fallback_rows(self):
+        """rows in their Jacobi form, as of the last numeric phase (the host build, or set_values on the device)"""
+        return int(self.array("counts")[1])
+
+    @property
+    def plans(self):
+        """ehyb_fsai_plans -> (the plan of G, the plan of G^T or None): views for stats and arrays; they belong to this object"""
+        g, t = C.c_void_p(), C.c_void_p()
+        _check(self.lib.ehyb_fsai_plans(self.h, C.byref(g), C.byref(t)), "ehyb_fsai_plans")
+        return _BorrowedPlan(g.value, self.n), (_BorrowedPlan(t.value, self.n) if t.value else None)
+
+    def set_values(self, values, entry_order=None, stream=0):
+        """ehyb_fsai_set_values: the numeric phase again, on the device, for new values of A on the same pattern.  values /
+        entry_order as Plan.set_values takes them: numpy arrays (host) or, both of them, device pointers given as (ptr, count)."""
+        if isinstance(values, tuple):
+            ptr, count = values
+            order = None if entry_order is None else C.c_void_p(entry_order[0])
+            _check(self.lib.ehyb_fsai_set_values(self.h, C.c_void_p(ptr), count, order, 1, C.c_void_p(stream)), "ehyb_fsai_set_values")
+            return
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        o = None if entry_order is None else np.ascontiguousarray(entry_order, dtype=np.int32)
+        assert o is None or o.shape == v.shape
+        _check(self.lib.ehyb_fsai_set_values(self.h, v.ctypes.data_as(C.c_void_p), len(v), o.ctypes.data_as(C.c_void_p) if o is not None else None,
+                                             0, C.c_void_p(stream)), "ehyb_fsai_set_values")
+
+    def apply(self, r, stream=0):
+        """ehyb_fsai_apply: z = G^T (G r) for a host vector r (permuted numbering) -> z"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape == (self.n,)
+        dr, dz = DeviceBuffer(self.n).upload(r), DeviceBuffer(self.n)
+        _check(self.lib.ehyb_fsai_apply(self.h, C.c_void_p(dr.ptr), C.c_void_p(dz.ptr), C.c_void_p(stream)), "ehyb_fsai_apply")
+        _check(self.lib.ehyb_dev_sync(), "ehyb_dev_sync")
+        return dz.download()
+
+    def destroy(self):
+        if self.h:
+            self.lib.ehyb_fsai_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def fsai_factor_step(indptr, indices, data, g_ptr, g_cols, stream=0):
+    """ehyb_fsai_factor_step: one launch of the factor kernel on A in CSR form and a pattern (host arrays) -> (g, fallback rows)"""
+    ap = np.ascontiguousarray(indptr, dtype=np.int32)
+    ac = np.ascontiguousarray(indices, dtype=np.int32)
+    av = np.ascontiguousarray(data, dtype=np.float64)
+    gp = np.ascontiguousarray(g_ptr, dtype=np.int64)
+    gc = np.ascontiguousarray(g_cols, dtype=np.int32)
+    n = len(ap) - 1
+    assert gp.shape == (n + 1,) and len(ac) == len(av) == ap[-1] and len(gc) == gp[-1]
+    g, fb = np.empty(max(len(gc), 1)), C.c_int(0)
+    _check(_lib.load().ehyb_fsai_factor_step(n, _ptr(ap, C.c_int32), _ptr(ac, C.c_int32), _ptr(av, C.c_double), _ptr(gp, C.c_int64),
+                                             _ptr(gc, C.c_int32), _ptr(g, C.c_double), C.byref(fb), C.c_void_p(stream)), "ehyb_fsai_factor_step")
+    return g[:len(gc)], fb.value
 
 
 def minres_inv_diag(diag):

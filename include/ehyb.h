@@ -1127,6 +1127,86 @@ int  ehyb_coarse_prolong_step(ehyb_coarse* c, const double* r_dev, const double*
 int  ehyb_coarse_create_raw(int n, const int32_t* map, int nc, const double* einv, ehyb_coarse** out);
 
 /*
+ * PCG WITH A FACTORISED SPARSE APPROXIMATE INVERSE (FSAI): the incomplete-factorisation-class preconditioner whose apply is
+ * two multiplies.  G is lower triangular on the pattern of tril(A) with G A G^T ~ I, M^-1 = G^T G, z = G^T (G r).  An incomplete
+ * Cholesky factor would be applied by two triangular solves, chains of dependent levels; G and G^T are applied by the multiply
+ * this library is about, on plans of their own.  Everything lives in the numbering of the matrix after ehyb_matrix_reorder,
+ * and the matrix is taken to be symmetric: only its lower triangle (columns j <= i of row i) is read.  A column is taken to be
+ * stored at most once per row.
+ *
+ * Definition.
+ *   Pattern.  Row i of G holds the columns J_i = { j < i : a_ij is stored } + { i }, in rising order, m_i = |J_i|.  row_cap in
+ *   1 .. EHYB_FSAI_MAX_ROW (<= 0: EHYB_FSAI_MAX_ROW, the dense block the factor kernel holds): where m_i > row_cap the row keeps i
+ *   and the row_cap - 1 columns j < i of largest |a_ij|, ties to the lower column, still in rising order; such rows are counted.
+ *   Values.  S = A[J_i, J_i] from the stored entries of the rows J_i (what is not stored is 0), its lower triangle (row k of S
+ *   from row J_i[k] of A) mirrored.  S = L L^T in fp64 and row i of G solves L^T g = e_m: the textbook y / sqrt(y_m) with
+ *   S y = e_m, and S g = e_m / g_m.  The order of every sum: the factorisation is right-looking -- for j = 0 .. m - 1 in turn
+ *   L[j][j] = sqrt(S[j][j]), L[r][j] = S[r][j] / L[j][j], then S[r][c] <- S[r][c] - L[r][j] L[c][j] for j < c <= r, so an entry
+ *   loses its terms in rising j; the solve runs from the last unknown up, g[r] = (e[r] - L[m-1][r] g[m-1] - ... - L[r+1][r] g[r+1]) /
+ *   L[r][r], the terms taken off in falling c.  (The host rounds every product and difference; the device may fuse the two.)
+ *   Fallback.  A pivot S[j][j] that is not a positive finite number sends the row to its Jacobi form, g_ii = 1 / sqrt(a_ii) and
+ *   zeros elsewhere in the row; such rows are counted.  An a_ii that is itself missing or not a positive finite number:
+ *   EHYB_ERR_ARG, "not positive definite" in ehyb_last_error.
+ *
+ * ehyb_fsai_create_host: pattern and values on the host (no GPU needed; the result does not depend on the number of OpenMP
+ *   threads: rows are dealt to threads whole), then G as a matrix on m's partitions -- m's partBoundary, no second reorder; its
+ *   graph is half of A's -- and its plan(s) from plan_cfg (NULL: the defaults) with sym_pairs off and value_map on.
+ *   transpose_mode 0 (the default of the Python layer): a second plan, built from G^T; every sum in a fixed order.
+ *   transpose_mode 1: one plan, G^T applied by ehyb_spmv_t on it -- half the device memory, the order of ehyb_spmv_t's atomic
+ *   adds; a plan ehyb_spmv_t_supported refuses (cfg.val_f32, a residual in panel form) fails here with that call's words.
+ *   plan_cfg->val_f32 = 1 is allowed in mode 0: the preconditioner then lives in fp32 on the device, the CG around it stays fp64.
+ *   EHYB_ERR_ARG before any work: a null pointer, row_cap > EHYB_FSAI_MAX_ROW, a transpose_mode other than 0 / 1, a matrix
+ *   without partition data.
+ * ehyb_fsai_host_array: which = EHYB_FSAI_ROW_PTR int64[n + 1], _COLS int32[nnz(G)], _VALS double[nnz(G)] (G in CSR form, as
+ *   create_host computed it: ehyb_fsai_set_values does not refresh it), _COUNTS int64[2] {capped rows, fallback rows} (the
+ *   second as of the last numeric phase).
+ * ehyb_fsai_plans: the plan of G and that of G^T (NULL in mode 1), for stats; they belong to the object.
+ * ehyb_fsai_upload: the plan(s), and for the numeric phase A's row pointers and columns, G's pattern and the entry order of the
+ *   G^T plan (the G plan's is the identity): 4 (nnz(A) + 2 nnz(G)) + 8 nnz(G) bytes and a few vectors beside the plans.
+ *   ehyb_fsai_destroy releases both sides; NULL is allowed.
+ * ehyb_fsai_set_values: the numeric phase again, on the device, for new values of A on the same pattern (the pattern of G stays,
+ *   capped rows keep their columns).  values, count, entry_order, on_device: ehyb_plan_set_values' conventions exactly (count =
+ *   the entries of A).  ehyb_fsai_factor_kernel gives each row of G to one wave (assembly of the block's lower triangle in LDS
+ *   by matching the columns of the rows J_i against J_i, factorisation, solve, g in CSR order, the fallback rule with its count
+ *   on the device), then one ehyb_plan_set_values(..., on_device = 1) per plan fills the value streams.  The call drains the
+ *   stream once in between to read the counts: a non-positive diagonal entry or an entry_order value out of range is
+ *   EHYB_ERR_ARG with the plans untouched.
+ * ehyb_fsai_apply: t = G r, z = G^T t on the stream.  One apply at a time per object (it owns t).
+ * ehyb_pcg_fsai / ehyb_pcg_fsai_multi: arguments (there is no inv_diag: G carries the scaling), stopping, breakdown, graphs and
+ *   outputs as ehyb_pcg_coarse / ehyb_pcg_coarse_multi -- the same loop.  Per iteration: q = A p, p.q, the update kernel without
+ *   a preconditioner, T = G R, the partials of r.z = t.t (fsai_tt_kernel, fixed-order sums), Z = G^T T, the direction kernel.
+ *   k columns go through ehyb_spmm on G's plans (as wide as ehyb_spmm_max_k of each allows), in mode 1 column by column.  With
+ *   plain storage and transpose_mode 0, x, iters_done and rel_residual are the same bits from run to run, for graphs and plain
+ *   launches, on any stream and for any check_every, and column j of a k-column solve equals the one-vector solve.  Mode 1
+ *   inherits the order of ehyb_spmv_t's atomic adds: reproducible up to the order of summation only.
+ *   In this order: EHYB_ERR_ARG for what ehyb_pcg rejects, then for a null object or one with another number of rows;
+ *   EHYB_ERR_STATE for a plan, then an object, that was never uploaded.  All before any device work.
+ * ehyb_fsai_factor_step (for tests of the kernel): HOST arrays in and out -- A in CSR form (a_ptr int32[n + 1]), a pattern
+ *   (g_ptr int64[n + 1], every row 1 .. EHYB_FSAI_MAX_ROW columns, rising, the diagonal last), g_out double[g_ptr[n]]; one launch of
+ *   the factor kernel on `stream`, with the LDS of the pattern's longest row.  *fallback_rows (may be NULL): the device's count.
+ * ehyb_fsai_tt_step: the partials of t.t (n doubles on the device) into r.z slot number rz (0 / 1) of ehyb_cg_layout, with the
+ *   grid of the other *_step calls.
+ * Out of scope: adaptive or powered patterns, an unsymmetric FSAI for GMRES and BiCGSTAB, several GPUs.
+ */
+#define EHYB_FSAI_MAX_ROW 64
+enum { EHYB_FSAI_ROW_PTR = 0, EHYB_FSAI_COLS = 1, EHYB_FSAI_VALS = 2, EHYB_FSAI_COUNTS = 3 };
+typedef struct ehyb_fsai ehyb_fsai;
+int  ehyb_fsai_create_host(const matrixCOO* m, int row_cap, const ehyb_config* plan_cfg, int transpose_mode, ehyb_fsai** out);
+int  ehyb_fsai_host_array(const ehyb_fsai* f, int which, const void** ptr, int64_t* count);
+int  ehyb_fsai_plans(const ehyb_fsai* f, ehyb_plan** plan_g, ehyb_plan** plan_t);
+int  ehyb_fsai_upload(ehyb_fsai* f);
+void ehyb_fsai_destroy(ehyb_fsai* f);
+int  ehyb_fsai_set_values(ehyb_fsai* f, const double* values, int64_t count, const int32_t* entry_order, int on_device, void* stream);
+int  ehyb_fsai_apply(ehyb_fsai* f, const double* r_dev, double* z_dev, void* stream);
+int  ehyb_pcg_fsai(ehyb_plan* plan, ehyb_fsai* f, const double* b_dev, double* x_dev, int max_iter, double rtol, int check_every,
+                   void* stream, int* iters_done, double* rel_residual);
+int  ehyb_pcg_fsai_multi(ehyb_plan* plan, ehyb_fsai* f, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k, int max_iter,
+                         double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+int  ehyb_fsai_factor_step(int n, const int32_t* a_ptr, const int32_t* a_cols, const double* a_vals, const int64_t* g_ptr,
+                           const int32_t* g_cols, double* g_out, int* fallback_rows, void* stream);
+int  ehyb_fsai_tt_step(int n, const double* t_dev, double* s_dev, int rz, void* stream);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
