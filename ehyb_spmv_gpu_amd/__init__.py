@@ -31,6 +31,7 @@ from .host import (  # noqa: F401
     host_threads,
     kernel_table,
     kernel_table_t,
+    lobpcg_rr,
     make_config,
     minres_inv_diag,
     partition_graph,

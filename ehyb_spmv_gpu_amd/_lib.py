@@ -320,6 +320,11 @@ SIGNATURES = {
     "ehyb_eigsh_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_eigsh_scale_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_eigsh_rotate_step": (C.c_int, [C.c_int, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "ehyb_lobpcg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _vp, C.c_int64, _vp, _ip,
+                              _ip, _ip, _dp]),
+    "ehyb_lobpcg_rr": (C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip]),
+    "ehyb_lobpcg_gram_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_lobpcg_resid_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, C.c_uint, C.c_int64, _vp, _vp, _vp, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

@@ -720,6 +720,40 @@ class Plan:
         X = dv.download().reshape(-1, ldv)[:f, :n].copy() if dv else None
         return evals[:f].copy(), X, info
 
+    def lobpcg(self, nev, block=0, coarse=None, inv_diag=None, X0=None, max_iter=500, tol=1e-8, anorm=0.0, vectors=True,
+               allow_breakdown=False, stream=0):
+        """ehyb_lobpcg: the nev (1 .. 8) smallest eigenpairs of the plan's symmetric matrix by LOBPCG on the device, with a block
+        of `block` vectors (0: nev) -- a block finds the copies of a multiple eigenvalue, which eigsh finds once.  Preconditioner:
+        `coarse` (a Coarse of the reordered matrix, with inv_diag as in cg_coarse), inv_diag alone (Jacobi) or none.  X0 (block, n)
+        or None (the start block of the header); inv_diag, X0 and the vectors in the permuted numbering.  A column has converged
+        when ||A x - theta x|| <= tol * max(max |theta|, anorm).  -> (evals (nev,), X (nev, n) or None, info) with info = {"nconv",
+        "iters", "multiplies", "resid" (nev,)}; nconv < nev means max_iter ran out.  A breakdown (a non-finite quantity, a basis
+        of rank < block) raises EhybError, unless allow_breakdown: then nconv = 0 and evals, resid are NaN.  On a matrix whose
+        lowest eigenvalues are well separated eigsh(nev, "SA") needs fewer multiplies."""
+        n, nev = self.n, int(nev)
+        nb = nev if int(block) == 0 else int(block)
+        ld = n + (n & 1)
+        dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
+        d0 = None
+        if X0 is not None:
+            X0 = np.ascontiguousarray(X0, dtype=np.float64)
+            assert X0.shape == (nb, n), (X0.shape, nb, n)
+            padded = np.zeros((nb, ld))
+            padded[:, :n] = X0
+            d0 = DeviceBuffer(nb * ld).upload(padded.ravel())
+        dv = DeviceBuffer(max(nev, 1) * ld).upload(np.zeros(max(nev, 1) * ld)) if vectors else None
+        evals, resid = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        nconv, iters, mult = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self.lib.ehyb_lobpcg(self.h, coarse.h if coarse is not None else None, C.c_void_p(dd.ptr) if dd else None,
+                                  C.c_void_p(d0.ptr) if d0 else None, ld, nev, int(block), int(max_iter), tol, anorm, _ptr(evals, C.c_double),
+                                  C.c_void_p(dv.ptr) if dv else None, ld, C.c_void_p(stream), C.byref(nconv), C.byref(iters), C.byref(mult),
+                                  _ptr(resid, C.c_double))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, "ehyb_lobpcg")
+        info = {"nconv": nconv.value, "iters": iters.value, "multiplies": mult.value, "resid": resid[:nev].copy()}
+        X = dv.download().reshape(-1, ld)[:nev, :n].copy() if dv else None
+        return evals[:nev].copy(), X, info
+
     def spectrum_bounds(self, inv_diag=None, tol=1e-4, stream=0):
         """(lmin, lmax) of D^-1 A (inv_diag None: of A) from two eigsh calls with scale = sqrt(inv_diag): the smallest and the
         largest Ritz value at relative residual tol.  Ritz values approach the ends of the spectrum FROM INSIDE: lmin is never
@@ -936,6 +970,20 @@ def minres_inv_diag(diag):
     """The positive diagonal preconditioner of Plan.minres from the matrix's diagonal: 1 / |a_ii|, and 1 where a_ii = 0."""
     d = np.abs(np.asarray(diag, dtype=np.float64))
     return np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 1.0)
+
+
+def lobpcg_rr(G, H, nb):
+    """ehyb_lobpcg_rr: the Rayleigh-Ritz step of Plan.lobpcg on the host for the pencil (H, G), both (mc, mc) symmetric (only the
+    upper triangles are read), mc <= 24 -> (theta (nb,) rising, Y (mc, nb) with Y^T G Y = I, rank).  Raises EhybError (code 1)
+    for a non-finite entry, a negative G[i, i] or a rank below nb."""
+    G = np.asfortranarray(G, dtype=np.float64)
+    H = np.asfortranarray(H, dtype=np.float64)
+    mc = G.shape[0]
+    assert G.shape == (mc, mc) and H.shape == (mc, mc)
+    theta, Y, rank = np.zeros(max(int(nb), 1)), np.zeros((mc, max(int(nb), 1)), order="F"), C.c_int(0)
+    _check(_lib.load().ehyb_lobpcg_rr(mc, _ptr(G, C.c_double), _ptr(H, C.c_double), int(nb), _ptr(theta, C.c_double), _ptr(Y, C.c_double),
+                                      C.byref(rank)), "ehyb_lobpcg_rr")
+    return theta, np.ascontiguousarray(Y), rank.value
 
 
 def cheb_coeffs(lmin, lmax, degree):

@@ -1440,7 +1440,8 @@ int ehyb_gmres_solve_x_step(int n, int64_t ld, const double* V_dev, const double
  * With scale_dev the operator is S A S, S = diag(scale) -- scale = 1 / sqrt(diag) gives the spectrum of D^-1 A.  The host looks
  * once per restart cycle: it solves the projected problem (at most 64 x 64, ehyb_sym_eig), decides convergence and uploads the
  * rotation.  Ritz values approach the ends of the spectrum from inside.  A MULTIPLE eigenvalue is found ONCE: this is Lanczos
- * from one start vector, whose Krylov space holds one vector of every eigenspace; no locking and no block version exist.
+ * from one start vector, whose Krylov space holds one vector of every eigenspace; no locking and no block version exist
+ * (ehyb_lobpcg below is the block method for the smallest end; rounding can bring a second copy in after several restarts).
  *   nev 1 .. EHYB_EIGSH_MAX_NEV; which EHYB_EIG_LARGEST / _SMALLEST; basis 0 = min(max(2 nev + 1, 20), 64), else
  *   nev + 2 .. EHYB_EIGSH_MAX_BASIS; the effective basis m = min(basis, n); keep = nev + (m - nev) / 2 (ehyb_eigsh_basis).
  *   Start vector: v0_dev, NULL = that of ehyb_lambda_max, v_i = 1 + (i mod 7) / 8; normalised to v_0.  A zero or non-finite
@@ -1511,6 +1512,85 @@ int ehyb_eigsh_next_step(int n, int64_t ld, double* V_dev, const double* w_dev, 
 int ehyb_eigsh_scale_step(int n, const double* scale_dev, double* w_dev, double* s_dev, void* stream);
 int ehyb_eigsh_rotate_step(int n, int64_t ld_src, const double* src_dev, int64_t ld_dst, double* dst_dev, const double* Y_dev,
                            int mc, int kc, void* stream);
+
+/*
+ * The nev SMALLEST eigenpairs of the plan's SYMMETRIC matrix by LOBPCG (locally optimal block preconditioned conjugate gradients),
+ * the vectors on the device.  Where ehyb_eigsh finds a multiple eigenvalue once and is slowest at the low end of a stiffness-like
+ * spectrum, this is a block method (a block of nb vectors finds up to nb copies of an eigenvalue) that takes a preconditioner.
+ * On a matrix whose wanted end is well separated ehyb_eigsh needs fewer multiplies (36 against 116 on the planted grid of the
+ * tests): prefer it there, and for the largest end, which this solver does not do.
+ *   Sizes.  nb = block, 0 = nev; 1 <= nev <= nb <= EHYB_LOBPCG_MAX_BLOCK = 8; nb <= n.  The trial basis S = [X (nb) | P (nb,
+ *     absent in the first iteration) | W (na)] has mc = nb or 2 nb, + na <= 24 columns, column-major with the leading dimension
+ *     ld = n rounded up to even, beside its image AS.  A second pair (S, AS) receives the rotation and the pairs swap by pointer:
+ *     the solve allocates 12 nb vectors of ld doubles, nb more with a coarse object, and 2.3 MB of partial sums.
+ *   Preconditioner.  T r = ehyb_coarse_apply(coarse, inv_diag_dev, r) with a coarse object, inv_diag o r with inv_diag_dev
+ *     alone, r with neither.
+ *   Start.  X = X0_dev (nb columns, column j at X0_dev + j ldx0), NULL: x_ij = ((h & 2047) - 1023.5) / 1024 for row i, column j
+ *     with, in 32-bit unsigned arithmetic, h = (i + 1) 2654435761 + (j + 1) 40503; h ^= h >> 15; h *= 2246822519; h ^= h >> 13.
+ *     AX = A X is one ehyb_spmm of nb columns; one Rayleigh-Ritz step on [X] alone gives theta and an orthonormal X.
+ *   Iteration it = 0, 1, ...
+ *     1. R_i = AX_i - theta_i X_i and res_i = ||R_i||_2 for all nb columns; nrm = max(max_l |theta_l|, anorm); column i is
+ *        converged iff res_i <= tol nrm; nconv = the number of leading converged columns among the first nev.  Stop when
+ *        nconv == nev or it == max_iter.
+ *     2. Soft locking: the active columns are all non-converged columns of the block (a column may re-enter).  W = T R[:, active],
+ *        na columns; AW = A W is one ehyb_spmm of na columns; multiplies += na.
+ *     3. G = S^T S and H = S^T AS, mc x mc, on the device in one pass over the 2 mc columns.
+ *     4. ehyb_lobpcg_rr on the host: theta (nb values, rising) and Y (mc x nb).  Yp = Y with its first nb rows zeroed.
+ *     5. [X | P] = S [Y | Yp], [AX | AP] = AS [Y | Yp]: two launches of the rotation kernel of ehyb_eigsh with kc = 2 nb.
+ *   The whole Gram matrix is used, its X-X block included, so a drift of X^T X is absorbed at every step; there is no separate
+ *   orthogonalisation.  The host looks twice per iteration (after the residual norms, after the Gram matrices), so there is no
+ *   hipGraph and cfg.graphs does not matter.  The solver only calls ehyb_spmm, so every plan form works; a plan built with
+ *   cfg.lds_doubles = EHYB_LDS_MAX_DOUBLES / 4 multiplies four columns per pass, any other plan makes passes of width 1
+ *   (ehyb_spmm_max_k).  Every device sum is re-added from per-workgroup partials in a fixed order on a grid that depends on n
+ *   alone and the host arithmetic is deterministic: with plain storage every output is the same bits from run to run, on a given
+ *   or a private stream.
+ * Outputs: evals[i] = theta_i and resid[i] = res_i for i < nev; evecs_dev column i (at evecs_dev + i ldv) = X_i, nev columns;
+ * *nconv, *iters_done = it at the stop, *multiplies (columns multiplied, the nb of the start included).  Host outputs and
+ * evecs_dev may be NULL.  ldv and ldx0 even and >= n; evecs_dev, inv_diag_dev, X0_dev 16-byte aligned.  stream NULL = a private
+ * stream.  max_iter = 0 is allowed: one multiply of nb columns, the first Rayleigh-Ritz step, the residuals.  EHYB_OK also when
+ * nconv < nev at max_iter.  Breakdown -- a non-finite theta, res, G or H, or a basis of rank < nb in step 4 --: EHYB_ERR_ARG with
+ * "breakdown" in ehyb_last_error after every output is written: nconv = 0, evals and resid NaN, iters_done and multiplies as they
+ * stand, evecs_dev untouched.
+ * EHYB_ERR_ARG, in this order and before any device work: a null plan; nev, block outside their ranges or max_iter < 0; a negative
+ * or NaN tol, a negative or non-finite anorm; a plan not over all rows; nb > n; an odd ldv (ldx0) or one below n with a non-NULL
+ * evecs_dev (X0_dev); a misaligned evecs_dev, inv_diag_dev or X0_dev; a coarse object with another number of rows.  Then
+ * EHYB_ERR_STATE on a plan, then a coarse object, that was never uploaded.
+ * Out of scope: the largest end, a mass matrix or scaling, hard locking, nev > 8, several GPUs.
+ *
+ * ehyb_lobpcg_rr (host only, no device, deterministic): the Rayleigh-Ritz step for the pencil (H, G), both mc x mc (1 .. 24),
+ * column-major with leading dimension mc, only the upper triangles i <= j read; 1 <= nb <= min(8, mc).
+ *   1. A non-finite entry or a negative G_ii: EHYB_ERR_ARG.
+ *   2. Columns with G_ii == 0 are dropped; their rows of Y are 0.
+ *   3. d_i = 1 / sqrt(G_ii), G^ = d G d with a unit diagonal.
+ *   4. (sigma, U) = ehyb_sym_eig(G^); keep sigma_l > 2^-40 sigma_max; *rank = their count (may be NULL); fewer than nb:
+ *      EHYB_ERR_ARG with "rank" in ehyb_last_error.
+ *   5. Q = D U_keep Sigma^-1/2.    6. (theta, Z) = ehyb_sym_eig(Q^T H Q).    7. Y = Q Z[:, :nb], theta = theta[:nb].
+ *   Every sum runs in rising index order.  theta: nb doubles, rising; Y: mc x nb, column-major with leading dimension mc,
+ *   Y^T G Y = I.
+ *
+ * The two new kernels, each with its fixed-order sum, one call each; vectors and leading dimensions as the ehyb_gmres_*_step calls.
+ *   gram   G = S^T S and H = S^T AS for the first mc (1 .. 24) columns, each of the 2 mc columns read once; the upper triangles
+ *          are computed and mirrored bit for bit.  G_dev, H_dev: mc x mc, column-major with leading dimension mc.  min(ceil(n /
+ *          128), 256) workgroups of 768 threads write their partial sums to slots of their own in scratch_dev
+ *          (EHYB_LOBPCG_SCRATCH_DOUBLES doubles) and a second launch adds the slots in rising order.
+ *   resid  R_c = AX_c - theta_c X_c for c < nb (1 .. 8), theta_dev nb doubles on the device; res2_dev[c] = R_c . R_c; for every
+ *          bit c of active_mask (within the low nb bits) W column number (set bits of the mask below c) = inv_diag o R_c
+ *          (inv_diag_dev NULL: R_c), column a at W_dev + a ldw.  Columns of W not listed and everything else stay untouched.
+ *          slot_doubles / 2 workgroups leave partial sums in scratch_dev (4096 doubles); a second launch adds them in rising order.
+ * EHYB_ERR_ARG for n < 0, a null pointer that would be used, mc, nb or the mask outside its range, an odd leading dimension or
+ * one below n, a misaligned vector.  All asynchronous on `stream`.
+ */
+#define EHYB_LOBPCG_MAX_BLOCK 8
+#define EHYB_LOBPCG_SCRATCH_DOUBLES 294912   /* 256 workgroups x 2 matrices x 24 x 24 */
+int ehyb_lobpcg(ehyb_plan* plan, ehyb_coarse* coarse, const double* inv_diag_dev, const double* X0_dev, int64_t ldx0, int nev, int block,
+                int max_iter, double tol, double anorm, double* evals, double* evecs_dev, int64_t ldv, void* stream, int* nconv,
+                int* iters_done, int* multiplies, double* resid);
+int ehyb_lobpcg_rr(int mc, const double* G, const double* H, int nb, double* theta, double* Y, int* rank);
+int ehyb_lobpcg_gram_step(int n, int64_t ld, const double* S_dev, const double* AS_dev, int mc, double* G_dev, double* H_dev,
+                          double* scratch_dev, void* stream);
+int ehyb_lobpcg_resid_step(int n, int64_t ld, const double* X_dev, const double* AX_dev, int nb, const double* theta_dev,
+                           const double* inv_diag_dev, unsigned int active_mask, int64_t ldw, double* W_dev, double* res2_dev,
+                           double* scratch_dev, void* stream);
 
 /* -------------------------------------------- harness pieces (solver_test.c) */
 
