@@ -120,6 +120,22 @@ def pcg(A, b, cmap, nc, dinv=None, max_iter=1000, rtol=1e-10, x0=None, check_eve
     return x, it
 
 
+# ------------------------------------------------------------------ the freezing mix at full size (test_gpu_precond_full.py)
+# The right-hand-side bank of test_gpu_solver_kernels.MIX_KINDS (cheb_cases.mix_bank, mix_x0) with the e of its "near" columns
+# (b = A x*, x0 = x* + e u) chosen for this solver.  Relative residual per unit e on spd_matrix(1024, 921, 3000, 21) after 0, 2, 4,
+# 6, 8 iterations, from pcg above with the library's own map and E^-1 (ehyb_coarse_map with the automatic agg_rows = 614:
+# nc = 1735; the host object's arrays "map" and "Einv"), everything in the permuted numbering:
+#   with inv_diag      3.40  0.359  0.120  0.0555  0.0304     a random b from x0 = 0 is at 7.0e-2 after 12
+#   without            3.40  0.407  0.127  0.0585  0.0326                                   7.5e-2
+# (the two "near" columns measured, u of columns 0 and 3, agree to two digits.)  MIX_E[with inv_diag] = the three e that cross
+# MIX_RTOL = 1e-6 at check points 2, 4 and 6 (check_every = 2): each near the geometric middle of its interval,
+# 1e-6 / sqrt(residual before * residual after), a factor of 1.4 to 3.1 from either edge.  With them pcg above stops the seven
+# columns of the bank after 4, 0, 12, 2, 6, 4, 12 iterations, with inv_diag and without.  These numbers are measured from the
+# restatement on the CPU, not from the device; no host test repeats them: the restatement alone takes 1.7 s for the bank, the
+# matrix, its reordering and the host object another 2 s, and the slowest host test of this solver takes 0.5 s.
+MIX_E = {True: (9e-7, 4.8e-6, 1.2e-5), False: (8.5e-7, 4.4e-6, 1.2e-5)}
+
+
 def near_singular_grid(nx, ny, seed, shift):
     """test_gpu_cg.spd_matrix's construction with extra = 0 and the diagonal = row sum + shift"""
     rng = np.random.default_rng(seed)

@@ -106,6 +106,22 @@ def pcg(A, b, G, max_iter=1000, rtol=1e-10, x0=None, check_every=1):
     return x, it
 
 
+# ------------------------------------------------------------------ the freezing mix at full size (test_gpu_precond_full.py)
+# The right-hand-side bank of test_gpu_solver_kernels.MIX_KINDS (cheb_cases.mix_bank, mix_x0) with the e of its "near" columns
+# (b = A x*, x0 = x* + e u) chosen for this solver.  Relative residual per unit e on spd_matrix(1024, 921, 3000, 21) after 0, 2, 4,
+# 6, 8 iterations, from pcg above with G = matrix(row_ptr, cols, vals) of the library's host object (no row capped, none fallen
+# back, 2,830,367 entries; factor's Python loop over 943,104 rows is too slow, and test_fsai_host.py holds the host factor to its
+# bounds), everything in the permuted numbering:
+#                      3.40  0.167  0.0348  0.0124  0.0059     a random b from x0 = 0 is at 1.25e-2 after 12
+# (the two "near" columns measured, u of columns 0 and 3, agree to two digits.)  MIX_E = the three e that cross MIX_RTOL = 1e-6 at
+# check points 2, 4 and 6 (check_every = 2): each near the geometric middle of its interval, 1e-6 / sqrt(residual before *
+# residual after), a factor of 1.7 to 4.6 from either edge.  With them pcg above stops the seven columns of the bank after 4, 0,
+# 12, 2, 6, 4, 12 iterations.  These numbers are measured from the restatement on the CPU, not from the device; no host test
+# repeats them: the restatement alone takes 2.0 s for the bank, the matrix, its reordering and the host object another 2 s, and
+# the slowest host test of this solver takes 0.9 s.
+MIX_E = (1.3e-6, 1.3e-5, 4.8e-5)
+
+
 def jacobi_pcg(A, b, max_iter=1000, rtol=1e-10):
     """-> iterations of CG preconditioned with the diagonal, the stopping test made every iteration"""
     dinv = 1.0 / A.diagonal()

@@ -2,8 +2,9 @@
 coarse_cases.py, against a direct solve and against ehyb_pcg in the same process.  The hard system is the nearly singular grid
 of test_coarse_host.py (plain storage, symmetric pairs, a plan with a CSR residual); then the easy system Jacobi already
 suits, a 3-unknowns-per-node pattern with dof = 3, apply alone, reproducibility (runs, graphs against plain launches, a user
-stream, check_every), the k-column solve bit for bit against the one-vector one, and a coarse object that belongs to another
-system.  Everything in the permuted numbering."""
+stream, check_every), the k-column solve bit for bit against the one-vector one -- also four columns wide at the largest coarse
+space, nc = 2048 and 2047, where coarse_solve_kernel<4> asks for all 64 KiB of LDS -- and a coarse object that belongs to another
+system.  Everything in the permuted numbering.  (The kernels' unrolled bodies at K > 1: test_gpu_precond_full.py.)"""
 import ctypes as C
 
 import numpy as np
@@ -179,6 +180,59 @@ def test_multi_is_the_single_solve_column_by_column(E, gpu):
         assert_same_bits(got, want, f"k=5 inv_diag={inv is not None}")
         assert got[1][1] == 0 and got[2][1] == 0.0 and not got[0][1].any()
         assert (got[2] <= RTOL).all() and 0 < got[1][2] < got[1][0] and len(set(got[1].tolist())) >= 3, (got[1], got[2])
+
+
+# ------------------------------------------------------------------ the widest solve kernel at the largest coarse space
+WIDE_RTOL, WIDE_ITERS = 1e-6, 12
+# e of the two nearly converged starts (b = A x*, x0 = x* + e u, x* and u uniform in [-1, 1]).  With a map of 2,048 or 2,047
+# contiguous runs of five or six rows the restatement (kc.pcg, with inv_diag) has the relative residual of such a start at
+# e * (1, 0.114, 0.034, 0.0145) after 0, 2, 4, 6 iterations, so these two cross WIDE_RTOL at check points 4 and 2 (check_every =
+# 2), each a factor of 1.8 to 3 from the edges of its interval; the random right-hand sides are between 0.0024 and 0.15 after 12.
+WIDE_E = (1.6e-5, 3e-6)
+
+
+@pytest.fixture(scope="module")
+def wide(E):
+    """the system of test_multi_is_the_single_solve_column_by_column and a bank of eight columns: random b's, a zero b and two
+    nearly converged starts"""
+    s = System(E, kc.near_singular_grid(120, 100, 1, 0.0005), lds_doubles=20480 // 4, sym_pairs=0, direct=2)
+    rng = np.random.default_rng(5)
+    x_star = rng.uniform(-1, 1, s.n)
+    near = s.A @ x_star
+    s.B = np.stack([s.b, np.zeros(s.n), near, rng.uniform(-1, 1, s.n), s.A @ rng.uniform(-1, 1, s.n), near, rng.uniform(-1, 1, s.n),
+                    rng.uniform(-1, 1, s.n)])
+    s.X0 = np.zeros_like(s.B)
+    s.X0[2] = x_star + WIDE_E[0] * rng.uniform(-1, 1, s.n)
+    s.X0[5] = x_star + WIDE_E[1] * rng.uniform(-1, 1, s.n)
+    return s
+
+
+@pytest.mark.parametrize("nc", [2048, 2047])
+def test_the_widest_solve_kernels_at_the_largest_coarse_space(E, gpu, wide, nc):
+    """coarse_solve_kernel<4> stages 4 * ld doubles of dynamic LDS: at nc = EHYB_COARSE_MAX = 2048 exactly 65,536 bytes, and <3>
+    49,152.  nc = 2047 has ld = 2048 too: the zero pad column of E^-1 and of the staged T is read.  k = 4, 7 (4 + 3) and 8 (4 + 4)
+    against the one-vector solves, whose coarse_solve_kernel<1> test_solve_step of test_gpu_coarse_kernels.py pins exactly at
+    these nc; a launch that is refused would leave C = 0 (the loop zeroes it) and other iterates, or an error."""
+    s = wide
+    plan = s.plan()
+    assert plan.spmm_max_k == 4 and plan.stats["sym_pairs"] == 0
+    assert (plan.array("er_seg_row") >= 0).all(), "no residual row may be split into segments"
+    cmap = (np.arange(s.n, dtype=np.int64) * nc // s.n).astype(np.int32)      # contiguous runs of the reordered rows
+    co = E.Coarse(s.m, map=cmap)
+    row_ptr = co.array("row_ptr")
+    assert co.nc == nc and co.array("Einv").shape == (nc, nc) and np.array_equal(co.array("map"), cmap)
+    assert len(row_ptr) == nc + 1 and row_ptr[-1] == s.n and (np.diff(row_ptr) >= 1).all()
+    kw = dict(max_iter=WIDE_ITERS, rtol=WIDE_RTOL, check_every=2, inv_diag=s.inv_diag)
+    singles = [plan.cg_coarse(s.B[j], co, x0=s.X0[j], **kw) for j in range(8)]
+    for k in (4, 7, 8):
+        want = (np.stack([o[0] for o in singles[:k]]), np.array([o[1] for o in singles[:k]]), np.array([o[2] for o in singles[:k]]))
+        got = plan.cg_coarse_multi(s.B[:k], co, X0=s.X0[:k], **kw)
+        print(f"nc={nc} k={k}: iterations per column {list(got[1])}, relative residuals {[f'{r:.2e}' for r in got[2]]}")
+        assert_same_bits(got, want, f"nc={nc} k={k}")
+        assert got[1][1] == 0 and got[2][1] == 0.0 and not got[0][1].any()
+        assert np.isfinite(got[2]).all() and (got[2] < 1).all(), got[2]
+        assert len(set(got[1].tolist())) >= 3, got[1]
+    co.destroy()
 
 
 # ------------------------------------------------------------------ another system's coarse object

@@ -4,7 +4,8 @@ systems of test_gpu_coarse.py (the nearly singular grid and the diagonally domin
 and a CSR-residual plan for A -- G's plans are always plain.  Then apply alone, the numeric phase repeated on the device (the
 same values and new ones, from the host and from device arrays, with an entry order), G in fp32, reproducibility (runs, graphs
 against plain launches, a user stream, check_every), k columns bit for bit against the one-vector solves, G^T through
-ehyb_spmv_t, and the refusals.  Everything in the permuted numbering."""
+ehyb_spmv_t, and the refusals.  Everything in the permuted numbering.  (fsai_tt_kernel's unrolled body at K > 1:
+test_gpu_precond_full.py.)"""
 import ctypes as C
 
 import numpy as np
@@ -190,25 +191,31 @@ def test_runs_graphs_streams_and_check_every_agree_bit_for_bit(E, gpu, hard):
 
 
 def test_multi_is_the_single_solve_column_by_column(E, gpu):
-    """k = 3 on plans whose passes serve four columns, A's and G's: a zero b (done at 0 iterations) and two random ones"""
+    """k = 5: tt launches three and two columns wide on plans whose passes serve four columns, A's and G's.  The bank of
+    test_gpu_coarse.py's test of the same name -- a zero b (done at 0 iterations), a nearly converged start and random b's: the
+    columns freeze at different check points, so the flags change while the solve runs."""
     s = FsaiSystem(E, kc.near_singular_grid(120, 100, 1, 0.0005), lds_doubles=20480 // 4, sym_pairs=0, direct=2)
     plan, f = s.plan(), s.fsai()
     assert plan.spmm_max_k == 4 and all(p.spmm_max_k == 4 for p in f.plans)
     for p in (plan,) + f.plans:
         assert (p.array("er_seg_row") >= 0).all(), "no residual row may be split into segments"
-    B = np.stack([s.b, np.zeros(s.n), np.random.default_rng(5).uniform(-1, 1, s.n)])
+    rng = np.random.default_rng(5)
+    B = np.stack([s.b, np.zeros(s.n), s.b, rng.uniform(-1, 1, s.n), s.A @ rng.uniform(-1, 1, s.n)])
+    X0 = np.zeros_like(B)
+    X0[2] = s.solved()[0] + 1e-7 * rng.uniform(-1, 1, s.n)
     kw = dict(max_iter=5000, rtol=RTOL, check_every=2)
-    singles = [plan.cg_fsai(B[j], f, **kw) for j in range(3)]
+    singles = [plan.cg_fsai(B[j], f, x0=X0[j], **kw) for j in range(5)]
     want = (np.stack([o[0] for o in singles]), np.array([o[1] for o in singles]), np.array([o[2] for o in singles]))
-    got = plan.cg_fsai_multi(B, f, **kw)
+    got = plan.cg_fsai_multi(B, f, X0=X0, **kw)
     print(f"iterations per column {list(got[1])}")
-    assert_same_bits(got, want, "k=3")
+    assert_same_bits(got, want, "k=5")
     assert got[1][1] == 0 and got[2][1] == 0.0 and not got[0][1].any() and (got[2] <= RTOL).all()
+    assert 0 < got[1][2] < got[1][0] and len(set(got[1].tolist())) >= 3, (got[1], got[2])
     # G in fp32: passes of width 1 on G's plans, still the single solves
     f32 = s.fsai(val_f32=1)
     assert all(p.spmm_max_k == 1 for p in f32.plans)
-    singles = [plan.cg_fsai(B[j], f32, **kw) for j in (0, 2)]
-    got = plan.cg_fsai_multi(B[[0, 2]], f32, **kw)
+    singles = [plan.cg_fsai(B[j], f32, **kw) for j in (0, 3)]
+    got = plan.cg_fsai_multi(B[[0, 3]], f32, **kw)
     assert_same_bits(got, (np.stack([o[0] for o in singles]), np.array([o[1] for o in singles]), np.array([o[2] for o in singles])), "k=2, G in fp32")
 
 
