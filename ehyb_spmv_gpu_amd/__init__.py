@@ -37,6 +37,7 @@ from .host import (  # noqa: F401
     partition_graph,
     sizing,
     spmv_gpu_ehyb,
+    tune_decide,
     vector_recover,
     vector_reorder,
     x_glibc,

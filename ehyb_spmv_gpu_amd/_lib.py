@@ -211,6 +211,9 @@ SIGNATURES = {
     "ehyb_debug_kernel_table": (C.c_int, [C.c_int, _P(C.c_int32), C.c_int, _ip]),
     "ehyb_debug_launched": (C.c_int, [_vp, C.c_int, _P(C.c_uint8), C.c_int]),
     "ehyb_debug_launched_clear": (C.c_int, [_vp]),
+    "ehyb_debug_item_map": (C.c_int, [_vp, _P(C.c_int32), C.c_int, _ip, _ip]),
+    "ehyb_debug_set_item_map": (C.c_int, [_vp, _P(C.c_int32), C.c_int, C.c_int]),
+    "ehyb_debug_tune_decide": (C.c_int, [C.c_int, _dp, _P(C.c_int), _dp, _P(C.c_int32), _P(C.c_int32), _ip]),
     "ehyb_spmv_part": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "ehyb_plan_col_segs": (C.c_int, [_vp, _ip]),
     "ehyb_gather": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),

@@ -841,6 +841,75 @@ int ehyb_halo_step(ehyb_plan* P, const double* x, double* y, const int32_t* send
     return rc;
 }
 
+// ---- the item -> workgroup map (ehyb_plan_tune; ehyb_debug_item_map, _set_item_map, _tune_decide: see ehyb.h)
+// The item workgroup b takes under the map in force: the installed map, else the built-in order -- item b for symmetric pairs or
+// cfg.xcd_map = 2, else xcd_item(b, n_items) of ell_device.h (restated here for the host).
+static std::vector<int32_t> item_map_now(const ehyb_plan* P)
+{
+    const int n_items = (int)(P->host.items.size() / kItemWords);
+    if (!P->item_map.empty()) return P->item_map;
+    std::vector<int32_t> map_now((size_t)n_items);
+    const bool in_order = P->host.sym || P->cfg.xcd_map == 2;
+    for (int b = 0; b < n_items; ++b) {
+        const int k = b & 7, j = b >> 3, chunk = n_items >> 3, rem = n_items & 7;
+        map_now[(size_t)b] = in_order ? b : k * chunk + std::min(k, rem) + j;
+    }
+    return map_now;
+}
+
+// The decision of ehyb_plan_tune, a pure host function: from the cost of every item, and the XCD (0..15) and duration of every
+// workgroup of a launch under map_now, the map that puts the heaviest items on the XCD that streamed fastest, and so on down.
+// -> false (map_new untouched) where a workgroup has no stable placement (xcc < 0).
+static bool tune_decide(int n_items, const double* cost, const int* xcc, const double* dur, const int32_t* map_now, std::vector<int32_t>* map_new)
+{
+    for (int b = 0; b < n_items; ++b)
+        if (xcc[b] < 0) return false;
+    // how fast each XCD streamed what it was given: median over its workgroups of bytes per microsecond
+    std::vector<std::vector<double>> rates(16);
+    std::vector<std::vector<int>> slots(16);
+    for (int b = 0; b < n_items; ++b) {
+        rates[(size_t)xcc[b]].push_back(cost[map_now[b]] / std::max(dur[b], 1e-3));
+        slots[(size_t)xcc[b]].push_back(b);
+    }
+    std::vector<std::pair<double, int>> order;  // (median rate, xcd), fastest first
+    for (int k = 0; k < 16; ++k)
+        if (!rates[(size_t)k].empty()) {
+            std::nth_element(rates[(size_t)k].begin(), rates[(size_t)k].begin() + rates[(size_t)k].size() / 2, rates[(size_t)k].end());
+            order.push_back({-rates[(size_t)k][rates[(size_t)k].size() / 2], k});
+        }
+    std::sort(order.begin(), order.end());
+    std::vector<int> by_cost((size_t)n_items);
+    for (int i = 0; i < n_items; ++i) by_cost[(size_t)i] = i;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](int a, int b2) { return cost[a] > cost[b2]; });
+    // the heaviest items on the fastest XCD, and so on down: the pairing that minimises the largest cost / rate
+    map_new->assign((size_t)n_items, -1);
+    size_t at = 0;
+    for (const auto& o : order)
+        for (int b : slots[(size_t)o.second]) (*map_new)[(size_t)b] = by_cost[at++];
+    return true;
+}
+
+// The install: `map` (empty: none, the built-in order) copied to the device and made the plan's map.  The device map it replaces
+// is handed back: whoever keeps the new one retires it (item_map_retire), the tuner's roll-back puts it back.
+static int item_map_install(ehyb_plan* P, const std::vector<int32_t>& map, int32_t** old_dev)
+{
+    int32_t* dm = nullptr;
+    if (!map.empty() && (hipMalloc((void**)&dm, map.size() * 4) != hipSuccess || hipMemcpy(dm, map.data(), map.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        if (dm) (void)hipFree(dm);
+        (void)hipGetLastError();
+        return EHYB_ERR_HIP;
+    }
+    *old_dev = P->d_item_map;
+    P->d_item_map = dm;
+    P->item_map = map;
+    return EHYB_OK;
+}
+
+static void item_map_retire(ehyb_plan* P, int32_t* old_dev)
+{
+    if (old_dev) P->retired_item_maps.push_back(old_dev);  // a hipGraph captured earlier may still name it: freed with the plan
+}
+
 // Tuning of the item -> workgroup map on the device the plan lives on (see ehyb.h).
 int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* span_before_us, double* span_after_us)
 {
@@ -902,59 +971,78 @@ int ehyb_plan_tune(ehyb_plan* P, const double* x, double* y, int reps, double* s
     std::vector<int> xcc;
     double span0 = 0, span1 = 0;
     int rc = measure(&dur, &xcc, &span0);
-    std::vector<int32_t> map_now((size_t)n_items);
-    for (int b = 0; b < n_items; ++b) map_now[(size_t)b] = P->item_map.empty() ? (P->host.sym || P->cfg.xcd_map == 2 ? b : [&] { const int k = b & 7, j = b >> 3, chunk = n_items >> 3, rem = n_items & 7; return k * chunk + std::min(k, rem) + j; }()) : P->item_map[(size_t)b];
-    bool stable = rc == EHYB_OK;
-    for (int b = 0; b < n_items && stable; ++b) stable = xcc[(size_t)b] >= 0;
+    const std::vector<int32_t> map_now = item_map_now(P);
+    std::vector<int32_t> map_new;
+    const bool stable = rc == EHYB_OK && tune_decide(n_items, cost.data(), xcc.data(), dur.data(), map_now.data(), &map_new);
     if (stable) {
-        // how fast each XCD streamed what it was given: median over its workgroups of bytes per microsecond
-        std::vector<std::vector<double>> rates(16);
-        std::vector<std::vector<int>> slots(16);
-        for (int b = 0; b < n_items; ++b) {
-            rates[(size_t)xcc[(size_t)b]].push_back(cost[(size_t)map_now[(size_t)b]] / std::max(dur[(size_t)b], 1e-3));
-            slots[(size_t)xcc[(size_t)b]].push_back(b);
-        }
-        std::vector<std::pair<double, int>> order;  // (median rate, xcd), fastest first
-        for (int k = 0; k < 16; ++k)
-            if (!rates[(size_t)k].empty()) {
-                std::nth_element(rates[(size_t)k].begin(), rates[(size_t)k].begin() + rates[(size_t)k].size() / 2, rates[(size_t)k].end());
-                order.push_back({-rates[(size_t)k][rates[(size_t)k].size() / 2], k});
-            }
-        std::sort(order.begin(), order.end());
-        std::vector<int> by_cost((size_t)n_items);
-        for (int i = 0; i < n_items; ++i) by_cost[(size_t)i] = i;
-        std::stable_sort(by_cost.begin(), by_cost.end(), [&](int a, int b2) { return cost[(size_t)a] > cost[(size_t)b2]; });
-        // the heaviest items on the fastest XCD, and so on down: the pairing that minimises the largest cost / rate
-        std::vector<int32_t> map_new((size_t)n_items, -1);
-        size_t at = 0;
-        for (const auto& o : order)
-            for (int b : slots[(size_t)o.second]) map_new[(size_t)b] = by_cost[at++];
-        int32_t* dm = nullptr;
-        if (at == (size_t)n_items && hipMalloc((void**)&dm, (size_t)n_items * 4) == hipSuccess &&
-            hipMemcpy(dm, map_new.data(), (size_t)n_items * 4, hipMemcpyHostToDevice) == hipSuccess) {
-            int32_t* old = P->d_item_map;
-            std::vector<int32_t> old_host = P->item_map;
-            P->d_item_map = dm;
-            P->item_map = map_new;
+        int32_t* old = nullptr;
+        const std::vector<int32_t> old_host = P->item_map;
+        if (item_map_install(P, map_new, &old) == EHYB_OK) {
             std::vector<double> dur2;
             std::vector<int> xcc2;
             rc = measure(&dur2, &xcc2, &span1);
             if (rc != EHYB_OK || span1 >= span0) {  // no gain on this device: the map the plan had stays
+                (void)hipFree(P->d_item_map);
                 P->d_item_map = old;
                 P->item_map = old_host;
-                (void)hipFree(dm);
                 span1 = span0;
-            } else if (old) {
-                P->retired_item_maps.push_back(old);  // a hipGraph captured earlier may still name it: freed with the plan
+            } else {
+                item_map_retire(P, old);
             }
-        } else if (dm) {
-            (void)hipFree(dm);
         }
     }
     (void)hipFree(d);
     if (span_before_us) *span_before_us = span0;
     if (span_after_us) *span_after_us = stable ? span1 : span0;
     return rc;
+}
+
+// Diagnostics (tests/test_item_map_host.py, tests/test_gpu_item_map.py): the map in force read back, a map set by the caller,
+// and the tuner's decision on the caller's numbers (see ehyb.h).
+int ehyb_debug_item_map(const ehyb_plan* P, int32_t* out, int cap, int* n_items, int* installed)
+{
+    clear_error();
+    if (!P || !n_items || !installed || cap < 0 || (cap > 0 && !out)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_item_map: bad arguments");
+    const std::vector<int32_t> map_now = item_map_now(P);
+    *n_items = (int)map_now.size();
+    *installed = P->item_map.empty() ? 0 : 1;
+    std::copy(map_now.begin(), map_now.begin() + std::min((size_t)cap, map_now.size()), out);
+    return EHYB_OK;
+}
+
+int ehyb_debug_set_item_map(ehyb_plan* P, const int32_t* map, int n, int strict)
+{
+    clear_error();
+    if (!P || n < 0 || (n > 0 && !map) || (n == 0 && map)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_set_item_map: bad arguments");
+    const HostLayout& H = P->host;
+    const int n_items = (int)(H.items.size() / kItemWords);
+    if (H.direct || n_items == 0 || (H.pb_assign && H.segs.empty())) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_set_item_map: the plan has no window launch that takes items");
+    if (map && n != n_items) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_set_item_map: %d entries for a plan of %d items", n, n_items);
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (int b = 0; b < n; ++b) {
+        if (map[b] < 0 || map[b] >= n_items) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_set_item_map: entry %d is %d, the plan has items 0..%d", b, map[b], n_items - 1);
+        if (strict && seen[(size_t)map[b]]++) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_set_item_map: item %d is named twice (strict: a permutation)", map[b]);
+    }
+    if (!P->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_debug_set_item_map: the plan is not uploaded");
+    HIP_TRY(hipDeviceSynchronize());  // (no launch of this plan is under way while its map changes hands)
+    int32_t* old = nullptr;
+    if (item_map_install(P, std::vector<int32_t>(map, map + n), &old) != EHYB_OK) EHYB_FAIL(EHYB_ERR_HIP, "ehyb_debug_set_item_map: no device memory for %d entries", n);
+    item_map_retire(P, old);
+    HIP_TRY(hipDeviceSynchronize());
+    return EHYB_OK;
+}
+
+int ehyb_debug_tune_decide(int n_items, const double* cost, const int* xcc, const double* dur, const int32_t* map_now, int32_t* map_new, int* stable)
+{
+    clear_error();
+    if (n_items < 1 || !cost || !xcc || !dur || !map_now || !map_new || !stable) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_tune_decide: bad arguments");
+    for (int b = 0; b < n_items; ++b)
+        if (xcc[b] > 15 || map_now[b] < 0 || map_now[b] >= n_items)
+            EHYB_FAIL(EHYB_ERR_ARG, "ehyb_debug_tune_decide: workgroup %d on XCD %d with item %d (XCDs up to 15, items 0..%d)", b, xcc[b], map_now[b], n_items - 1);
+    std::vector<int32_t> out;
+    *stable = tune_decide(n_items, cost, xcc, dur, map_now, &out) ? 1 : 0;
+    if (*stable) std::copy(out.begin(), out.end(), map_new);
+    return EHYB_OK;
 }
 
 // Diagnostic (tools/panel_sweep.py): mean time of each pass of the panel residual alone, `iters` launches each

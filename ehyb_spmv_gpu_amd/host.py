@@ -501,6 +501,25 @@ class Plan:
         _check(self.lib.ehyb_plan_tune(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), reps, C.byref(a), C.byref(b)), "ehyb_plan_tune")
         return a.value, b.value
 
+    def item_map(self):
+        """ehyb_debug_item_map -> (the item every workgroup of the window launch takes, True if the plan holds a map of its own:
+        a tuned or a set one; False: the built-in order).  Host only."""
+        n, inst = C.c_int(0), C.c_int(0)
+        _check(self.lib.ehyb_debug_item_map(self.h, None, 0, C.byref(n), C.byref(inst)), "ehyb_debug_item_map")
+        out = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            _check(self.lib.ehyb_debug_item_map(self.h, _ptr(out, C.c_int32), len(out), C.byref(n), C.byref(inst)), "ehyb_debug_item_map")
+        return out, bool(inst.value)
+
+    def set_item_map(self, map, strict=True):
+        """ehyb_debug_set_item_map: workgroup b takes item map[b] from now on (None: the built-in order again).  strict=False
+        allows repeated and missing items: products are then wrong by design."""
+        if map is None:
+            _check(self.lib.ehyb_debug_set_item_map(self.h, None, 0, int(strict)), "ehyb_debug_set_item_map")
+            return
+        m = np.ascontiguousarray(map, dtype=np.int32)
+        _check(self.lib.ehyb_debug_set_item_map(self.h, _ptr(m, C.c_int32), len(m), int(strict)), "ehyb_debug_set_item_map")
+
     def launched(self):
         """ehyb_debug_launched -> {"window" / "panel" / "er_csr": set of the rows of kernel_table() this plan's launches took since
         the plan was made or launched_clear()}, each row a tuple of the table's fields"""
@@ -1006,6 +1025,18 @@ def spmv_gpu_ehyb(matrix, vector_in, max_iter, cfg=None, timing=False):
     _check(lib.spmvGPuEHYB_cfg(C.byref(matrix.c), _ptr(x, C.c_double), _ptr(y, C.c_double), max_iter, C.byref(it),
                                C.byref(cfg) if cfg is not None else None, C.byref(ms)), "spmvGPuEHYB")
     return (y, it.value, ms.value) if timing else (y, it.value)
+
+
+def tune_decide(cost, xcc, dur, map_now):
+    """ehyb_debug_tune_decide: the decision of ehyb_plan_tune on these numbers -> the new map, or None (no stable placement)"""
+    cost, dur = np.ascontiguousarray(cost, dtype=np.float64), np.ascontiguousarray(dur, dtype=np.float64)
+    xcc, map_now = np.ascontiguousarray(xcc, dtype=np.intc), np.ascontiguousarray(map_now, dtype=np.int32)
+    n = len(cost)
+    assert len(xcc) == len(dur) == len(map_now) == n
+    out, stable = np.full(n, -1, dtype=np.int32), C.c_int(-1)
+    _check(_lib.load().ehyb_debug_tune_decide(n, _ptr(cost, C.c_double), _ptr(xcc, C.c_int), _ptr(dur, C.c_double), _ptr(map_now, C.c_int32),
+                                              _ptr(out, C.c_int32), C.byref(stable)), "ehyb_debug_tune_decide")
+    return out if stable.value else None
 
 
 def host_threads():

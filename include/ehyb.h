@@ -673,6 +673,33 @@ int ehyb_plan_tune(ehyb_plan* plan, const double* x_dev, double* y_dev, int reps
  *                              was made or the log last cleared; cap >= the table's rows (EHYB_ERR_ARG otherwise).  A launch marks
  *                              its row with one byte store before it enqueues the kernel; a launch that finds nothing to do (no
  *                              item, no residual) marks nothing.  ehyb_debug_launched_clear zeroes all three logs.
+ * THE ITEM MAP.  Workgroup b of a window launch takes item map[b]; a launch that walks a plan of several rounds of workgroups from
+ * the far end (ehyb_spmv_walk 1) takes map[n_items - 1 - b].  The transposed launch and the stamped launch read the same map.
+ * ehyb_debug_item_map          the map in force: *n_items = stats.n_items, the first min(cap, *n_items) entries are written to out
+ *                              (out may be NULL with cap 0); *installed = 1 if the plan holds a map (ehyb_plan_tune kept one, or
+ *                              ehyb_debug_set_item_map set one), 0 if the launches take the built-in order, which is then what out
+ *                              receives: item b for symmetric pairs and cfg.xcd_map = 2, else one contiguous run of items per XCD
+ *                              (k = b mod 8, j = b / 8: item k * (n / 8) + min(k, n mod 8) + j).  Host only: needs no device and
+ *                              works on a plan that was never uploaded.
+ * ehyb_debug_set_item_map      installs map[0..n) as the plan's map, the way ehyb_plan_tune installs the one it keeps: the map it
+ *                              replaces stays allocated until the plan is destroyed, so a hipGraph captured under it stays valid.
+ *                              n must be stats.n_items and every entry in [0, n), whatever strict is: EHYB_ERR_ARG otherwise, the
+ *                              plan untouched.  strict = 1 also demands a permutation.  strict = 0 allows an item to be named
+ *                              twice and another not at all -- for tests that show that a kernel READS the map: the rows of an
+ *                              item nobody takes are not written (ehyb_spmv_t: not added), so products are WRONG by design, as
+ *                              with the stamp probes.  map = NULL with n = 0 removes the plan's map (back to the built-in order)
+ *                              and retires it the same way.  Any uploaded plan with a window launch: several rounds of
+ *                              workgroups and cfg.val_f32, which ehyb_plan_tune leaves alone, included.  EHYB_ERR_ARG for the
+ *                              direct shape and for plans without items; all of the above is checked first, then EHYB_ERR_STATE
+ *                              for a plan never uploaded.  Synchronises the device before it changes the map and before it returns.
+ * ehyb_debug_tune_decide       the decision of ehyb_plan_tune on the caller's numbers, a pure host function: cost[i] of item i,
+ *                              xcc[b] (0..15) and dur[b] (us) of workgroup b, which took item map_now[b].  The rate of an XCD is the
+ *                              median over its workgroups of cost[map_now[b]] / max(dur[b], 1e-3) (the upper median of an even
+ *                              count); XCDs are ordered fastest first, equal rates by id; items by falling cost, equal costs by
+ *                              index; each XCD's workgroups, in rising b, take the next items.  *stable = 1 and map_new[0..n_items)
+ *                              is that map -- or *stable = 0 and map_new untouched where some xcc[b] < 0 (ehyb_plan_tune: a
+ *                              workgroup that ran on two XCDs in two launches).  EHYB_ERR_ARG for a null pointer, n_items < 1, an
+ *                              xcc[b] > 15 or a map_now[b] outside [0, n_items).
  */
 enum { EHYB_KERNELS_WINDOW = 0, EHYB_KERNELS_PANEL = 1, EHYB_KERNELS_ER_CSR = 2 };
 enum { EHYB_KERNEL_ROW_WINDOW = 7, EHYB_KERNEL_ROW_PANEL = 6, EHYB_KERNEL_ROW_ER_CSR = 3 };
@@ -682,6 +709,9 @@ int ehyb_debug_panel_times(ehyb_plan* plan, const double* x_dev, double* y_dev, 
 int ehyb_debug_kernel_table(int which, int32_t* rows, int cap, int* n_rows);
 int ehyb_debug_launched(const ehyb_plan* plan, int which, uint8_t* out, int cap);
 int ehyb_debug_launched_clear(ehyb_plan* plan);
+int ehyb_debug_item_map(const ehyb_plan* plan, int32_t* out, int cap, int* n_items, int* installed);
+int ehyb_debug_set_item_map(ehyb_plan* plan, const int32_t* map, int n, int strict);
+int ehyb_debug_tune_decide(int n_items, const double* cost, const int* xcc, const double* dur, const int32_t* map_now, int32_t* map_new, int* stable);
 /*
  * The kernels of the transposed multiply (ehyb_spmv_t) have a table and a launch log of their own; the three tables above do not
  * list them.  EHYB_KERNEL_ROW_T = 3 ints per row: kind, threads, inl -- EHYB_KERNEL_T_WINDOW (the transposed window kernel) or

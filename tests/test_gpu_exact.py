@@ -246,8 +246,19 @@ def test_exact_tuned_plan(E, O, gpu):
     dx, dy = E.DeviceBuffer(c.n).upload(c.xp), E.DeviceBuffer(c.n)
     before, after = plan.tune(dx.ptr, dy.ptr, reps=3)
     assert before > 0 and 0 < after <= before
+    n_items = plan.stats["n_items"]
+    tuned, kept = plan.item_map()
+    print(f"ehyb_plan_tune: {before:.1f} -> {after:.1f} us, {'a map was kept' if kept else 'no gain: no map'}")
+    assert np.array_equal(np.sort(tuned), np.arange(n_items)), "the map in force takes every item once"
     for _ in range(2):
         assert_exact(multiply(E, plan, c.xp), c.y_ref_p, "tuned")
+    # whatever the tuner found on this device: the same check under a map that is set, on every run
+    shuffled = np.random.default_rng(1).permutation(n_items).astype(np.int32)
+    plan.set_item_map(shuffled)
+    got, installed = plan.item_map()
+    assert installed and np.array_equal(got, shuffled)
+    for _ in range(2):
+        assert_exact(multiply(E, plan, c.xp), c.y_ref_p, "under a shuffled map")
 
 
 # ---------------------------------------------------------------------------------------------- refill

@@ -187,4 +187,16 @@ def test_tuned_plan_logs_its_stamped_row(E, gpu):
     assert_exact(multiply(E, plan, X[0]), Y[0], "after ehyb_plan_tune")
     stamped_launch(E, plan, X[0], Y[0], "stamped, after ehyb_plan_tune")
     assert plan.launched()["window"] == {(512, 1, 1, 1, 0, 1, 0), (512, 1, 1, 0, 0, 1, 0)}
+    n_items = plan.stats["n_items"]
+    tuned, kept = plan.item_map()
+    print(f"ehyb_plan_tune: {before:.1f} -> {after:.1f} us, {'a map was kept' if kept else 'no gain: no map'}")
+    assert np.array_equal(np.sort(tuned), np.arange(n_items)), "the map in force takes every item once"
+    # whatever the tuner found on this device: the same checks under a map that is set, on every run
+    shuffled = np.random.default_rng(1).permutation(n_items).astype(np.int32)
+    plan.set_item_map(shuffled)
+    got, installed = plan.item_map()
+    assert installed and np.array_equal(got, shuffled)
+    assert_exact(multiply(E, plan, X[0]), Y[0], "under a shuffled map")
+    stamped_launch(E, plan, X[0], Y[0], "stamped, under a shuffled map")
+    assert plan.launched()["window"] == {(512, 1, 1, 1, 0, 1, 0), (512, 1, 1, 0, 0, 1, 0)}
     dx.free(), dy.free(), plan.destroy()

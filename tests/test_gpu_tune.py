@@ -29,8 +29,21 @@ def test_tuned_plan_multiplies_right(E, O, gpu, kw, gen):
             assert before == 0 and after == 0  # more than one round of workgroups: left alone
         else:
             assert before > 0 and 0 < after <= before
+        tuned, kept = plan.item_map()
+        print(f"round {rnd}: {before:.1f} -> {after:.1f} us, {'a map was kept' if kept else 'no map'}")
+        assert np.array_equal(np.sort(tuned), np.arange(st["n_items"])), "the map in force takes every item once"
         dy.upload(np.full(n, np.nan))
         plan.spmv(dx.ptr, dy.ptr)
         y = E.vector_recover(dy.download(), perm)
         bad, worst = O.check_strict(y, y_ref, scale)
         assert bad == 0, (rnd, worst)
+    # whatever the tuner found on this device: the same product check under a map that is set, on every run
+    shuffled = np.random.default_rng(1).permutation(st["n_items"]).astype(np.int32)
+    plan.set_item_map(shuffled)
+    got, installed = plan.item_map()
+    assert installed and np.array_equal(got, shuffled)
+    dy.upload(np.full(n, np.nan))
+    plan.spmv(dx.ptr, dy.ptr)
+    y = E.vector_recover(dy.download(), perm)
+    bad, worst = O.check_strict(y, y_ref, scale)
+    assert bad == 0, ("under a shuffled map", worst)
