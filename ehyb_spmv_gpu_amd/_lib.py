@@ -170,6 +170,7 @@ SIGNATURES = {
     "ehyb_partition_graph": (C.c_int, [C.c_int, _i64p, _ip, _ip, C.c_int, C.c_int, _cfgp, _ip, _i64p]),
     "ehyb_matrix_reorder": (C.c_int, [_mp, C.c_int, _cfgp]),
     "ehyb_matrix_reorder_blocks": (C.c_int, [_mp, C.c_int, _cfgp, _ip]),
+    "ehyb_matrix_reorder_like": (C.c_int, [_mp, _mp]),
     "spmvGPuEHYB_cfg": (C.c_int, [_mp, _dp, _dp, C.c_int, _ip, _cfgp, _dp]),
     "ehyb_vector_reorder": (None, [C.c_int, _dp, _dp, _ip]),
     "ehyb_vector_recover": (None, [C.c_int, _dp, _dp, _ip]),
@@ -328,6 +329,10 @@ SIGNATURES = {
     "ehyb_lobpcg_rr": (C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip]),
     "ehyb_lobpcg_gram_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_lobpcg_resid_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, C.c_uint, C.c_int64, _vp, _vp, _vp, _vp]),
+    "ehyb_lobpcg_gen": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _vp,
+                                  C.c_int64, _vp, _ip, _ip, _ip, _ip, _dp]),
+    "ehyb_lobpcg_gram_b_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_lobpcg_resid_b_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint, C.c_int64, _vp, _vp, _vp, _vp]),
     "ehyb_mm_read": (C.c_int, [C.c_char_p, _cfgp, _mp, _ip]),
     "ehyb_mm_write": (C.c_int, [C.c_char_p, _mp, C.c_int]),
     "ehyb_matrix_from_csr": (C.c_int, [C.c_int, _i64p, _ip, _dp, _cfgp, _mp]),

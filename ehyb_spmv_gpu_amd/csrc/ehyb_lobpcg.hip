@@ -11,6 +11,10 @@
 // 8 + 8 columns from LDS.  The loads of the next tile are in flight while the blocks of this one are summed.  At the end a wave
 // adds its lanes with the shuffle tree and lane 0 writes the block's entries of the upper triangle into the workgroup's own
 // slot; a second launch adds the slots in rising order and mirrors the triangle.  No atomics, no "last workgroup".
+//
+// ehyb_lobpcg_gen is the same driver for the pencil K x = lambda M x: a third image BS = M S beside S and AS (stored and rotated
+// for a mass plan, formed as m o s inside the kernels for a lumped mass), G = S^T BS, R = AX - theta BX.  Without a mass the driver
+// launches the kernels above and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -226,16 +230,224 @@ void launch_resid(int grid, int n, long long ld, const double* X, const double* 
     hipLaunchKernelGGL(lobpcg_resid_sum_kernel, dim3(1), dim3(64), 0, st, part, grid, nb, res2);
 }
 
+// ------------------------------------------------------------------ the pencil (A, M): ehyb_lobpcg_gen
+// The Gram kernel with a third image: G = S^T BS and H = S^T AS, BS = M S.  The shape is lobpcg_gram_kernel's -- twelve waves, one
+// 8 x 8 block each, lane l adds rows l and l + 64 of every tile, the same tile order, shuffle tree and grid -- so that BS == S
+// gives its bits.  The tile holds three groups of 24 columns x 128 rows, 73,728 B: dynamic LDS, opted in by launch_gram_b.
+// LUMPED: M = diag(m).  No third stream leaves memory: a wave forms m[r] S[r, c] (one rounding) from the S pairs it fetched
+// and the tile's m pair while it fills the tile.
+constexpr int kGramBTile = 3 * kS * kGramRows;  // doubles of the tile: S, AS, BS
+constexpr int kGramBLds = kGramBTile * (int)sizeof(double);
+
+template <bool LUMPED>
+__global__ __launch_bounds__(kGramThreads) void lobpcg_gram_b_kernel(int n, long long ld_, const double* __restrict__ S,
+                                                                     const double* __restrict__ AS, const double* __restrict__ BS,
+                                                                     const double* __restrict__ m, int mc, double* __restrict__ part)
+{
+    // column q < 24 of the tile is column q of S, 24 + q column q of AS, 48 + q column q of BS; columns >= mc stay zero
+    extern __shared__ __attribute__((aligned(16))) double tile[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // uniform: column bases in scalar registers
+    for (int k = threadIdx.x; k < kGramBTile; k += kGramThreads) tile[k] = 0.0;
+    const int groups = (mc + kGroup - 1) / kGroup;
+    const int b = wave % 6;
+    const bool is_h = wave >= 6, active = b < groups * (groups + 1) / 2;
+    const int gi = kBlockI[b], gj = kBlockJ[b];
+    const double* a_sh = tile + (size_t)gi * kGroup * kGramRows;
+    const double* b_sh = tile + (size_t)((is_h ? kS : 2 * kS) + gj * kGroup) * kGramRows;
+    const size_t ld = (size_t)ld_;
+    const long long tiles = ((long long)n + kGramRows - 1) / kGramRows;
+
+    // a wave copies columns wave and wave + 12 of every group -- number k = 2 group + (0 or 1) -- lane l the pair (2l, 2l + 1) of
+    // each: k < 6 with BS in memory; LUMPED: k < 4, and its two columns of S, scaled by the pair of m, are its two of the third group
+    constexpr int kFetch = LUMPED ? 4 : 6;
+    double2 pre[kFetch], mp = {0.0, 0.0};
+    auto fetch = [&](long long t) {
+        const long long i = t * kGramRows + 2 * lane;
+        if (LUMPED) {
+            if (i + 1 < n)
+                mp = load2(m + i);
+            else
+                mp = {i < n ? m[i] : 0.0, 0.0};
+        }
+#pragma unroll
+        for (int k = 0; k < kFetch; ++k) {
+            const int c = wave + kGramWaves * (k & 1);
+            if (c >= mc) continue;
+            const double* col = (k < 2 ? S : k < 4 ? AS : BS) + (size_t)c * ld;
+            if (i + 1 < n)
+                pre[k] = load2(col + i);
+            else
+                pre[k] = {i < n ? col[i] : 0.0, 0.0};
+        }
+    };
+    auto put = [&]() {
+#pragma unroll
+        for (int k = 0; k < kFetch; ++k) {
+            const int c = wave + kGramWaves * (k & 1);
+            if (c >= mc) continue;
+            store2(tile + (size_t)(kS * (k / 2) + c) * kGramRows + 2 * lane, pre[k]);
+            if (LUMPED && k < 2) store2(tile + (size_t)(2 * kS + c) * kGramRows + 2 * lane, double2{mp.x * pre[k].x, mp.y * pre[k].y});
+        }
+    };
+
+    double acc[kGroup][kGroup];
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) acc[i][j] = 0.0;
+    }
+    long long t = blockIdx.x;
+    if (t < tiles) fetch(t);
+    __syncthreads();  // the zeros are in place
+    for (; t < tiles; t += gridDim.x) {
+        put();
+        __syncthreads();
+        if (t + gridDim.x < tiles) fetch(t + gridDim.x);
+        __builtin_amdgcn_sched_barrier(0);  // the loads are issued before the sums, not sunk behind them
+        if (active) {
+#pragma unroll 1  // as lobpcg_gram_kernel: 64 sums fill the registers of a wave that shares its SIMD with two more
+            for (int r = lane; r < kGramRows; r += 64) {
+                // four columns of a at a time, the halves kept apart: the registers this frees hold the next tile's third group.
+                // Every sum still takes one term per row, in the order of the rows
+#pragma unroll
+                for (int h = 0; h < kGroup; h += 4) {
+                    double a[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) a[i] = a_sh[(h + i) * kGramRows + r];
+#pragma unroll
+                    for (int j = 0; j < kGroup; ++j) {
+                        const double bj = b_sh[j * kGramRows + r];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[h + i][j] = fma(a[i], bj, acc[h + i][j]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        __syncthreads();  // the tile is free
+    }
+    if (!active) return;
+    double* slot = part + (size_t)blockIdx.x * kGramSlot + (is_h ? kS * kS : 0);
+#pragma unroll
+    for (int j = 0; j < kGroup; ++j) {
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            double v = acc[i][j];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            const int I = gi * kGroup + i, J = gj * kGroup + j;
+            if (lane == 0 && I <= J && J < mc) slot[I + J * kS] = v;
+        }
+    }
+}
+
+// lobpcg_resid_kernel with R_c = AX_c - theta_c BX_c: BX read next to X, or LUMPED formed as m o X (one rounding)
+template <bool LUMPED>
+__global__ __launch_bounds__(kThreads) void lobpcg_resid_b_kernel(int n, long long ld_, const double* __restrict__ X,
+                                                                  const double* __restrict__ AX, const double* __restrict__ BX,
+                                                                  const double* __restrict__ m, int nb, const double* __restrict__ theta,
+                                                                  const double* __restrict__ dinv, unsigned mask, long long ldw_, double* W,
+                                                                  double* __restrict__ part)
+{
+    __shared__ double th[kBlock];
+    if (threadIdx.x < kBlock) th[threadIdx.x] = (int)threadIdx.x < nb ? theta[threadIdx.x] : 0.0;
+    __syncthreads();
+    double acc[kBlock];
+#pragma unroll
+    for (int c = 0; c < kBlock; ++c) acc[c] = 0.0;
+    const size_t ld = (size_t)ld_, ldw = (size_t)ldw_;
+    const int stride = (int)gridDim.x * kThreads;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        const bool pair = i + 1 < (size_t)n;
+        double2 d = {1.0, 1.0}, mm = {0.0, 0.0};
+        if (dinv && mask) d = pair ? load2(dinv + i) : double2{dinv[i], 1.0};
+        if (LUMPED) mm = pair ? load2(m + i) : double2{m[i], 0.0};
+#pragma unroll
+        for (int c = 0; c < kBlock; ++c) {
+            if (c >= nb) break;
+            const double* src = LUMPED ? X : BX;
+            double2 bx, ax;
+            if (pair) {
+                bx = load2(src + (size_t)c * ld + i);
+                ax = load2(AX + (size_t)c * ld + i);
+            } else {
+                bx = {src[(size_t)c * ld + i], 0.0};
+                ax = {AX[(size_t)c * ld + i], 0.0};
+            }
+            if (LUMPED) {
+                bx.x *= mm.x;
+                bx.y *= mm.y;
+            }
+            double2 r;
+            r.x = fma(-th[c], bx.x, ax.x);
+            r.y = fma(-th[c], bx.y, ax.y);
+            acc[c] = fma(r.y, r.y, fma(r.x, r.x, acc[c]));
+            if (mask >> c & 1u) {
+                double* w = W + (size_t)__popc(mask & ((1u << c) - 1u)) * ldw + i;
+                if (dinv) {
+                    r.x *= d.x;
+                    r.y *= d.y;
+                }
+                if (pair)
+                    store2(w, r);
+                else
+                    *w = r.x;
+            }
+        }
+    }
+    block_sum_n(acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < kBlock; ++c) part[(size_t)blockIdx.x * kBlock + c] = acc[c];
+    }
+}
+
+// exactly one of BS and m is given.  The tile is over the 64 KiB a kernel gets without asking: the opt-in comes before the launch.
+hipError_t launch_gram_b(int n, long long ld, const double* S, const double* AS, const double* BS, const double* m, int mc, double* G,
+                         double* H, double* part, hipStream_t st)
+{
+    const int grid = gram_grid(n);
+    const void* fn = m ? reinterpret_cast<const void*>(lobpcg_gram_b_kernel<true>) : reinterpret_cast<const void*>(lobpcg_gram_b_kernel<false>);
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kGramBLds);
+    if (e != hipSuccess) return e;
+    if (m)
+        hipLaunchKernelGGL(lobpcg_gram_b_kernel<true>, dim3(grid), dim3(kGramThreads), kGramBLds, st, n, ld, S, AS, BS, m, mc, part);
+    else
+        hipLaunchKernelGGL(lobpcg_gram_b_kernel<false>, dim3(grid), dim3(kGramThreads), kGramBLds, st, n, ld, S, AS, BS, m, mc, part);
+    hipLaunchKernelGGL(lobpcg_gram_sum_kernel, dim3((2 * mc * mc + kThreads - 1) / kThreads), dim3(kThreads), 0, st, part, grid, mc, G, H);
+    return hipGetLastError();
+}
+
+void launch_resid_b(int grid, int n, long long ld, const double* X, const double* AX, const double* BX, const double* m, int nb,
+                    const double* theta, const double* dinv, unsigned mask, long long ldw, double* W, double* part, double* res2, hipStream_t st)
+{
+    if (m)
+        hipLaunchKernelGGL(lobpcg_resid_b_kernel<true>, dim3(grid), dim3(kThreads), 0, st, n, ld, X, AX, BX, m, nb, theta, dinv, mask, ldw, W, part);
+    else
+        hipLaunchKernelGGL(lobpcg_resid_b_kernel<false>, dim3(grid), dim3(kThreads), 0, st, n, ld, X, AX, BX, m, nb, theta, dinv, mask, ldw, W, part);
+    hipLaunchKernelGGL(lobpcg_resid_sum_kernel, dim3(1), dim3(64), 0, st, part, grid, nb, res2);
+}
+
 // ------------------------------------------------------------------ the driver
+// the mass matrix of ehyb_lobpcg_gen: a plan, a diagonal, or neither (ehyb_lobpcg: M = I and the kernels without a third image)
+struct Mass {
+    ehyb_plan* plan;
+    const double* diag;
+    double bnorm;
+    bool any() const { return plan || diag; }
+};
+
 struct Outputs {
     int nev;
     double *evals, *resid;
-    int *nconv, *iters, *multiplies;
-    void counts(int c, int it, int mu) const
+    int *nconv, *iters, *multiplies, *mass_multiplies;
+    void counts(int c, int it, int mu, int mm) const
     {
         if (nconv) *nconv = c;
         if (iters) *iters = it;
         if (multiplies) *multiplies = mu;
+        if (mass_multiplies) *mass_multiplies = mm;
     }
     void values(const double* theta, const double* res) const
     {
@@ -260,24 +472,26 @@ inline double start_entry(uint32_t i, uint32_t j)
 enum { D_THETA = 0, D_RES2 = D_THETA + kBlock, D_Y = D_RES2 + kBlock, D_G = D_Y + kS * 2 * kBlock, D_H = D_G + kS * kS,
        D_PART = D_H + kS * kS, D_COUNT = D_PART + (kMaxGrid / 2) * kBlock };
 
-int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const double* X0, int64_t ldx0, int nev, int nb, int max_iter,
-                 double tol, double anorm, double* evecs, int64_t ldv, void* stream, const Outputs& out)
+int lobpcg_solve(const char* who, ehyb_plan* P, const Mass& mass, ehyb_coarse* coarse, const double* dinv, const double* X0, int64_t ldx0,
+                 int nev, int nb, int max_iter, double tol, double anorm, double* evecs, int64_t ldv, void* stream, const Outputs& out)
 {
     const int n = P->host.n_cols;
     const size_t ld = (size_t)n + (n & 1);
     SolveLoop L(n, 0);
     double* sm;
     HIP_TRY(L.begin(stream, {}, 0, &sm, 0, D_COUNT));
-    // two pairs (S, AS) of 3 nb columns: one holds [X | P | W], the other receives the rotation; they swap by pointer
-    double *S[2], *AS[2], *gram_part, *Rs = nullptr;
+    // two pairs (S, AS) of 3 nb columns: one holds [X | P | W], the other receives the rotation; they swap by pointer.  A mass
+    // plan makes them triples (S, AS, BS); a lumped mass is applied where S is read
+    double *S[2], *AS[2], *BS[2] = {nullptr, nullptr}, *gram_part, *Rs = nullptr;
     for (int p = 0; p < 2; ++p) {
         HIP_TRY(L.more(&S[p], ld * 3 * (size_t)nb));
         HIP_TRY(L.more(&AS[p], ld * 3 * (size_t)nb));
+        if (mass.plan) HIP_TRY(L.more(&BS[p], ld * 3 * (size_t)nb));
     }
     HIP_TRY(L.more(&gram_part, (size_t)kGramGrid * kGramSlot));
     if (coarse) HIP_TRY(L.more(&Rs, ld * (size_t)nb));
     const hipStream_t st = L.st;
-    int cur = 0, it = 0, mult = 0, walks = 0;
+    int cur = 0, it = 0, mult = 0, walks = 0, mass_mult = 0, mass_walks = 0;
 
     std::vector<double> start;
     if (X0) {
@@ -291,14 +505,28 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
     }
     auto multiply = [&](int c0, int k) -> int {
         mult += k;
-        return ehyb_spmm(P, S[cur] + (size_t)c0 * ld, (int64_t)ld, AS[cur] + (size_t)c0 * ld, (int64_t)ld, k, st,
-                         walks++ & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
+        const int rc = ehyb_spmm(P, S[cur] + (size_t)c0 * ld, (int64_t)ld, AS[cur] + (size_t)c0 * ld, (int64_t)ld, k, st,
+                                 walks++ & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
+        if (rc != EHYB_OK || !mass.plan) return rc;
+        mass_mult += k;
+        return ehyb_spmm(mass.plan, S[cur] + (size_t)c0 * ld, (int64_t)ld, BS[cur] + (size_t)c0 * ld, (int64_t)ld, k, st,
+                         mass_walks++ & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
+    };
+    auto resid = [&](unsigned mask, const double* scale, double* W) {
+        if (mass.any())
+            launch_resid_b(L.grid, n, (long long)ld, S[cur], AS[cur], BS[cur], mass.diag, nb, sm + D_THETA, scale, mask, (long long)ld, W,
+                           sm + D_PART, sm + D_RES2, st);
+        else
+            launch_resid(L.grid, n, (long long)ld, S[cur], AS[cur], nb, sm + D_THETA, scale, mask, (long long)ld, W, sm + D_PART, sm + D_RES2, st);
     };
     std::vector<double> GH((size_t)2 * kS * kS), theta(kBlock), Y((size_t)kS * kBlock), YY((size_t)kS * 2 * kBlock), res2(kBlock), res(kBlock);
     std::string why;
     // the Gram matrices of the first mc columns, the projected problem, the rotation by kc columns into the other pair, the swap
     auto rayleigh_ritz = [&](int mc, bool with_p, bool* broke) -> int {
-        launch_gram(n, (long long)ld, S[cur], AS[cur], mc, sm + D_G, sm + D_H, gram_part, st);
+        if (mass.any())
+            HIP_TRY(launch_gram_b(n, (long long)ld, S[cur], AS[cur], BS[cur], mass.diag, mc, sm + D_G, sm + D_H, gram_part, st));
+        else
+            launch_gram(n, (long long)ld, S[cur], AS[cur], mc, sm + D_G, sm + D_H, gram_part, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(GH.data(), sm + D_G, GH.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -319,13 +547,14 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
         HIP_TRY(hipMemcpyAsync(sm + D_THETA, theta.data(), kBlock * sizeof(double), hipMemcpyHostToDevice, st));
         int rc = ehyb_eigsh_rotate_step(n, (int64_t)ld, S[cur], (int64_t)ld, S[cur ^ 1], sm + D_Y, mc, kc, st);
         if (rc == EHYB_OK) rc = ehyb_eigsh_rotate_step(n, (int64_t)ld, AS[cur], (int64_t)ld, AS[cur ^ 1], sm + D_Y, mc, kc, st);
+        if (rc == EHYB_OK && mass.plan) rc = ehyb_eigsh_rotate_step(n, (int64_t)ld, BS[cur], (int64_t)ld, BS[cur ^ 1], sm + D_Y, mc, kc, st);
         cur ^= 1;
         return rc;
     };
     auto breakdown = [&]() -> int {
         out.values(nullptr, nullptr);
-        out.counts(0, it, mult);
-        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg: breakdown after %d iterations (%s)", it, why.c_str());
+        out.counts(0, it, mult, mass_mult);
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown after %d iterations (%s)", who, it, why.c_str());
     };
 
     int rc = multiply(0, nb);
@@ -342,8 +571,7 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
         // every column as active -- W where it belongs, or with a coarse object R into the scratch columns, which is all the
         // coarse apply needs.  Without a coarse object, once a column has converged, a second launch packs W for the active
         // ones: it reads X and AX again (2 nb + 1 vectors read, na written) and leaves the same res2.
-        launch_resid(L.grid, n, (long long)ld, S[cur], AS[cur], nb, sm + D_THETA, coarse ? nullptr : dinv, all, (long long)ld,
-                     coarse ? Rs : S[cur] + (size_t)w0 * ld, sm + D_PART, sm + D_RES2, st);
+        resid(all, coarse ? nullptr : dinv, coarse ? Rs : S[cur] + (size_t)w0 * ld);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(res2.data(), sm + D_RES2, kBlock * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // the first look; Y and theta are the host's again
@@ -352,7 +580,7 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
         for (int c = 0; c < nb; ++c) {
             res[c] = std::sqrt(res2[c]);
             finite = finite && std::isfinite(res[c]) && std::isfinite(theta[c]);
-            nrm = std::max(nrm, std::fabs(theta[c]));
+            nrm = std::max(nrm, mass.bnorm * std::fabs(theta[c]));
         }
         if (!finite) {
             why = "a non-finite Ritz value or residual norm";
@@ -371,8 +599,7 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
                     if (rc != EHYB_OK) return rc;
                 }
         } else if (active != all) {  // the active columns packed
-            launch_resid(L.grid, n, (long long)ld, S[cur], AS[cur], nb, sm + D_THETA, dinv, active, (long long)ld, S[cur] + (size_t)w0 * ld,
-                         sm + D_PART, sm + D_RES2, st);
+            resid(active, dinv, S[cur] + (size_t)w0 * ld);
         }
         if ((rc = multiply(w0, na)) != EHYB_OK) return rc;
         if ((rc = rayleigh_ritz(w0 + na, true, &broke)) != EHYB_OK) return rc;  // the second look
@@ -385,7 +612,7 @@ int lobpcg_solve(ehyb_plan* P, ehyb_coarse* coarse, const double* dinv, const do
         HIP_TRY(hipStreamSynchronize(st));
     }
     out.values(theta.data(), res.data());
-    out.counts(nconv, it, mult);
+    out.counts(nconv, it, mult, mass_mult);
     return EHYB_OK;
 }
 
@@ -415,8 +642,44 @@ extern "C" int ehyb_lobpcg(ehyb_plan* P, ehyb_coarse* coarse, const double* inv_
     const int rc = solve_uploaded("ehyb_lobpcg", P);
     if (rc != EHYB_OK) return rc;
     if (coarse && !coarse->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_lobpcg: coarse object not uploaded");
-    const Outputs out{nev, evals, resid, nconv, iters_done, multiplies};
-    return lobpcg_solve(P, coarse, inv_diag, X0, ldx0, nev, nb, max_iter, tol, anorm, evecs, ldv, stream, out);
+    const Outputs out{nev, evals, resid, nconv, iters_done, multiplies, nullptr};
+    return lobpcg_solve("ehyb_lobpcg", P, Mass{nullptr, nullptr, 1.0}, coarse, inv_diag, X0, ldx0, nev, nb, max_iter, tol, anorm, evecs, ldv, stream,
+                        out);
+}
+
+extern "C" int ehyb_lobpcg_gen(ehyb_plan* P, ehyb_plan* MP, const double* mass_diag, ehyb_coarse* coarse, const double* inv_diag,
+                               const double* X0, int64_t ldx0, int nev, int block, int max_iter, double tol, double anorm, double bnorm,
+                               double* evals, double* evecs, int64_t ldv, void* stream, int* nconv, int* iters_done, int* multiplies,
+                               int* mass_multiplies, double* resid)
+{
+    clear_error();
+    if (!P) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: null argument");
+    const int nb = block == 0 ? nev : block;
+    if (nev < 1 || nb < nev || nb > EHYB_LOBPCG_MAX_BLOCK || max_iter < 0)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: nev %d (1 .. block), block %d (0 or nev .. %d), max_iter %d", nev, block, EHYB_LOBPCG_MAX_BLOCK,
+                  max_iter);
+    if (!(tol >= 0) || !(anorm >= 0) || !std::isfinite(anorm) || !(bnorm >= 0) || !std::isfinite(bnorm))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: tol %g, anorm %g, bnorm %g", tol, anorm, bnorm);
+    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: needs a plan over all rows");
+    const int n = P->host.n_cols;
+    if (!MP == !mass_diag) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: exactly one of mass_plan and mass_diag_dev must be given");
+    if (MP && (MP->host.row_begin != 0 || MP->host.row_end != MP->host.n_cols || MP->host.n_cols != n))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: the mass plan must cover all rows of a matrix of %d rows (it has rows %d .. %d of %d)", n,
+                  MP->host.row_begin, MP->host.row_end, MP->host.n_cols);
+    if (((uintptr_t)mass_diag & 15) != 0) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: mass_diag_dev must be 16-byte aligned");
+    if (nb > n) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: a block of %d vectors for %d rows", nb, n);
+    if ((evecs && (ldv < n || (ldv & 1))) || (X0 && (ldx0 < n || (ldx0 & 1))))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: ldv %lld and ldx0 %lld must be even and >= %d rows", (long long)ldv, (long long)ldx0, n);
+    if ((((uintptr_t)evecs | (uintptr_t)inv_diag | (uintptr_t)X0) & 15) != 0)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: evecs_dev, inv_diag_dev and X0_dev must be 16-byte aligned");
+    if (coarse && coarse->n != n) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gen: the coarse object has %d rows, the plan %d", coarse->n, n);
+    int rc = solve_uploaded("ehyb_lobpcg_gen", P);
+    if (rc != EHYB_OK) return rc;
+    if (MP && !MP->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_lobpcg_gen: mass plan not uploaded");
+    if (coarse && !coarse->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_lobpcg_gen: coarse object not uploaded");
+    const Outputs out{nev, evals, resid, nconv, iters_done, multiplies, mass_multiplies};
+    return lobpcg_solve("ehyb_lobpcg_gen", P, Mass{MP, mass_diag, bnorm == 0 ? 1.0 : bnorm}, coarse, inv_diag, X0, ldx0, nev, nb, max_iter, tol, anorm,
+                        evecs, ldv, stream, out);
 }
 
 // host only
@@ -494,6 +757,38 @@ extern "C" int ehyb_lobpcg_gram_step(int n, int64_t ld, const double* S, const d
     if (mc < 1 || mc > kS) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gram_step: bad arguments (mc %d, 1 .. %d)", mc, kS);
     if ((rc = check_pairs("ehyb_lobpcg_gram_step", n, ld, {S, AS})) != EHYB_OK) return rc;
     launch_gram(n, (long long)ld, S, AS, mc, G, H, scratch, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_lobpcg_gram_b_step(int n, int64_t ld, const double* S, const double* AS, const double* BS, const double* mass_diag, int mc,
+                                       double* G, double* H, double* scratch, void* stream)
+{
+    clear_error();
+    int rc = check_step("ehyb_lobpcg_gram_b_step", n, {S, AS, G, H, scratch});
+    if (rc != EHYB_OK) return rc;
+    if (!BS == !mass_diag) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gram_b_step: exactly one of BS_dev and mass_diag_dev must be given");
+    if (mc < 1 || mc > kS) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_gram_b_step: bad arguments (mc %d, 1 .. %d)", mc, kS);
+    if ((rc = check_pairs("ehyb_lobpcg_gram_b_step", n, ld, {S, AS, BS, mass_diag})) != EHYB_OK) return rc;
+    HIP_TRY(launch_gram_b(n, (long long)ld, S, AS, BS, mass_diag, mc, G, H, scratch, (hipStream_t)stream));
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_lobpcg_resid_b_step(int n, int64_t ld, const double* X, const double* AX, const double* BX, const double* mass_diag, int nb,
+                                        const double* theta, const double* inv_diag, unsigned active_mask, int64_t ldw, double* W, double* res2,
+                                        double* scratch, void* stream)
+{
+    clear_error();
+    int rc = check_step("ehyb_lobpcg_resid_b_step", n, {X, AX, theta, res2, scratch});
+    if (rc != EHYB_OK) return rc;
+    if (!BX == !mass_diag) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_resid_b_step: exactly one of BX_dev and mass_diag_dev must be given");
+    if (nb < 1 || nb > kBlock || active_mask >> nb != 0 || (active_mask && !W))
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_lobpcg_resid_b_step: bad arguments (nb %d, 1 .. %d; active mask 0x%x within nb bits, with its W)", nb, kBlock,
+                  active_mask);
+    if ((rc = check_pairs("ehyb_lobpcg_resid_b_step", n, ld, {X, AX, BX, mass_diag, inv_diag})) != EHYB_OK) return rc;
+    if (active_mask && (rc = check_pairs("ehyb_lobpcg_resid_b_step", n, ldw, {W})) != EHYB_OK) return rc;
+    launch_resid_b(kStepGrid, n, (long long)ld, X, AX, BX, mass_diag, nb, theta, inv_diag, active_mask, (long long)ldw, W, scratch, res2,
+                   (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }

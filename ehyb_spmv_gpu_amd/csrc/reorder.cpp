@@ -851,3 +851,92 @@ extern "C" int ehyb_top_boundary(const matrixCOO* m, const ehyb_config* cfg, int
     part_of_block[n_top] = np;
     return EHYB_OK;
 }
+
+// A second matrix in the numbering of a reordered one: new row `pos` is b's old row with a->reorderList[old] == pos, its entries
+// sorted by their new columns (equal columns keep their stored order), and a's partition data so that a plan of b walks a's partitions.
+extern "C" int ehyb_matrix_reorder_like(matrixCOO* b, const matrixCOO* a)
+{
+    clear_error();
+    if (!b || !a) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: null argument");
+    if (b->dimension <= 0 || b->totalNum < 0 || !b->I || !b->J || !b->V || !b->rowIdx || !b->numInRow || !b->numInRow2 || !b->partBoundary ||
+        !b->reorderList)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: incomplete matrixCOO");
+    const int n = b->dimension;
+    if (a->dimension != n) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: %d rows, the reordered matrix has %d", n, a->dimension);
+    const int nparts = a->nParts;
+    if (nparts < 1 || !a->partBoundary || !a->reorderList || a->partBoundary[0] != 0 || a->partBoundary[nparts] != n)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: the other matrix carries no partition data (call ehyb_matrix_reorder on it first)");
+    const int64_t nnz = b->totalNum;
+    if (b->rowIdx[0] != 0 || b->rowIdx[n] != nnz) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: rowIdx does not span the %lld entries", (long long)nnz);
+    const int* list = a->reorderList;
+    std::vector<int> old_of(n, -1);
+    for (int i = 0; i < n; ++i) {
+        const int t = list[i];
+        if ((unsigned)t >= (unsigned)n || old_of[t] >= 0) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: reorderList is not a permutation (entry %d)", i);
+        old_of[t] = i;
+    }
+    for (int p = 0; p < nparts; ++p)
+        if (a->partBoundary[p] > a->partBoundary[p + 1]) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: partBoundary falls at partition %d", p);
+    for (int i = 0; i < n; ++i) {
+        if (b->rowIdx[i] > b->rowIdx[i + 1]) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: rowIdx falls at row %d", i);
+        for (int k = b->rowIdx[i]; k < b->rowIdx[i + 1]; ++k)
+            if ((unsigned)b->J[k] >= (unsigned)n) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_matrix_reorder_like: entry %d has column %d outside the %d x %d matrix", k, b->J[k], n, n);
+    }
+    const size_t e = (size_t)std::max<int64_t>(nnz, 1);
+    int* nI = (int*)malloc(e * sizeof(int));
+    int* nJ = (int*)malloc(e * sizeof(int));
+    double* nV = (double*)malloc(e * sizeof(double));
+    if (!nI || !nJ || !nV) {
+        free(nI);
+        free(nJ);
+        free(nV);
+        EHYB_FAIL(EHYB_ERR_ALLOC, "ehyb_matrix_reorder_like: out of memory for %lld entries", (long long)nnz);
+    }
+    const std::vector<int> old_rp(b->rowIdx, b->rowIdx + n + 1);
+    int* rp = b->rowIdx;
+    int maxcol = 0;
+    rp[0] = 0;
+    for (int pos = 0; pos < n; ++pos) {
+        b->numInRow[pos] = old_rp[old_of[pos] + 1] - old_rp[old_of[pos]];
+        rp[pos + 1] = rp[pos] + b->numInRow[pos];
+        maxcol = std::max(maxcol, b->numInRow[pos]);
+    }
+    std::vector<int> part_start(n);
+    for (int p = 0; p < nparts; ++p)
+        for (int t = a->partBoundary[p]; t < a->partBoundary[p + 1]; ++t) part_start[t] = a->partBoundary[p];
+    const int cache = (int)a->vectorCacheSize;
+    OmpScope omp(0);
+#pragma omp parallel
+    {
+        std::vector<std::pair<int, int>> row;  // (new column, old entry)
+#pragma omp for schedule(dynamic, 1024)
+        for (int ti = 0; ti < n; ++ti) {
+            const int oi = old_of[ti], ps = part_start[ti];
+            row.clear();
+            for (int k = old_rp[oi]; k < old_rp[oi + 1]; ++k) row.emplace_back(list[b->J[k]], k);
+            std::sort(row.begin(), row.end());
+            int64_t dst = rp[ti];
+            int in_window = 0;
+            for (const auto& ck : row) {
+                nI[dst] = ti;
+                nJ[dst] = ck.first;
+                nV[dst++] = b->V[ck.second];
+                in_window += ck.first >= ps && ck.first < ps + cache;
+            }
+            b->numInRow2[ti] = in_window;
+        }
+    }
+    free(b->I);
+    free(b->J);
+    free(b->V);
+    b->I = nI;
+    b->J = nJ;
+    b->V = nV;
+    b->maxCol = maxcol;
+    b->nParts = nparts;
+    b->vectorCacheSize = a->vectorCacheSize;
+    b->kernelPerPart = a->kernelPerPart;
+    std::copy(a->partBoundary, a->partBoundary + nparts + 1, b->partBoundary);
+    std::copy(list, list + n, b->reorderList);
+    return EHYB_OK;
+}

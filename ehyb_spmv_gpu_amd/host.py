@@ -263,6 +263,13 @@ class Matrix:
         self.block_first = [int(b) for b in blocks]
         return self
 
+    def reorder_like(self, other):
+        """ehyb_matrix_reorder_like, in place: this matrix, in the ORIGINAL numbering of `other` (a Matrix that has been through
+        reorder()), takes other's permutation -- new = other.reorder_list[old], as vector_reorder -- and its partitions, so that a
+        Plan of it lives in other's numbering (a mass matrix beside its stiffness matrix).  Build that Plan with sym_pairs=2."""
+        _check(self.lib.ehyb_matrix_reorder_like(C.byref(self.c), C.byref(other.c)), "ehyb_matrix_reorder_like")
+        return self
+
     def reorder_dropin(self):
         """matrixReorder(m) / matrixReorder_unsym(m) exactly as the reference's driver calls them
         (solver_test.c:369-374; the C++-linkage symbols of include/reordering.h): no configuration,
@@ -770,6 +777,45 @@ class Plan:
         if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
             raise EhybError(rc, "ehyb_lobpcg")
         info = {"nconv": nconv.value, "iters": iters.value, "multiplies": mult.value, "resid": resid[:nev].copy()}
+        X = dv.download().reshape(-1, ld)[:nev, :n].copy() if dv else None
+        return evals[:nev].copy(), X, info
+
+    def lobpcg_gen(self, nev, mass, block=0, coarse=None, inv_diag=None, X0=None, max_iter=500, tol=1e-8, anorm=0.0, bnorm=0.0,
+                   vectors=True, allow_breakdown=False, stream=0):
+        """ehyb_lobpcg_gen: the nev smallest eigenpairs of K x = lambda M x, K this plan's symmetric matrix.  `mass` is an uploaded
+        Plan of the consistent mass matrix in this plan's numbering (Matrix.reorder_like) or a length-n array, the lumped mass
+        diagonal in the permuted numbering.  Everything else as lobpcg(), except: a column has converged when
+        ||K x - theta M x|| <= tol * max(bnorm * max |theta|, anorm) with bnorm the caller's scale of ||M|| (0: 1), the vectors
+        come out with X M X^T = I, and info gains "mass_multiplies" (0 for a lumped mass)."""
+        n, nev = self.n, int(nev)
+        nb = nev if int(block) == 0 else int(block)
+        ld = n + (n & 1)
+        mass_plan = mass if isinstance(mass, Plan) else None
+        dm = None
+        if mass_plan is None:
+            mass = np.ascontiguousarray(mass, dtype=np.float64)
+            assert mass.shape == (n,), (mass.shape, n)
+            dm = DeviceBuffer(n).upload(mass)
+        dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
+        d0 = None
+        if X0 is not None:
+            X0 = np.ascontiguousarray(X0, dtype=np.float64)
+            assert X0.shape == (nb, n), (X0.shape, nb, n)
+            padded = np.zeros((nb, ld))
+            padded[:, :n] = X0
+            d0 = DeviceBuffer(nb * ld).upload(padded.ravel())
+        dv = DeviceBuffer(max(nev, 1) * ld).upload(np.zeros(max(nev, 1) * ld)) if vectors else None
+        evals, resid = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        nconv, iters, mult, mmult = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self.lib.ehyb_lobpcg_gen(self.h, mass_plan.h if mass_plan is not None else None, C.c_void_p(dm.ptr) if dm else None,
+                                      coarse.h if coarse is not None else None, C.c_void_p(dd.ptr) if dd else None,
+                                      C.c_void_p(d0.ptr) if d0 else None, ld, nev, int(block), int(max_iter), tol, anorm, bnorm,
+                                      _ptr(evals, C.c_double), C.c_void_p(dv.ptr) if dv else None, ld, C.c_void_p(stream), C.byref(nconv),
+                                      C.byref(iters), C.byref(mult), C.byref(mmult), _ptr(resid, C.c_double))
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, "ehyb_lobpcg_gen")
+        info = {"nconv": nconv.value, "iters": iters.value, "multiplies": mult.value, "mass_multiplies": mmult.value,
+                "resid": resid[:nev].copy()}
         X = dv.download().reshape(-1, ld)[:nev, :n].copy() if dv else None
         return evals[:nev].copy(), X, info
 

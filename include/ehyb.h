@@ -287,6 +287,21 @@ void ehyb_vector_reorder(int dimension, const double* v_in, double* v_rodr, cons
 /* v[i] = v_rodr[list[i]]     (reordering.c:386-391) */
 void ehyb_vector_recover(int dimension, const double* v_rodr, double* v, const int* list);
 
+/*
+ * A second matrix on the partitions of the first (host only).  a has been through ehyb_matrix_reorder; b has the same dimension
+ * and is row-grouped in a's ORIGINAL numbering (a mass matrix on the mesh of a stiffness matrix, say).  b receives the symmetric
+ * permutation new = a->reorderList[old] -- the convention of ehyb_vector_reorder --: its rows are grouped, the entries of a row
+ * stand in rising new column order (equal columns keep their stored order, so the result is deterministic), I/J/V are replaced
+ * (the old arrays freed with free()), rowIdx/numInRow/numInRow2/maxCol are refilled, and b takes a's nParts, vectorCacheSize and
+ * kernelPerPart and copies of its partBoundary and reorderList into its own arrays (caller-allocated as for ehyb_matrix_reorder:
+ * >= a->nParts + 1 and >= dimension ints).  ehyb_plan_create_host(b, ...) then builds a plan that walks a's partitions, as the
+ * plan of an FSAI factor does.  Build it with cfg.sym_pairs off (2) unless b's rows are known to fit the windows sized for a:
+ * the partitions were cut for a's pattern, not for b's.
+ * EHYB_ERR_ARG: a null pointer, an incomplete b, different dimensions, a without partition data (nParts < 1, no partBoundary
+ * spanning the rows, no reorderList, or one that is no permutation), a column of b outside the matrix.
+ */
+int ehyb_matrix_reorder_like(matrixCOO* b, const matrixCOO* a);
+
 /* Cuts a reordered matrix into n_top runs of whole partitions with (nearly) equal entry counts:
  * part_of_block[b] = first partition of run b, n_top+1 entries.  A pure function of m (for matrices
  * whose two-level block boundaries were not kept; ehyb_matrix_reorder_blocks returns the real ones). */
@@ -1585,7 +1600,7 @@ int ehyb_eigsh_rotate_step(int n, int64_t ld_src, const double* src_dev, int64_t
  * or NaN tol, a negative or non-finite anorm; a plan not over all rows; nb > n; an odd ldv (ldx0) or one below n with a non-NULL
  * evecs_dev (X0_dev); a misaligned evecs_dev, inv_diag_dev or X0_dev; a coarse object with another number of rows.  Then
  * EHYB_ERR_STATE on a plan, then a coarse object, that was never uploaded.
- * Out of scope: the largest end, a mass matrix or scaling, hard locking, nev > 8, several GPUs.
+ * Out of scope: the largest end, hard locking, nev > 8, several GPUs.  A mass matrix (K x = lambda M x) is ehyb_lobpcg_gen below.
  *
  * ehyb_lobpcg_rr (host only, no device, deterministic): the Rayleigh-Ritz step for the pencil (H, G), both mc x mc (1 .. 24),
  * column-major with leading dimension mc, only the upper triangles i <= j read; 1 <= nb <= min(8, mc).
@@ -1621,6 +1636,54 @@ int ehyb_lobpcg_gram_step(int n, int64_t ld, const double* S_dev, const double* 
 int ehyb_lobpcg_resid_step(int n, int64_t ld, const double* X_dev, const double* AX_dev, int nb, const double* theta_dev,
                            const double* inv_diag_dev, unsigned int active_mask, int64_t ldw, double* W_dev, double* res2_dev,
                            double* scratch_dev, void* stream);
+
+/*
+ * The nev SMALLEST eigenpairs of the pencil K x = lambda M x: `plan` holds the symmetric K, M is symmetric positive definite and
+ * given in exactly one of two forms:
+ *   mass_plan      a consistent mass: an uploaded plan over all rows of a matrix with the same n in the same numbering (build
+ *                  it from ehyb_matrix_reorder_like(M, K));
+ *   mass_diag_dev  a lumped mass: n doubles on the device, 16-byte aligned, M = diag(mass_diag_dev).
+ * The rules are ehyb_lobpcg's, with these changes and no others.
+ *   Third image.  Beside S and AS the solve keeps BS = M S.  With a mass plan BS is stored: BX is one ehyb_spmm on the mass plan
+ *     at the start, BW one ehyb_spmm of na columns per iteration (passes of the mass plan's own ehyb_spmm_max_k, the walk
+ *     direction alternating from multiply to multiply as for K), [BX | BP] = BS [Y | Yp] a third launch of the rotation kernel.
+ *     With a lumped mass BS is never stored: every kernel forms m o s (one rounding) where it reads s.
+ *   Allocation.  With a mass plan 18 nb vectors of ld doubles, with a lumped mass 12 nb; nb more with a coarse object in either
+ *     case; 2.3 MB of partial sums.
+ *   Gram matrices.  G = S^T BS and H = S^T AS, upper triangles computed and mirrored, handed to the unchanged ehyb_lobpcg_rr: the
+ *     Ritz vectors come out M-orthonormal, X^T M X = I.
+ *   Residual.  R_i = AX_i - theta_i BX_i, res_i = ||R_i||_2 (the plain 2-norm).
+ *   Convergence.  Column i is converged iff res_i <= tol max(bnorm max_l |theta_l|, anorm); bnorm is the caller's scale of ||M||,
+ *     0 = 1.0.  With bnorm = 1 the rule is ehyb_lobpcg's.
+ *   Preconditioner.  It acts on R and is built from K alone: a coarse object, inv_diag_dev, or neither.
+ *   A mass that is not positive definite shows as a negative G_ii or a rank below nb in ehyb_lobpcg_rr: the breakdown of
+ *     ehyb_lobpcg with its outputs.
+ *   Counters.  *multiplies = columns multiplied by K, *mass_multiplies = columns multiplied by M (0 with a lumped mass).
+ *   Every device sum keeps a fixed order: with plain storage of both plans every output is the same bits from run to run, on a
+ *     given or a private stream.  With mass_diag_dev all 1.0 and bnorm = 1 every output is ehyb_lobpcg's, bit for bit.
+ * EHYB_ERR_ARG in ehyb_lobpcg's order (a negative or non-finite bnorm beside anorm), with these after "a plan not over all rows":
+ * both or neither of mass_plan and mass_diag_dev; a mass plan not over all rows or of another n; a misaligned mass_diag_dev.
+ * Then EHYB_ERR_STATE on a plan, then a mass plan, then a coarse object, that was never uploaded.
+ *
+ * Its two kernels, one call each with the fixed-order second launch and the argument checks of ehyb_lobpcg_gram_step and
+ * ehyb_lobpcg_resid_step; exactly one of BS_dev (BX_dev) and mass_diag_dev is given, else EHYB_ERR_ARG.
+ *   gram_b   G = S^T BS and H = S^T AS with BS_dev, or BS = mass_diag o S formed on the way into the tile.  One pass: every
+ *            column of S, AS and (if stored) BS is read once; scratch_dev as ehyb_lobpcg_gram_step
+ *            (EHYB_LOBPCG_SCRATCH_DOUBLES).  Rows per lane, tile order, shuffle tree and grid are ehyb_lobpcg_gram_step's: with
+ *            BS_dev equal to S_dev bit for bit, G and H are that call's bits.
+ *   resid_b  R_c = AX_c - theta_c BX_c with BX_dev, or BX = mass_diag o X; everything else as ehyb_lobpcg_resid_step, whose
+ *            bits come out with BX_dev equal to X_dev or a mass_diag of 1.0.
+ */
+int ehyb_lobpcg_gen(ehyb_plan* plan, ehyb_plan* mass_plan, const double* mass_diag_dev, ehyb_coarse* coarse,
+                    const double* inv_diag_dev, const double* X0_dev, int64_t ldx0, int nev, int block, int max_iter, double tol,
+                    double anorm, double bnorm, double* evals, double* evecs_dev, int64_t ldv, void* stream, int* nconv,
+                    int* iters_done, int* multiplies, int* mass_multiplies, double* resid);
+int ehyb_lobpcg_gram_b_step(int n, int64_t ld, const double* S_dev, const double* AS_dev, const double* BS_dev,
+                            const double* mass_diag_dev, int mc, double* G_dev, double* H_dev, double* scratch_dev, void* stream);
+int ehyb_lobpcg_resid_b_step(int n, int64_t ld, const double* X_dev, const double* AX_dev, const double* BX_dev,
+                             const double* mass_diag_dev, int nb, const double* theta_dev, const double* inv_diag_dev,
+                             unsigned int active_mask, int64_t ldw, double* W_dev, double* res2_dev, double* scratch_dev,
+                             void* stream);
 
 /* -------------------------------------------- harness pieces (solver_test.c) */
 

@@ -19,7 +19,16 @@ End to end.  nev = 4 to tol 1e-8 with the two-level preconditioner against Plan.
 multiplied), iterations or restarts, the wall time around the call (best of --rounds; it includes staging the vectors through the
 host), the true residual of every pair recomputed on the CPU.
 
-usage: python tools/lobpcg_time.py [--workload audikw_1-like] [--shift 1e-2] [--sym 0] [--rounds 3] [--iters 20] [--out FILE]
+--mass lumped, --mass consistent (or both words): ehyb_lobpcg_gen beside ehyb_lobpcg IN THE SAME RUN, on the same four-wide plan.  The
+mass matrix has the bench matrix's pattern: m_ij = |k_ij| / s off the diagonal, m_ii = (2 sum_j |k_ij| + 0.01 s) / s with s the mean
+off-diagonal row sum -- positive, strictly diagonally dominant, of order one --, put on K's partitions by Matrix.reorder_like with a
+four-wide plan of its own; the lumped mass is its row sums.  Per form: the Gram kernel alone (ehyb_lobpcg_gram_b_step at mc = 12,
+its bytes and TB/s), the microseconds of an iteration of a solve (as above), and nev = 4 to 1e-8 with the two-level preconditioner
+(iterations, multiplies, wall ms, the true residual ||K x - theta M x|| recomputed on the CPU).  With a mass the lines go to
+profiles/lobpcg_gen_time_audikw.jsonl.
+
+usage: python tools/lobpcg_time.py [--workload audikw_1-like] [--shift 1e-2] [--sym 0] [--rounds 3] [--iters 20]
+                                   [--mass {none,lumped,consistent} ...] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -47,8 +56,13 @@ def main():
     ap.add_argument("--sym", type=int, default=0, help="cfg.sym_pairs of the plan")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lobpcg_time_audikw.jsonl"))
+    ap.add_argument("--mass", nargs="+", choices=["none", "lumped", "consistent"], default=["none"],
+                    help="also time ehyb_lobpcg_gen with this form of mass matrix (both forms may be named)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    forms = [f for f in ("lumped", "consistent") if f in args.mass]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "lobpcg_gen_time_audikw.jsonl" if forms else "lobpcg_time_audikw.jsonl")
     import scipy.sparse as sp
 
     import bench as B
@@ -84,8 +98,23 @@ def main():
     V[I != J] = -np.abs(V[I != J])
     off = np.bincount(I, weights=np.abs(V) * (I != J), minlength=m.n)
     V[I == J] = (off + args.shift * off.mean())[I[I == J]]
+    mass_plan = lumped = Mp = None
+    if forms:                                                    # the mass matrix in the original numbering, on K's pattern
+        scale = off.mean()
+        Vm = np.abs(V) / scale
+        Vm[I == J] = ((2.0 * off + 0.01 * scale) / scale)[I[I == J]]
+        rp0, J0 = m.row_idx.astype(np.int64), m.J.copy()
+        lumped0 = np.bincount(I, weights=Vm, minlength=m.n)
     m.reorder(cfg)
     n = m.n
+    if forms:
+        mm = E.Matrix.from_csr(rp0, J0, Vm, cfg).reorder_like(m)
+        del rp0, J0, Vm
+        lumped = E.vector_reorder(lumped0, m.reorder_list)
+        if "consistent" in forms:
+            Mp = sp.csr_matrix((mm.V.copy(), mm.J.copy(), mm.row_idx.astype(np.int64)), shape=(n, n))
+            mass_plan = E.Plan(mm, E.make_config(partitioner=B.partitioner_for(E, gen), sym_pairs=2, lds_doubles=LDS_MAX_DOUBLES // 4))
+        mm.free()
     A = sp.csr_matrix((m.V.copy(), m.J.copy(), m.row_idx.astype(np.int64)), shape=(n, n))      # the permuted numbering, for the CPU checks
     plan = E.Plan(m, cfg)
     coarse = E.Coarse(m)
@@ -138,20 +167,42 @@ def main():
 
     us_packed = best_us(packed)
     parts = {name: best_us(fn) for name, fn in (("multiply", multiply), ("gram", gram), ("rotation", rotation), ("residual", residual))}
+    gram_b = {}
+    for form in forms:                                           # the Gram kernel with the third image, alone
+        third = E.DeviceBuffer(ld * mc if form == "consistent" else ld)
+        if form == "consistent":
+            for c in range(mc):
+                column[:n] = rng.standard_normal(n) / np.sqrt(n)
+                ok(lib.ehyb_h2d(vp(third.ptr + 8 * ld * c), column.ctypes.data_as(vp), column.nbytes))
+        else:
+            third.upload(np.concatenate([lumped, np.zeros(ld - n)]))
+        bs, md = (vp(third.ptr), None) if form == "consistent" else (None, vp(third.ptr))
+        us = best_us(lambda: ok(lib.ehyb_lobpcg_gram_b_step(n, ld, vp(dS.ptr), vp(dAS.ptr), bs, md, mc, vp(dG.ptr), vp(dH.ptr), vp(dscr.ptr), s_)))
+        nbytes = 8 * n * (3 * mc if form == "consistent" else 2 * mc + 1)
+        gram_b[form] = dict(us_gram_b=round(us, 1), MB_gram_b=round(nbytes / 1e6, 1), gram_b_TBps=round(nbytes / us / 1e6, 3))
+        third.free()
     for b in (dS, dAS, dS2, dR, dG, dH, dY, dth, dr2, dscr, dpart, dd):
         b.free()
 
-    def solve_us(iters):
+    def mass_of(form):
+        return mass_plan if form == "consistent" else lumped
+
+    def solve_us(iters, form=None):
         best = None
         for _ in range(args.rounds):
             t0 = time.perf_counter()
-            info = plan.lobpcg(nb, coarse=coarse, inv_diag=1.0 / d, max_iter=iters, tol=0.0, vectors=False, stream=st.ptr)[2]
+            if form is None:
+                info = plan.lobpcg(nb, coarse=coarse, inv_diag=1.0 / d, max_iter=iters, tol=0.0, vectors=False, stream=st.ptr)[2]
+            else:
+                info = plan.lobpcg_gen(nb, mass_of(form), coarse=coarse, inv_diag=1.0 / d, max_iter=iters, tol=0.0, vectors=False,
+                                       stream=st.ptr)[2]
             t = (time.perf_counter() - t0) * 1e6
             best = t if best is None else min(best, t)
         assert info["iters"] == iters and info["multiplies"] == nb * (iters + 1), info
         return best
 
     per_iter = (solve_us(3 * args.iters) - solve_us(args.iters)) / (2 * args.iters)      # the start and the staging cancel
+    per_iter_gen = {form: (solve_us(3 * args.iters, form) - solve_us(args.iters, form)) / (2 * args.iters) for form in forms}
     emit(dict(workload=args.workload, kind="iteration", n=n, nb=nb, na=nb, mc=mc, spmm_max_k=plan.spmm_max_k, sym_pairs=plan.stats["sym_pairs"],
               coarse_unknowns=coarse.nc, us_multiply=round(parts["multiply"], 1), us_gram=round(parts["gram"], 1),
               us_rotation=round(parts["rotation"], 1), us_residual_with_preconditioner=round(parts["residual"], 1),
@@ -159,8 +210,15 @@ def main():
               per_iteration_from=f"the wall time of {3 * args.iters} iterations less that of {args.iters}",
               MB_gram=round(8 * n * 2 * mc / 1e6, 1), gram_GBps=round(8 * n * 2 * mc / parts["gram"] / 1e3, 1)))
 
+    for form in forms:
+        emit(dict(workload=args.workload, kind="iteration_gen", mass=form, n=n, nb=nb, na=nb, mc=mc, spmm_max_k=plan.spmm_max_k,
+                  mass_spmm_max_k=mass_plan.spmm_max_k if form == "consistent" else None,
+                  us_per_iteration_of_a_solve=round(per_iter_gen[form], 1), us_per_iteration_of_ehyb_lobpcg_same_run=round(per_iter, 1),
+                  over_ehyb_lobpcg=round(per_iter_gen[form] / per_iter, 3), us_gram_of_ehyb_lobpcg_same_run=round(parts["gram"], 1),
+                  **gram_b[form]))
+
     # ---------------------------------------------------------------- end to end
-    def solve(name, fn, count):
+    def solve(name, fn, count, Mh=None):
         wall, got = None, None
         for _ in range(args.rounds):
             t0 = time.perf_counter()
@@ -169,13 +227,19 @@ def main():
             wall = ms if wall is None else min(wall, ms)
         ev, X, info = got
         nrm = float(np.abs(ev).max()) if len(ev) else 1.0
-        true = max((float(np.linalg.norm(A @ X[i] - ev[i] * X[i])) for i in range(len(ev))), default=0.0) / nrm
+        mx = (lambda x: x) if Mh is None else (lambda x: Mh * x) if np.ndim(Mh) == 1 else (lambda x: Mh @ x)
+        true = max((float(np.linalg.norm(A @ X[i] - ev[i] * mx(X[i]))) for i in range(len(ev))), default=0.0) / nrm
         emit(dict(workload=args.workload, kind="solve", solver=name, nev=4, tol=1e-8, nconv=info["nconv"], multiplies=info["multiplies"],
                   **{count: info[count]}, wall_ms=round(wall, 2), wall_includes="staging the vectors through the host",
                   evals=[float(f"{v:.12g}") for v in ev], true_residual_over_nrm=float(f"{true:.3e}")))
 
     solve("lobpcg, two-level preconditioner", lambda: plan.lobpcg(4, coarse=coarse, inv_diag=1.0 / d, tol=1e-8, stream=st.ptr), "iters")
-    solve("eigsh SA", lambda: plan.eigsh(4, "SA", tol=1e-8, stream=st.ptr), "restarts")
+    for form in forms:
+        solve(f"lobpcg_gen, {form} mass, two-level preconditioner",
+              lambda: plan.lobpcg_gen(4, mass_of(form), coarse=coarse, inv_diag=1.0 / d, tol=1e-8, stream=st.ptr), "iters",
+              Mh=Mp if form == "consistent" else lumped)
+    if not forms:
+        solve("eigsh SA", lambda: plan.eigsh(4, "SA", tol=1e-8, stream=st.ptr), "restarts")
     if args.out:
         with open(args.out, "w") as f:
             for line in lines:
