@@ -35,6 +35,7 @@ from .host import (  # noqa: F401
     make_config,
     minres_inv_diag,
     partition_graph,
+    rigid_body_modes,
     sizing,
     spmv_gpu_ehyb,
     tune_decide,

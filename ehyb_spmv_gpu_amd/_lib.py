@@ -284,6 +284,8 @@ SIGNATURES = {
     "ehyb_coarse_restrict_step": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_coarse_solve_step": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ehyb_coarse_prolong_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_coarse_create_host_vecs": (C.c_int, [_mp, _P(C.c_int32), C.c_int, _dp, C.c_int64, C.c_int, _P(_vp)]),
+    "ehyb_coarse_create_raw_vecs": (C.c_int, [C.c_int, _P(C.c_int32), C.c_int, _P(C.c_int32), _dp, C.c_int64, C.c_int, _dp, _P(_vp)]),
     "ehyb_fsai_create_host": (C.c_int, [_mp, C.c_int, _cfgp, C.c_int, _P(_vp)]),
     "ehyb_fsai_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
     "ehyb_fsai_plans": (C.c_int, [_vp, _P(_vp), _P(_vp)]),

@@ -2,6 +2,8 @@
 // matrix, the coarse matrix E = P^T A P of the piecewise-constant prolongation P, and its dense inverse through a Cholesky
 // factorisation.  No GPU is needed here.  Every sum runs in an order that does not depend on the number of OpenMP threads:
 // threads share out independent outputs (partitions, rows of E, the entries of a column of L), never the terms of one sum.
+// Further down: the vector object (ehyb_coarse_create_host_vecs), whose P holds per aggregate an orthonormal basis of the
+// restriction of the caller's near-null-space vectors instead of a constant.
 #include <omp.h>
 
 #include <cmath>
@@ -129,18 +131,18 @@ int check_matrix(const char* who, const matrixCOO* m)
 
 }  // namespace
 
-bool ehyb::coarse_transpose(ehyb_coarse* c, int* bad_row, int* empty_unknown)
+bool ehyb::coarse_transpose(ehyb_coarse* c, int groups, int* bad_row, int* empty_unknown)
 {
     *bad_row = *empty_unknown = -1;
-    c->row_ptr.assign((size_t)c->nc + 1, 0);
+    c->row_ptr.assign((size_t)groups + 1, 0);
     for (int i = 0; i < c->n; ++i) {
-        if (c->map[i] < 0 || c->map[i] >= c->nc) {
+        if (c->map[i] < 0 || c->map[i] >= groups) {
             *bad_row = i;
             return false;
         }
         ++c->row_ptr[c->map[i] + 1];
     }
-    for (int u = 0; u < c->nc; ++u) {
+    for (int u = 0; u < groups; ++u) {
         if (c->row_ptr[u + 1] == 0) {
             *empty_unknown = u;
             return false;
@@ -211,7 +213,7 @@ extern "C" int ehyb_coarse_create_host(const matrixCOO* m, const int32_t* map, i
     c->ld = (nc + 1) & ~1;
     c->map.assign(map, map + c->n);
     int bad_row, empty;
-    if (!coarse_transpose(c.get(), &bad_row, &empty)) {
+    if (!coarse_transpose(c.get(), nc, &bad_row, &empty)) {
         if (bad_row >= 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: map[%d] = %d is outside 0 .. %d", who, bad_row, map[bad_row], nc - 1);
         EHYB_FAIL(EHYB_ERR_ARG, "%s: coarse unknown %d holds no row", who, empty);
     }
@@ -251,11 +253,165 @@ extern "C" int ehyb_coarse_create_raw(int n, const int32_t* map, int nc, const d
     c->ld = (nc + 1) & ~1;
     c->map.assign(map, map + n);
     int bad_row, empty;
-    if (!coarse_transpose(c.get(), &bad_row, &empty)) {
+    if (!coarse_transpose(c.get(), nc, &bad_row, &empty)) {
         if (bad_row >= 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: map[%d] = %d is outside 0 .. %d", who, bad_row, map[bad_row], nc - 1);
         EHYB_FAIL(EHYB_ERR_ARG, "%s: coarse unknown %d holds no row", who, empty);
     }
     c->Einv.assign(einv, einv + (size_t)nc * nc);
+    *out = c.release();
+    return EHYB_OK;
+}
+
+// ------------------------------------------------------------------ the vector object: local bases from near-null-space vectors
+namespace {
+
+// n, map = agg and its transpose over nagg aggregates; the errors of both vector constructors
+int vecs_object(const char* who, int n, const int32_t* agg, int nagg, int nv, std::unique_ptr<ehyb_coarse>* out)
+{
+    if (nv < 1 || nv > EHYB_COARSE_MAX_VECS) EHYB_FAIL(EHYB_ERR_ARG, "%s: %d vectors (1 .. %d)", who, nv, EHYB_COARSE_MAX_VECS);
+    if (nagg < 1) EHYB_FAIL(EHYB_ERR_ARG, "%s: %d aggregates (at least 1)", who, nagg);
+    std::unique_ptr<ehyb_coarse> c(new (std::nothrow) ehyb_coarse);
+    if (!c) EHYB_FAIL(EHYB_ERR_ALLOC, "%s: out of memory", who);
+    c->n = n;
+    c->nv = nv;
+    c->nagg = nagg;
+    c->map.assign(agg, agg + n);
+    int bad_row, empty;
+    if (!coarse_transpose(c.get(), nagg, &bad_row, &empty)) {
+        if (bad_row >= 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: agg[%d] = %d is outside 0 .. %d", who, bad_row, agg[bad_row], nagg - 1);
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: aggregate %d holds no row", who, empty);
+    }
+    *out = std::move(c);
+    return EHYB_OK;
+}
+
+int vecs_count(const char* who, ehyb_coarse* c, int64_t nc)
+{
+    if (nc < 1) EHYB_FAIL(EHYB_ERR_ARG, "%s: no column was kept in any aggregate: 0 coarse unknowns (1 .. %d)", who, EHYB_COARSE_MAX);
+    if (nc > EHYB_COARSE_MAX)
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: %lld coarse unknowns from %d aggregates and %d vectors, more than %d: fewer aggregates or vectors are needed",
+                  who, (long long)nc, c->nagg, c->nv, EHYB_COARSE_MAX);
+    c->nc = (int)nc;
+    c->ld = (c->nc + 1) & ~1;
+    return EHYB_OK;
+}
+
+// The local basis of one aggregate (rows idx[0 .. len), rising): columns 0 .. nv - 1 of B in turn, each orthogonalised against
+// the columns kept so far by modified Gram-Schmidt, two passes, and kept iff it is not zero and at least kCut of it is left.
+// Q: nv * len doubles of the caller's, the kept columns in order.  -> the number kept
+constexpr double kCut = EHYB_COARSE_VEC_CUT;
+int local_basis(const double* B, int64_t ldb, int nv, const int32_t* idx, int len, double* Q)
+{
+    int kept = 0;
+    for (int v = 0; v < nv; ++v) {
+        double* t = Q + (size_t)kept * len;
+        for (int q = 0; q < len; ++q) t[q] = B[(size_t)v * ldb + idx[q]];
+        const double norm0 = std::sqrt(dot_fixed(t, t, len));
+        if (!(norm0 > 0)) continue;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int k = 0; k < kept; ++k) {
+                const double* Qk = Q + (size_t)k * len;
+                const double h = dot_fixed(Qk, t, len);
+                for (int q = 0; q < len; ++q) t[q] -= h * Qk[q];
+            }
+        const double norm1 = std::sqrt(dot_fixed(t, t, len));
+        if (!(norm1 >= kCut * norm0)) continue;
+        for (int q = 0; q < len; ++q) t[q] /= norm1;
+        ++kept;
+    }
+    return kept;
+}
+
+}  // namespace
+
+extern "C" int ehyb_coarse_create_host_vecs(const matrixCOO* m, const int32_t* agg, int nagg, const double* B, int64_t ldb, int nv,
+                                            ehyb_coarse** out)
+{
+    const char* who = "ehyb_coarse_create_host_vecs";
+    clear_error();
+    int rc = check_matrix(who, m);
+    if (rc != EHYB_OK) return rc;
+    if (!agg || !B || !out) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
+    const int n = m->dimension;
+    if (ldb < n) EHYB_FAIL(EHYB_ERR_ARG, "%s: ldb %lld is below the %d rows", who, (long long)ldb, n);
+    std::unique_ptr<ehyb_coarse> c;
+    if ((rc = vecs_object(who, n, agg, nagg, nv, &c)) != EHYB_OK) return rc;
+    for (int v = 0; v < nv; ++v)
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(B[(size_t)v * ldb + i]))
+                EHYB_FAIL(EHYB_ERR_ARG, "%s: B holds %g in row %d of column %d", who, B[(size_t)v * ldb + i], i, v);
+
+    // the local bases: one thread per aggregate, every sum inside one thread
+    const int threads = coarse_threads();
+    const size_t N0 = (size_t)n;
+    c->W.assign((size_t)nv * N0, 0.0);
+    c->off.assign((size_t)nagg + 1, 0);
+#pragma omp parallel num_threads(threads)
+    {
+        std::vector<double> Q;
+#pragma omp for schedule(dynamic, 4)
+        for (int a = 0; a < nagg; ++a) {
+            const int begin = c->row_ptr[a], len = c->row_ptr[a + 1] - begin;
+            Q.assign((size_t)nv * len, 0.0);
+            const int kept = local_basis(B, ldb, nv, &c->rows[begin], len, Q.data());
+            c->off[a + 1] = kept;
+            for (int j = 0; j < kept; ++j)
+                for (int q = 0; q < len; ++q) c->W[j * N0 + c->rows[begin + q]] = Q[(size_t)j * len + q];
+        }
+    }
+    int64_t total = 0;
+    for (int a = 0; a < nagg; ++a) total += c->off[a + 1];
+    if ((rc = vecs_count(who, c.get(), total)) != EHYB_OK) return rc;
+    for (int a = 0; a < nagg; ++a) c->off[a + 1] += c->off[a];
+
+    // E = P^T A P.  Row (a, j) of E takes the rows i of aggregate a, rising, and their entries in stored order: the entry a_ic
+    // adds (W_j[i] a_ic) W_j'[c] to column (agg[c], j'), j' rising over the kept columns there.  One thread per aggregate.
+    const int nc = c->nc;
+    const size_t N = (size_t)nc;
+    c->E.assign(N * N, 0.0);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(threads)
+    for (int a = 0; a < nagg; ++a)
+        for (int j = 0; j < c->off[a + 1] - c->off[a]; ++j) {
+            double* Eu = &c->E[(size_t)(c->off[a] + j) * N];
+            const double* Wj = &c->W[j * N0];
+            for (int q = c->row_ptr[a]; q < c->row_ptr[a + 1]; ++q) {
+                const int i = c->rows[q];
+                for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e) {
+                    const int col = m->J[e], b = agg[col];
+                    const double wa = Wj[i] * m->V[e];
+                    for (int o = c->off[b], j2 = 0; o < c->off[b + 1]; ++o, ++j2) Eu[o] += wa * c->W[j2 * N0 + col];
+                }
+            }
+        }
+    for (int u = 0; u < nc; ++u)
+        for (int v = 0; v < u; ++v) c->E[v * N + u] = c->E[u * N + v];
+    int bad = -1;
+    double bad_value = 0.0;
+    if (!invert_spd(c->E, nc, &c->Einv, &bad, &bad_value))
+        EHYB_FAIL(EHYB_ERR_ARG, "%s: the coarse matrix is not positive definite (pivot %d of %d is %g)", who, bad, nc, bad_value);
+    *out = c.release();
+    return EHYB_OK;
+}
+
+extern "C" int ehyb_coarse_create_raw_vecs(int n, const int32_t* agg, int nagg, const int32_t* off, const double* W, int64_t ldw, int nv,
+                                           const double* einv, ehyb_coarse** out)
+{
+    const char* who = "ehyb_coarse_create_raw_vecs";
+    clear_error();
+    if (n < 0 || !agg || !off || !W || !einv || !out) EHYB_FAIL(EHYB_ERR_ARG, "%s: bad arguments", who);
+    if (ldw < n) EHYB_FAIL(EHYB_ERR_ARG, "%s: ldw %lld is below the %d rows", who, (long long)ldw, n);
+    std::unique_ptr<ehyb_coarse> c;
+    int rc = vecs_object(who, n, agg, nagg, nv, &c);
+    if (rc != EHYB_OK) return rc;
+    if (off[0] != 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: off[0] = %d, not 0", who, off[0]);
+    for (int a = 0; a < nagg; ++a)
+        if (off[a + 1] < off[a] || off[a + 1] - off[a] > nv)
+            EHYB_FAIL(EHYB_ERR_ARG, "%s: aggregate %d keeps %d columns (0 .. %d)", who, a, off[a + 1] - off[a], nv);
+    c->off.assign(off, off + nagg + 1);
+    if ((rc = vecs_count(who, c.get(), off[nagg])) != EHYB_OK) return rc;
+    c->W.resize((size_t)nv * n);
+    for (int j = 0; j < nv; ++j) std::copy(W + (size_t)j * ldw, W + (size_t)j * ldw + n, &c->W[(size_t)j * n]);
+    c->Einv.assign(einv, einv + (size_t)c->nc * c->nc);
     *out = c.release();
     return EHYB_OK;
 }
@@ -270,6 +426,14 @@ extern "C" int ehyb_coarse_host_array(const ehyb_coarse* c, int which, const voi
     case EHYB_COARSE_ROWS: *ptr = c->rows.data(), *count = (int64_t)c->rows.size(); break;
     case EHYB_COARSE_E: *ptr = c->E.data(), *count = (int64_t)c->E.size(); break;
     case EHYB_COARSE_EINV: *ptr = c->Einv.data(), *count = (int64_t)c->Einv.size(); break;
+    case EHYB_COARSE_OFF:
+    case EHYB_COARSE_W:
+        if (!c->nv) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_coarse_host_array: no array %d on an object without vectors", which);
+        if (which == EHYB_COARSE_OFF)
+            *ptr = c->off.data(), *count = (int64_t)c->off.size();
+        else
+            *ptr = c->W.data(), *count = (int64_t)c->W.size();
+        break;
     default: EHYB_FAIL(EHYB_ERR_ARG, "ehyb_coarse_host_array: no array %d", which);
     }
     return EHYB_OK;

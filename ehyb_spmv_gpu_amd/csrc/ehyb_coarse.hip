@@ -7,6 +7,8 @@
 // All three are templated on K columns per launch like the CG kernels (active flags, column offset c0; leading dimension n for
 // the vectors, nc for T and C).  Every sum runs in a fixed order -- a lane's own terms in rising order, then the shuffle tree of
 // vec_reduce.h -- with no atomics and no LDS adds, so a solve is the same bits from run to run.
+// A vector object (P of local bases from near-null-space vectors, coarse.cpp) keeps the solve kernel and has a weighted
+// restrict and a weighted prolong of its own, further down; launch_restrict and launch_prolong choose by the kind of the object.
 //
 // Loads.  E^-1 is re-read every iteration (8 nc^2 bytes, 33.5 MB at most) and wants to stay cached: plain loads.  r is read by
 // restrict and again, one kernel later, by prolong, map and ROWS are read once per iteration but again in the next: plain loads
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void coarse_restrict_kernel(int n, int nc
 
 // C[u] = sum over d of Einv[u][d] T[d].  Einv has ld = nc rounded up to even doubles per row (the pad zero), so a row starts on
 // 16 bytes: lane l reads the double2 at d = 2 l, + 128, ...  T of the live columns is staged in LDS (ld doubles per column, the
-// pad zero) once per workgroup.  K columns share the row.
+// pad zero) once per workgroup.  K columns share the row.  (A vector object's solve too: its T and C hold nc entries.)
 template <int K>
 __global__ __launch_bounds__(kThreads) void coarse_solve_kernel(int nc, int ld, const double* __restrict__ Einv, const double* __restrict__ T,
                                                                 double* __restrict__ Cv, const int* __restrict__ active, int c0)
@@ -180,12 +182,203 @@ __global__ __launch_bounds__(kThreads) void coarse_prolong_kernel(int n, int nc,
     }
 }
 
+// ------------------------------------------------------------------ the vector object (ehyb_coarse_create_host_vecs)
+// The two kernels beside restrict and prolong when P holds local bases: aggregate a owns the unknowns off[a] .. off[a + 1), one
+// per kept column j, and W[j * n + i] is row i of column j.  NV bounds the columns at compile time (nv rounded up to 1, 2, 3, 4,
+// 6 or 8), so the K * NV accumulators stay in registers; a column j >= kept is never touched -- neither its W nor its T or C.
+//
+// T[off[a] + j] = sum over q in [row_ptr[a], row_ptr[a + 1]) of W[j][rows[q]] r[rows[q]]: one wave per aggregate (workgroups of
+// any whole number of waves), lane l takes q = begin + l, + 64, ... by fma in rising q, four index loads in flight per trip; then
+// the shuffle tree.
+template <int K, int NV>
+__global__ __launch_bounds__(kThreads) void coarse_restrict_vec_kernel(int n, int nc, int nagg, const int32_t* __restrict__ row_ptr,
+                                                                       const int32_t* __restrict__ rows, const int32_t* __restrict__ off,
+                                                                       const double* __restrict__ W, const double* __restrict__ R,
+                                                                       double* __restrict__ T, const int* __restrict__ active, int c0)
+{
+    const int a = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (a >= nagg) return;  // (a whole wave)
+    const int o0 = off[a], kept = min(off[a + 1] - o0, NV);
+    if (kept <= 0) return;
+    bool on[K];
+    double acc[K][NV];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = (K == 1 && !active) || active[c0 + c] != 0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[c][j] = 0.0;
+    }
+    const int end = row_ptr[a + 1];
+    int q = row_ptr[a] + (threadIdx.x & 63);
+    for (; q + 192 < end; q += 256) {
+        int idx[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) idx[t] = rows[q + 64 * t];
+        // every load of the trip is issued before the first fma waits: a guard, not a break, so that the loads of column j + 1 do
+        // not wait behind the sums of column j (an aggregate holds thousands of rows and only nagg waves run: latency is the cost)
+        double rv[K][4], wv[NV][4];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) rv[c][t] = R[(size_t)(c0 + c) * n + idx[t]];
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (j < kept) {  // (uniform over the wave)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) wv[j][t] = W[(size_t)j * n + idx[t]];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (j < kept) {
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    if (!on[c]) continue;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) acc[c][j] = fma(wv[j][t], rv[c][t], acc[c][j]);
+                }
+            }
+        }
+    }
+    for (; q < end; q += 64) {
+        const int i = rows[q];
+        double rv[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) rv[c] = R[(size_t)(c0 + c) * n + i];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (j >= kept) break;
+            const double w = W[(size_t)j * n + i];
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+                if (on[c]) acc[c][j] = fma(w, rv[c], acc[c][j]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        if (!on[c]) continue;  // (uniform over the launch)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (j >= kept) break;
+            const double t = wave_sum(acc[c][j]);
+            if ((threadIdx.x & 63) == 0) T[(size_t)(c0 + c) * nc + o0 + j] = t;
+        }
+    }
+}
+
+// s = sum over the kept columns j of the row's aggregate of W[j][i] C[off[agg[i]] + j], by fma from 0 in rising j
+template <int NV>
+__device__ __forceinline__ double coarse_vec_term(const double (&w)[NV], const double* __restrict__ Cc, int o0, int kept)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if (j < kept) s = fma(w[j], Cc[o0 + j], s);
+    return s;
+}
+
+// z = dinv .* r + s (dinv null: r + s), s as above; rz >= 0: partials of r.z into r.z slot number rz.  The grid, the walk and the
+// tail of coarse_prolong_kernel; a row's W is loaded once for the K columns.
+template <int K, int NV>
+__global__ __launch_bounds__(kThreads) void coarse_prolong_vec_kernel(int n, int nc, const int32_t* __restrict__ agg,
+                                                                      const int32_t* __restrict__ off, const double* __restrict__ W,
+                                                                      const double* __restrict__ R, const double* __restrict__ dinv,
+                                                                      const double* __restrict__ Cv, double* __restrict__ Z,
+                                                                      double* __restrict__ s, const int* __restrict__ active, int c0, int rz)
+{
+    bool on[K];
+    double acc[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        on[c] = (K == 1 && !active) || active[c0 + c] != 0;
+        acc[c] = 0.0;
+    }
+    const int stride = (int)gridDim.x * kThreads;
+    int i = blockIdx.x * kThreads + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+        int au[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) au[u] = agg[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int iu = i + u * stride;
+            const double dv = dinv ? dinv[iu] : 1.0;
+            const int o0 = off[au[u]], kept = min(off[au[u] + 1] - o0, NV);
+            double w[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (j < kept) w[j] = W[(size_t)j * n + iu];
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                if (!on[c]) continue;
+                const size_t o = (size_t)(c0 + c) * n + iu;
+                const double rv = R[o];
+                const double cv = coarse_vec_term<NV>(w, Cv + (size_t)(c0 + c) * nc, o0, kept);
+                const double zi = dinv ? fma(rv, dv, cv) : rv + cv;
+                Z[o] = zi;
+                acc[c] = fma(rv, zi, acc[c]);
+            }
+        }
+    }
+    for (; i < n; i += stride) {
+        const double dvi = dinv ? dinv[i] : 1.0;
+        const int ai = agg[i];
+        const int o0 = off[ai], kept = min(off[ai + 1] - o0, NV);
+        double w[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (j < kept) w[j] = W[(size_t)j * n + i];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            if (!on[c]) continue;
+            const size_t o = (size_t)(c0 + c) * n + i;
+            const double ri = R[o];
+            const double ci = coarse_vec_term<NV>(w, Cv + (size_t)(c0 + c) * nc, o0, kept);
+            const double zi = dinv ? fma(ri, dvi, ci) : ri + ci;
+            Z[o] = zi;
+            acc[c] = fma(ri, zi, acc[c]);
+        }
+    }
+    if (rz < 0) return;  // (a kernel argument: the whole launch returns)
+    block_sum_n(acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            if (on[c]) slot<A_COUNT>(s, c0 + c, A_RZ0 + 2 * rz)[blockIdx.x] = acc[c];
+    }
+}
+
+// f(integral_constant<NV>) with nv rounded up to an instantiated bound
+template <typename F>
+void with_vec_bound(int nv, F&& f)
+{
+    switch (nv) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5:
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
 inline int wave_grid(int nc) { return (nc + kWaves - 1) / kWaves; }
 inline int vector_grid(int n) { return std::max(1, std::min((n + kThreads - 1) / kThreads, kMaxGrid / 2)); }
 
 template <int K>
 void launch_restrict(const ehyb_coarse* c, hipStream_t st, const double* R, double* T, const int* active, int c0)
 {
+    if (c->nv) {  // a vector object: one wave per aggregate, and one per workgroup -- a few hundred long sums, spread over every CU
+        with_vec_bound(c->nv, [&](auto NV) {
+            hipLaunchKernelGGL((coarse_restrict_vec_kernel<K, decltype(NV)::value>), dim3(c->nagg), dim3(64), 0, st, c->n, c->nc,
+                               c->nagg, c->d_row_ptr, c->d_rows, c->d_off, c->d_w, R, T, active, c0);
+        });
+        return;
+    }
     hipLaunchKernelGGL(coarse_restrict_kernel<K>, dim3(wave_grid(c->nc)), dim3(kThreads), 0, st, c->n, c->nc, c->d_row_ptr, c->d_rows, R, T,
                        active, c0);
 }
@@ -199,6 +392,13 @@ template <int K>
 void launch_prolong(const ehyb_coarse* c, int grid, hipStream_t st, const double* R, const double* dinv, const double* Cv, double* Z,
                     double* s, const int* active, int c0, int rz)
 {
+    if (c->nv) {
+        with_vec_bound(c->nv, [&](auto NV) {
+            hipLaunchKernelGGL((coarse_prolong_vec_kernel<K, decltype(NV)::value>), dim3(grid), dim3(kThreads), 0, st, c->n, c->nc, c->d_map,
+                               c->d_off, c->d_w, R, dinv, Cv, Z, s, active, c0, rz);
+        });
+        return;
+    }
     hipLaunchKernelGGL(coarse_prolong_kernel<K>, dim3(grid), dim3(kThreads), 0, st, c->n, c->nc, c->d_map, R, dinv, Cv, Z, s, active, c0, rz);
 }
 
@@ -244,10 +444,10 @@ hipError_t to_device(T** d, const T* h, size_t count)
 
 void release_device(ehyb_coarse* c)
 {
-    for (void* p : {(void*)c->d_map, (void*)c->d_row_ptr, (void*)c->d_rows, (void*)c->d_einv, (void*)c->d_scratch})
+    for (void* p : {(void*)c->d_map, (void*)c->d_row_ptr, (void*)c->d_rows, (void*)c->d_off, (void*)c->d_w, (void*)c->d_einv, (void*)c->d_scratch})
         if (p) (void)hipFree(p);
-    c->d_map = c->d_row_ptr = c->d_rows = nullptr;
-    c->d_einv = c->d_scratch = nullptr;
+    c->d_map = c->d_row_ptr = c->d_rows = c->d_off = nullptr;
+    c->d_w = c->d_einv = c->d_scratch = nullptr;
     c->uploaded = false;
 }
 
@@ -269,6 +469,8 @@ extern "C" int ehyb_coarse_upload(ehyb_coarse* c)
     hipError_t e = to_device(&c->d_map, c->map.data(), c->map.size());
     if (e == hipSuccess) e = to_device(&c->d_row_ptr, c->row_ptr.data(), c->row_ptr.size());
     if (e == hipSuccess) e = to_device(&c->d_rows, c->rows.data(), c->rows.size());
+    if (e == hipSuccess && c->nv) e = to_device(&c->d_off, c->off.data(), c->off.size());
+    if (e == hipSuccess && c->nv) e = to_device(&c->d_w, c->W.data(), c->W.size());
     if (e == hipSuccess) e = to_device(&c->d_einv, padded.data(), padded.size());
     if (e == hipSuccess) e = hipMalloc((void**)&c->d_scratch, (size_t)2 * c->nc * sizeof(double));
     if (e != hipSuccess) {

@@ -841,13 +841,41 @@ class Plan:
             pass
 
 
-COARSE_ARRAYS = {"map": (0, np.int32), "row_ptr": (1, np.int32), "rows": (2, np.int32), "E": (3, np.float64), "Einv": (4, np.float64)}
+COARSE_ARRAYS = {"map": (0, np.int32), "row_ptr": (1, np.int32), "rows": (2, np.int32), "E": (3, np.float64), "Einv": (4, np.float64),
+                 "off": (5, np.int32), "W": (6, np.float64)}
+COARSE_MAX = 2048             # EHYB_COARSE_MAX
+COARSE_MAX_VECS = 8           # EHYB_COARSE_MAX_VECS
+
+
+def rigid_body_modes(coords, dof):
+    """The near-null space of a dof-unknowns-per-node elasticity operator from the nodes' coordinates (nodes, dof), in the
+    convention of ehyb_coarse_map's dof: unknown node * dof + component, the numbering before the reorder.  dof 1: the constant;
+    dof 2: two translations and the rotation (-y, x); dof 3: three translations and the three rotations about the origin,
+    linearised (about x: (0, -z, y), about y: (z, 0, -x), about z: (-y, x, 0)).  -> (nv, nodes * dof); permute every row with
+    vector_reorder before Coarse.from_vectors."""
+    coords = np.asarray(coords, dtype=np.float64)
+    if dof == 1:
+        coords = coords.reshape(len(coords), -1)
+    assert dof in (1, 2, 3) and coords.ndim == 2 and (dof == 1 or coords.shape[1] == dof), (dof, coords.shape)
+    nodes = coords.shape[0]
+    out = np.zeros((dof + (0, 0, 1, 3)[dof], nodes, dof))
+    for c in range(dof):
+        out[c, :, c] = 1.0
+    if dof == 2:
+        out[2, :, 0], out[2, :, 1] = -coords[:, 1], coords[:, 0]
+    if dof == 3:
+        x, y, z = coords.T
+        out[3, :, 1], out[3, :, 2] = -z, y
+        out[4, :, 0], out[4, :, 2] = z, -x
+        out[5, :, 0], out[5, :, 1] = -y, x
+    return out.reshape(len(out), nodes * dof)
 
 
 class Coarse:
     """ehyb_coarse: the aggregate coarse space of Plan.cg_coarse for a reordered matrix -- the matrix the plan was built from.
     map None: ehyb_coarse_map(matrix, agg_rows, dof) (agg_rows 0: chosen from the size); otherwise the caller's (n,) map, in the
-    permuted numbering like everything here.  upload=False keeps it on the host (no GPU needed)."""
+    permuted numbering like everything here.  upload=False keeps it on the host (no GPU needed).  Coarse.from_vectors builds the
+    space from near-null-space vectors instead of constants; every solver takes either kind."""
 
     def __init__(self, matrix, agg_rows=0, dof=1, map=None, upload=True):
         self.lib = _lib.load()
@@ -881,20 +909,71 @@ class Coarse:
             self.upload()
         return self
 
+    @classmethod
+    def from_vectors(cls, matrix, B, agg_rows=0, agg=None, upload=True):
+        """ehyb_coarse_create_host_vecs: the coarse space of the local bases of B (nv, n), near-null-space vectors in the permuted
+        numbering (rigid_body_modes, eigenvectors of Plan.lobpcg ...), on the aggregates `agg` (n,).  agg None:
+        ehyb_coarse_map(matrix, agg_rows, 1); agg_rows 0: max(128, ceil(n nv / 1536)), which keeps nagg * nv below EHYB_COARSE_MAX
+        as the default of Coarse does for dof."""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.n = _lib.load(), C.c_void_p(), matrix.n
+        B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, dtype=np.float64)))
+        assert B.ndim == 2 and B.shape[1] == self.n, (B.shape, self.n)
+        self.nv = B.shape[0]
+        if agg is None:
+            if agg_rows <= 0:
+                agg_rows = max(128, -(-self.n * self.nv // 1536))
+            agg, nagg = np.empty(max(self.n, 1), dtype=np.int32), C.c_int(0)
+            _check(self.lib.ehyb_coarse_map(C.byref(matrix.c), int(agg_rows), 1, _ptr(agg, C.c_int32), C.byref(nagg)), "ehyb_coarse_map")
+            agg, nagg = agg[:self.n], nagg.value
+        else:
+            agg = np.ascontiguousarray(agg, dtype=np.int32)
+            assert agg.shape == (self.n,), (agg.shape, self.n)
+            nagg = int(agg.max()) + 1 if self.n else 0
+        _check(self.lib.ehyb_coarse_create_host_vecs(C.byref(matrix.c), _ptr(agg, C.c_int32), nagg, _ptr(B, C.c_double), max(self.n, 1), self.nv,
+                                                     C.byref(self.h)), "ehyb_coarse_create_host_vecs")
+        self.nagg = nagg
+        self.nc = int(self.array("off")[-1])
+        if upload:
+            self.upload()
+        return self
+
+    @classmethod
+    def raw_vectors(cls, n, agg, off, W, einv, upload=True):
+        """ehyb_coarse_create_raw_vecs: an object from aggregates (n,), off (nagg + 1,), W (nv, n) and a caller's E^-1 (nc, nc) --
+        for tests of the kernels."""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.n = _lib.load(), C.c_void_p(), int(n)
+        agg = np.ascontiguousarray(agg, dtype=np.int32)
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        einv = np.ascontiguousarray(einv, dtype=np.float64)
+        self.nv, self.nagg, self.nc = W.shape[0], len(off) - 1, einv.shape[0]
+        assert agg.shape == (self.n,) and W.shape == (self.nv, self.n) and einv.shape == (self.nc, self.nc) and off[-1] == self.nc
+        _check(self.lib.ehyb_coarse_create_raw_vecs(self.n, _ptr(agg, C.c_int32), self.nagg, _ptr(off, C.c_int32), _ptr(W, C.c_double),
+                                                    max(self.n, 1), self.nv, _ptr(einv, C.c_double), C.byref(self.h)), "ehyb_coarse_create_raw_vecs")
+        if upload:
+            self.upload()
+        return self
+
     def upload(self):
         _check(self.lib.ehyb_coarse_upload(self.h), "ehyb_coarse_upload")
         return self
 
     def array(self, name):
-        """ehyb_coarse_host_array: "map" (n,), "row_ptr" (nc + 1,), "rows" (n,), "E" and "Einv" (nc, nc) -- copies"""
+        """ehyb_coarse_host_array: "map" (n,), "row_ptr" (nc + 1,), "rows" (n,), "E" and "Einv" (nc, nc) -- copies.  On an object
+        of from_vectors / raw_vectors "map", "row_ptr" (nagg + 1,) and "rows" describe the aggregates, and there are "off"
+        (nagg + 1,) and "W" (nv, n); on any other object these two are empty."""
         which, dtype = COARSE_ARRAYS[name]
+        if name in ("off", "W") and not getattr(self, "nv", 0):
+            return np.zeros(0, dtype=dtype)
         p, cnt = C.c_void_p(), C.c_int64()
         _check(self.lib.ehyb_coarse_host_array(self.h, which, C.byref(p), C.byref(cnt)), "ehyb_coarse_host_array")
         if cnt.value == 0 or not p.value:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * (cnt.value * np.dtype(dtype).itemsize)).from_address(p.value)
         out = np.frombuffer(buf, dtype=dtype, count=cnt.value).copy()
-        return out.reshape(self.nc, self.nc) if name in ("E", "Einv") else out
+        return out.reshape(self.nc, self.nc) if name in ("E", "Einv") else out.reshape(self.nv, self.n) if name == "W" else out
 
     def apply(self, r, inv_diag=None, stream=0):
         """ehyb_coarse_apply: z = inv_diag .* r + P E^-1 P^T r for a host vector r (permuted numbering) -> z"""

@@ -1172,6 +1172,55 @@ int  ehyb_coarse_prolong_step(ehyb_coarse* c, const double* r_dev, const double*
 int  ehyb_coarse_create_raw(int n, const int32_t* map, int nc, const double* einv, ehyb_coarse** out);
 
 /*
+ * A coarse space from near-null-space vectors: the tentative prolongator of smoothed-aggregation AMG, not smoothed.  The
+ * piecewise-constant P above holds the translations of an elasticity operator and not its rotations; here the caller hands in
+ * n x nv vectors B (rigid-body modes, [1, x, y], eigenvectors from ehyb_lobpcg ...) and P is block diagonal over aggregates: the
+ * block of an aggregate is the locally orthonormalised restriction of B to its rows.  Everything else -- E = P^T A P, its
+ * inverse, z = D^-1 r + P E^-1 P^T r, every solver call above, ehyb_lobpcg and ehyb_lobpcg_gen -- takes such a "vector object"
+ * wherever it takes a plain one; objects of the calls above keep every array, every bit and every launch they had.
+ *
+ * ehyb_coarse_create_host_vecs: m the reordered matrix; agg[i] in [0, nagg) the aggregate of row i, every aggregate holding a
+ *   row (ehyb_coarse_map(m, agg_rows, 1, ...) is the intended map); B column-major n x nv with leading dimension ldb >= n, in
+ *   the permuted numbering, nv in 1 .. EHYB_COARSE_MAX_VECS.
+ *   The local basis.  Per aggregate, its rows rising, the columns v = 0 .. nv - 1 in turn: norm0 = the norm of the restricted
+ *   column; it is orthogonalised against the columns already kept by modified Gram-Schmidt, two passes; it is kept, and
+ *   normalised, iff norm0 > 0 and the norm afterwards is at least EHYB_COARSE_VEC_CUT norm0 = 2^-20 norm0 (a design constant:
+ *   what is left of a column below it is rounding of the columns before it rather than a direction).  Every sum is dealt to
+ *   eight running sums by its index, added pairwise; threads share out aggregates, never the terms of a sum: the same bits for
+ *   any OpenMP thread count.
+ *   Numbering.  Aggregate-major: aggregate a owns the unknowns OFF[a] .. OFF[a + 1), one per kept column, nc = OFF[nagg].  An
+ *   aggregate may keep none: its rows get the Jacobi term only.
+ *   E = P^T A P, dense: row (a, j) takes the rows i of a, rising, and their entries in stored order; the entry a_ic adds
+ *   (W_j[i] a_ic) W_j'[c] to column (agg[c], j'), j' rising.  The lower triangle is mirrored (E symmetric bit for bit) and
+ *   inverted as above.  P has orthonormal columns, so E is positive definite whenever A is.
+ *   EHYB_ERR_ARG: a null pointer, nv out of range, ldb < n, an agg entry out of range or an aggregate without a row, an entry
+ *   of B that is not finite (the message names row and column), nc < 1, nc > EHYB_COARSE_MAX (the message names nc: fewer
+ *   aggregates or vectors are needed), E not positive definite.
+ * ehyb_coarse_host_array on a vector object: MAP, ROW_PTR and ROWS describe the aggregates (MAP = agg, ROW_PTR int32[nagg + 1]),
+ *   _OFF int32[nagg + 1], _W double[nv * n]: column j of the local bases at W + j n, zero where an aggregate kept fewer than
+ *   j + 1 columns.  A plain object has neither _OFF nor _W: EHYB_ERR_ARG.
+ * ehyb_coarse_upload sends agg, OFF, ROW_PTR, ROWS, W and E^-1.  The solve kernel is the one above (T and C hold nc entries); two
+ *   kernels replace restrict and prolong, chosen inside the launches by the kind of the object:
+ *   restrict  T[OFF[a] + j] = sum over the rows i of a of W_j[i] r[i]     one wave per aggregate: a lane's terms by fma in rising
+ *                                                                        order, then the shuffle tree
+ *   prolong   z[i] = inv_diag[i] r[i] + sum_j W_j[i] C[OFF[agg[i]] + j]   by fma from 0 in rising j, over the kept columns only
+ *   No atomics, no LDS adds; nothing of T, C or W outside an aggregate's own kept range is read.  The guarantees of
+ *   ehyb_pcg_coarse carry over: with plain storage the same bits from run to run, under graph replay, on any stream, for any
+ *   check_every, and column j of ehyb_pcg_coarse_multi is the single solve of b_j.
+ *   Cost.  W is 8 n nv bytes on the device and is read twice per iteration (restrict and prolong) beside the multiply.  One wave
+ *   sums a whole aggregate: a single global aggregate (pure deflation with a handful of vectors) is correct but slow.
+ * ehyb_coarse_create_raw_vecs (for tests of the kernels): agg, OFF (OFF[0] = 0, 0 <= OFF[a + 1] - OFF[a] <= nv), W (nv columns,
+ *   leading dimension ldw >= n) and E^-1 (nc * nc, nc = OFF[nagg]) as given; its _E array is empty.
+ */
+#define EHYB_COARSE_MAX_VECS 8
+#define EHYB_COARSE_VEC_CUT 9.5367431640625e-07 /* 2^-20 */
+enum { EHYB_COARSE_OFF = 5, EHYB_COARSE_W = 6 };
+int  ehyb_coarse_create_host_vecs(const matrixCOO* m, const int32_t* agg, int nagg, const double* B, int64_t ldb, int nv,
+                                  ehyb_coarse** out);
+int  ehyb_coarse_create_raw_vecs(int n, const int32_t* agg, int nagg, const int32_t* off, const double* W, int64_t ldw, int nv,
+                                 const double* einv, ehyb_coarse** out);
+
+/*
  * PCG WITH A FACTORISED SPARSE APPROXIMATE INVERSE (FSAI): the incomplete-factorisation-class preconditioner whose apply is
  * two multiplies.  G is lower triangular on the pattern of tril(A) with G A G^T ~ I, M^-1 = G^T G, z = G^T (G r).  An incomplete
  * Cholesky factor would be applied by two triangular solves, chains of dependent levels; G and G^T are applied by the multiply
