@@ -756,29 +756,10 @@ class Plan:
         "iters", "multiplies", "resid" (nev,)}; nconv < nev means max_iter ran out.  A breakdown (a non-finite quantity, a basis
         of rank < block) raises EhybError, unless allow_breakdown: then nconv = 0 and evals, resid are NaN.  On a matrix whose
         lowest eigenvalues are well separated eigsh(nev, "SA") needs fewer multiplies."""
-        n, nev = self.n, int(nev)
-        nb = nev if int(block) == 0 else int(block)
-        ld = n + (n & 1)
-        dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
-        d0 = None
-        if X0 is not None:
-            X0 = np.ascontiguousarray(X0, dtype=np.float64)
-            assert X0.shape == (nb, n), (X0.shape, nb, n)
-            padded = np.zeros((nb, ld))
-            padded[:, :n] = X0
-            d0 = DeviceBuffer(nb * ld).upload(padded.ravel())
-        dv = DeviceBuffer(max(nev, 1) * ld).upload(np.zeros(max(nev, 1) * ld)) if vectors else None
-        evals, resid = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
-        nconv, iters, mult = C.c_int(0), C.c_int(0), C.c_int(0)
-        rc = self.lib.ehyb_lobpcg(self.h, coarse.h if coarse is not None else None, C.c_void_p(dd.ptr) if dd else None,
-                                  C.c_void_p(d0.ptr) if d0 else None, ld, nev, int(block), int(max_iter), tol, anorm, _ptr(evals, C.c_double),
-                                  C.c_void_p(dv.ptr) if dv else None, ld, C.c_void_p(stream), C.byref(nconv), C.byref(iters), C.byref(mult),
-                                  _ptr(resid, C.c_double))
-        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
-            raise EhybError(rc, "ehyb_lobpcg")
-        info = {"nconv": nconv.value, "iters": iters.value, "multiplies": mult.value, "resid": resid[:nev].copy()}
-        X = dv.download().reshape(-1, ld)[:nev, :n].copy() if dv else None
-        return evals[:nev].copy(), X, info
+        return self._lobpcg("ehyb_lobpcg", ("nconv", "iters", "multiplies"), nev, block, inv_diag, X0, vectors, allow_breakdown,
+                            lambda dd, d0, ld, evals, dv, counts, resid: self.lib.ehyb_lobpcg(
+                                self.h, coarse.h if coarse is not None else None, dd, d0, ld, int(nev), int(block), int(max_iter), tol, anorm,
+                                evals, dv, ld, C.c_void_p(stream), *counts, resid))
 
     def lobpcg_gen(self, nev, mass, block=0, coarse=None, inv_diag=None, X0=None, max_iter=500, tol=1e-8, anorm=0.0, bnorm=0.0,
                    vectors=True, allow_breakdown=False, stream=0):
@@ -787,15 +768,25 @@ class Plan:
         diagonal in the permuted numbering.  Everything else as lobpcg(), except: a column has converged when
         ||K x - theta M x|| <= tol * max(bnorm * max |theta|, anorm) with bnorm the caller's scale of ||M|| (0: 1), the vectors
         come out with X M X^T = I, and info gains "mass_multiplies" (0 for a lumped mass)."""
-        n, nev = self.n, int(nev)
-        nb = nev if int(block) == 0 else int(block)
-        ld = n + (n & 1)
         mass_plan = mass if isinstance(mass, Plan) else None
         dm = None
         if mass_plan is None:
             mass = np.ascontiguousarray(mass, dtype=np.float64)
-            assert mass.shape == (n,), (mass.shape, n)
-            dm = DeviceBuffer(n).upload(mass)
+            assert mass.shape == (self.n,), (mass.shape, self.n)
+            dm = DeviceBuffer(self.n).upload(mass)
+        return self._lobpcg("ehyb_lobpcg_gen", ("nconv", "iters", "multiplies", "mass_multiplies"), nev, block, inv_diag, X0, vectors,
+                            allow_breakdown, lambda dd, d0, ld, evals, dv, counts, resid: self.lib.ehyb_lobpcg_gen(
+                                self.h, mass_plan.h if mass_plan is not None else None, C.c_void_p(dm.ptr) if dm else None,
+                                coarse.h if coarse is not None else None, dd, d0, ld, int(nev), int(block), int(max_iter), tol, anorm, bnorm,
+                                evals, dv, ld, C.c_void_p(stream), *counts, resid))
+
+    def _lobpcg(self, who, counters, nev, block, inv_diag, X0, vectors, allow_breakdown, call):
+        """what lobpcg() and lobpcg_gen() share: inv_diag and X0 (padded to an even leading dimension) on the device, the buffer of the
+        vectors, the counters, call(inv_diag, X0, ld, evals, vectors, the counters by reference, resid) -> rc, the breakdown rule and
+        the download -> (evals, X or None, info with the counters in their order and "resid")"""
+        n, nev = self.n, int(nev)
+        nb = nev if int(block) == 0 else int(block)
+        ld = n + (n & 1)
         dd = None if inv_diag is None else DeviceBuffer(n).upload(inv_diag)
         d0 = None
         if X0 is not None:
@@ -806,16 +797,13 @@ class Plan:
             d0 = DeviceBuffer(nb * ld).upload(padded.ravel())
         dv = DeviceBuffer(max(nev, 1) * ld).upload(np.zeros(max(nev, 1) * ld)) if vectors else None
         evals, resid = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
-        nconv, iters, mult, mmult = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        rc = self.lib.ehyb_lobpcg_gen(self.h, mass_plan.h if mass_plan is not None else None, C.c_void_p(dm.ptr) if dm else None,
-                                      coarse.h if coarse is not None else None, C.c_void_p(dd.ptr) if dd else None,
-                                      C.c_void_p(d0.ptr) if d0 else None, ld, nev, int(block), int(max_iter), tol, anorm, bnorm,
-                                      _ptr(evals, C.c_double), C.c_void_p(dv.ptr) if dv else None, ld, C.c_void_p(stream), C.byref(nconv),
-                                      C.byref(iters), C.byref(mult), C.byref(mmult), _ptr(resid, C.c_double))
+        counts = {name: C.c_int(0) for name in counters}
+        rc = call(*(C.c_void_p(b.ptr) if b else None for b in (dd, d0)), ld, _ptr(evals, C.c_double), C.c_void_p(dv.ptr) if dv else None,
+                  [C.byref(c) for c in counts.values()], _ptr(resid, C.c_double))
         if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
-            raise EhybError(rc, "ehyb_lobpcg_gen")
-        info = {"nconv": nconv.value, "iters": iters.value, "multiplies": mult.value, "mass_multiplies": mmult.value,
-                "resid": resid[:nev].copy()}
+            raise EhybError(rc, who)
+        info = {name: c.value for name, c in counts.items()}
+        info["resid"] = resid[:nev].copy()
         X = dv.download().reshape(-1, ld)[:nev, :n].copy() if dv else None
         return evals[:nev].copy(), X, info
 

@@ -1714,8 +1714,9 @@ int ehyb_lobpcg_resid_step(int n, int64_t ld, const double* X_dev, const double*
  * both or neither of mass_plan and mass_diag_dev; a mass plan not over all rows or of another n; a misaligned mass_diag_dev.
  * Then EHYB_ERR_STATE on a plan, then a mass plan, then a coarse object, that was never uploaded.
  *
- * Its two kernels, one call each with the fixed-order second launch and the argument checks of ehyb_lobpcg_gram_step and
- * ehyb_lobpcg_resid_step; exactly one of BS_dev (BX_dev) and mass_diag_dev is given, else EHYB_ERR_ARG.
+ * The two kernels of ehyb_lobpcg with a mass -- each is one body, built for no mass, a stored and a lumped one --, one call each with
+ * the fixed-order second launch and the argument checks of ehyb_lobpcg_gram_step and ehyb_lobpcg_resid_step; exactly one of BS_dev
+ * (BX_dev) and mass_diag_dev is given, else EHYB_ERR_ARG.
  *   gram_b   G = S^T BS and H = S^T AS with BS_dev, or BS = mass_diag o S formed on the way into the tile.  One pass: every
  *            column of S, AS and (if stored) BS is read once; scratch_dev as ehyb_lobpcg_gram_step
  *            (EHYB_LOBPCG_SCRATCH_DOUBLES).  Rows per lane, tile order, shuffle tree and grid are ehyb_lobpcg_gram_step's: with

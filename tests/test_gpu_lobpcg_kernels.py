@@ -6,8 +6,13 @@ Guards: every device array ends in a pad of sentinels and the rows n .. ld of ev
 read into a sum shows); the inputs must come back unchanged, the pads and every column of W that the mask does not list must keep
 the sentinel.  The Gram sizes: 1, around one wave of pairs and one tile of 128 rows (63, 64, 65), several tiles
 (1000), one row past 32 tiles (4097), and 70001 > 256 workgroups x 128 rows x 2, where a workgroup walks a third tile and the last
-tile is a single row.  The column counts sit on both sides of the 8-column register groups."""
+tile is a single row.  The column counts sit on both sides of the 8-column register groups.
+
+The exact inputs cannot tell one order of summation from another, so test_the_bits_of_the_recorded_build holds all three mass forms of
+both kernels (ehyb_lobpcg_gram_b_step and ehyb_lobpcg_resid_b_step included) to golden/lobpcg_bits.npz, recorded on the device by
+golden/make_lobpcg_bits.py, on inputs whose every sum rounds."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -127,3 +132,84 @@ def test_resid_step_without_active_columns_takes_no_w(E, gpu):
                                       C.c_void_p(part.ptr), None) == 0, lib.ehyb_last_error()
     a.host["res2"][:nb] = c["res2"]
     a.expect("resid without W")
+
+
+# ------------------------------------------------------------------ the bits of the build that golden/lobpcg_bits.npz was recorded with
+BITS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lobpcg_bits.npz")
+BITS_FORMS = ["none", "stored", "lumped"]
+BITS_GRAM = [("none", 1, 1), ("none", 129, 17), ("none", 4097, 9), ("none", 70001, 24)] + \
+    [(form, n, mc) for form in BITS_FORMS[1:] for n, mc in ((129, 17), (70001, 24))]
+BITS_RESID = [(form, n, nb) for form in BITS_FORMS for n, nb in ((257, 1), (1000, 3), (2 * gc.S + 3, 8))]
+BITS_EDGE = 64                    # entries kept of either end of a column of W
+
+
+def bits_inputs(n, k):
+    """exact functions of the indices, one IEEE division each, so that every product and every sum rounds: S (X) = the start block
+    over 3, AS (AX) = its columns 24 + c over 7, BS (BX) = its columns 48 + c over 5, m = 1 + (i mod 7) / 11, inv_diag = 1 + (i mod 5) / 13,
+    theta_c = (2 c - 7) / 9"""
+    sb, i = lc.start_block(n, 48 + k), np.arange(n)
+    return {"S": sb[:k] / 3.0, "AS": sb[24:24 + k] / 7.0, "BS": sb[48:] / 5.0, "m": 1.0 + (i % 7) / 11.0, "dinv": 1.0 + (i % 5) / 13.0,
+            "theta": (2.0 * np.arange(k) - 7.0) / 9.0}
+
+
+def mass_ptrs(a, form, stored):
+    return a.ptr(stored if form == "stored" else None), a.ptr("m" if form == "lumped" else None)
+
+
+def gram_bits(E, scratch, form, n, mc):
+    """one launch -> {"G", "H"}: the int64 patterns of the mc x mc outputs"""
+    lib = E.host._lib.load()
+    c, ld = bits_inputs(n, mc), n + (n & 1)
+    a = Arrays(E).put("S", columns(c["S"], n, ld)).put("AS", columns(c["AS"], n, ld)).put("BS", columns(c["BS"], n, ld))
+    a.put("m", np.concatenate([c["m"], np.full(ld - n, SENTINEL)])).put("G", np.full(mc * mc, SENTINEL)).put("H", np.full(mc * mc, SENTINEL))
+    if form == "none":
+        rc = lib.ehyb_lobpcg_gram_step(n, ld, a.ptr("S"), a.ptr("AS"), mc, a.ptr("G"), a.ptr("H"), C.c_void_p(scratch.ptr), None)
+    else:
+        rc = lib.ehyb_lobpcg_gram_b_step(n, ld, a.ptr("S"), a.ptr("AS"), *mass_ptrs(a, form, "BS"), mc, a.ptr("G"), a.ptr("H"),
+                                         C.c_void_p(scratch.ptr), None)
+    assert rc == 0 and lib.ehyb_dev_sync() == 0, lib.ehyb_last_error()
+    return {k: a.dev[k].download()[:mc * mc].view(np.int64).copy() for k in ("G", "H")}
+
+
+def resid_bits(E, form, n, nb):
+    """one launch with inv_diag and every other column active -> {"res2", "W"}: the int64 patterns of res2 and of the first and the
+    last BITS_EDGE entries of every packed column of W"""
+    lib = E.host._lib.load()
+    c, ld = bits_inputs(n, nb), n + (n & 1)
+    mask = lc.active_mask(nb, "alternate")
+    na = bin(mask).count("1")
+    a = Arrays(E).put("X", columns(c["S"], n, ld)).put("AX", columns(c["AS"], n, ld)).put("BX", columns(c["BS"], n, ld))
+    a.put("m", np.concatenate([c["m"], np.full(ld - n, SENTINEL)])).put("theta", c["theta"]).put("dinv", c["dinv"])
+    a.put("W", np.full(na * ld, np.nan)).put("res2", np.full(8, SENTINEL))
+    part = E.DeviceBuffer(RESID_SCRATCH)
+    if form == "none":
+        rc = lib.ehyb_lobpcg_resid_step(n, ld, a.ptr("X"), a.ptr("AX"), nb, a.ptr("theta"), a.ptr("dinv"), mask, ld, a.ptr("W"), a.ptr("res2"),
+                                        C.c_void_p(part.ptr), None)
+    else:
+        rc = lib.ehyb_lobpcg_resid_b_step(n, ld, a.ptr("X"), a.ptr("AX"), *mass_ptrs(a, form, "BX"), nb, a.ptr("theta"), a.ptr("dinv"), mask, ld,
+                                          a.ptr("W"), a.ptr("res2"), C.c_void_p(part.ptr), None)
+    assert rc == 0 and lib.ehyb_dev_sync() == 0, lib.ehyb_last_error()
+    W = a.dev["W"].download()[:na * ld].reshape(na, ld)[:, :n]
+    return {"res2": a.dev["res2"].download()[:nb].view(np.int64).copy(),
+            "W": np.concatenate([W[:, :BITS_EDGE], W[:, -BITS_EDGE:]], axis=1).view(np.int64).copy()}
+
+
+def bits_cases(E, scratch):
+    """-> (key in the file, its int64 array) for every recorded case, one launch per case"""
+    for form, n, mc in BITS_GRAM:
+        for k, v in gram_bits(E, scratch, form, n, mc).items():
+            yield f"gram_{form}_{n}_{mc}_{k}", v
+    for form, n, nb in BITS_RESID:
+        for k, v in resid_bits(E, form, n, nb).items():
+            yield f"resid_{form}_{n}_{nb}_{k}", v
+
+
+def test_the_bits_of_the_recorded_build(E, gpu, scratch):
+    """G, H, res2 and both ends of every column of W, in all three mass forms, are bit for bit what the build that recorded
+    golden/lobpcg_bits.npz gave: the order of every sum -- rows per lane, tiles, shuffle tree, slots -- and every rounding stay"""
+    want = np.load(BITS_FILE)
+    seen = set()
+    for key, got in bits_cases(E, scratch):
+        assert got.dtype == np.int64 and np.array_equal(got, want[key]), (key, int((got != want[key]).sum()), got.size)
+        seen.add(key)
+    assert seen == set(want.files)
