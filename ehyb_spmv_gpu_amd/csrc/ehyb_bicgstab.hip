@@ -33,6 +33,7 @@
 
 #include "ehyb_internal.h"
 #include "solve_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -42,47 +43,19 @@ namespace {
 // set of slots starts at s + j * B_COUNT * kMaxGrid; behind the last set two ints per column: the status word and the device's
 // iteration counter.  One column is the layout of ehyb_bicgstab_layout.
 enum { B_BB = 0, B_RV = 1, B_SS = 2, B_TS = 3, B_TT = 4, B_RHO0 = 5, B_RR = 6, B_RHO1 = 7, B_COUNT = 8 };
-enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
-enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
 
-__device__ __forceinline__ bool usable_divisor(double d) { return d != 0.0 && isfinite(d); }
-// a decision every thread of the workgroup takes alike (it comes from the status words or from sums in the fixed order), as a
-// scalar: the branches on it are not divergent
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
-// on[c]: column c0 + c was running when the workgroup entered, the same in every thread (a sibling workgroup of the launch may
-// set a status).  -> any column running
-template <int K>
-__device__ __forceinline__ bool running(const int* __restrict__ flags, int c0, bool (&on)[K])
+// column col's status word and counter, for running and set_status (vec_reduce.h)
+template <class I>
+__device__ __forceinline__ auto column_flags(I* __restrict__ flags)
 {
-    __shared__ int st[K];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < K; ++c) st[c] = __atomic_load_n(&flags[(c0 + c) * F_COUNT + F_STATUS], __ATOMIC_RELAXED);
-    }
-    __syncthreads();
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        on[c] = uniform(st[c] == ST_RUNNING);
-        any = any || on[c];
-    }
-    return any;
-}
-
-__device__ __forceinline__ void set_status(int* __restrict__ flags, int col, int status)
-{
-    if (threadIdx.x == 0) __atomic_store_n(&flags[col * F_COUNT + F_STATUS], status, __ATOMIC_RELAXED);
+    return [=](int col) { return flags + col * F_COUNT; };
 }
 
 // ------------------------------------------------------------------ the vector kernels, K columns per launch
 // Columns c0 .. c0 + K - 1 of vectors with leading dimension n (B: ldb, X: ldx); K <= 4 per launch (kMultiMaxK, for_each_group
-// of solve_loop.h), K = 1 for the one-vector solve and the ehyb_bicgstab_*_step building blocks.  Every kernel walks the indices with the
-// grid and the per-thread order of the one-vector kernel and does the same arithmetic in the same order per column, so a
-// column's partials and scalars are the one-vector solve's bits.  One thread serves the K columns at one index: one inv_diag
-// load for all of them, and the loads of every column are issued before the first store.  U grid strides per trip: a thread
-// accumulates in rising index order whatever U is, so U is free per K and is chosen to keep the loads of a trip in registers.
-// A column whose status is set is skipped: its vectors and partials stay as they are.
+// of solve_loop.h), K = 1 for the one-vector solve and the ehyb_bicgstab_*_step building blocks.  The walk is vec_walk.h's, U grid
+// strides per trip, so a column's partials and scalars are the one-vector solve's bits.  A column whose status is set is
+// skipped: its vectors and partials stay as they are.
 
 // r = b - q (q = A x0), r^ = r, p^ = M^-1 r; partials of rho = r^.r, r.r, b.b.  Takes no flags: they are zero at the start.
 template <int K>
@@ -124,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void bicg_dot_kernel(int n, const double*
                                                             double* __restrict__ s, const int* __restrict__ flags, int c0)
 {
     bool on[K];
-    if (!running<K>(flags, c0, on)) return;
+    if (!running<K>(column_flags(flags), c0, on)) return;
     const double* rh[K];
     const double* v[K];
     double acc[K];
@@ -134,33 +107,13 @@ __global__ __launch_bounds__(kThreads) void bicg_dot_kernel(int n, const double*
         v[c] = V + (size_t)(c0 + c) * n;
         acc[c] = 0.0;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {  // U grid strides per trip, as ehyb_cg.hip's update kernel
-        double av[K][U], bv[K][U];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                av[c][u] = rh[c][i + u * stride];
-                bv[c][u] = v[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[c] = fma(av[c][u], bv[c][u], acc[c]);
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-#pragma unroll
-            for (int c = 0; c < K; ++c)
-                if (on[c]) acc[c] = fma(rh[c][i], v[c][i], acc[c]);
-        }
-    }
+    walk<K, U, 2>(
+        n, on, NoShared{},
+        [&](int c, int i, double(&in)[2], int) {
+            in[0] = rh[c][i];
+            in[1] = v[c][i];
+        },
+        [&](int c, int, const double(&in)[2], int) { acc[c] = fma(in[0], in[1], acc[c]); });
     block_sum_n(acc);
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -177,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* _
                                                           int c0, int cur)
 {
     bool on[K];
-    if (!running<K>(flags, c0, on)) return;
+    if (!running<K>(column_flags(flags), c0, on)) return;
     double sums[2 * K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
@@ -201,52 +154,24 @@ __global__ __launch_bounds__(kThreads) void bicg_s_kernel(int n, const double* _
         const double rho = sums[c], rv = sums[K + c];
         alpha[c] = rho / rv;
         if (on[c] && uniform(!isfinite(rho) || !usable_divisor(rv) || !isfinite(alpha[c]))) {
-            set_status(flags, c0 + c, ST_BREAKDOWN);
+            set_status(column_flags(flags), c0 + c, ST_BREAKDOWN);
             on[c] = false;
         }
         any = any || on[c];
     }
     if (!any) return;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {
-        double rv[K][U], vv[K][U], dv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                rv[c][u] = r[c][i + u * stride];
-                vv[c][u] = v[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const double si = fma(-alpha[c], vv[c][u], rv[c][u]);
-                sv[c][i + u * stride] = si;
-                sh[c][i + u * stride] = dinv ? si * dv[u] : si;
-                ss[c] = fma(si, si, ss[c]);
-            }
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-            const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c]) continue;
-                const double si = fma(-alpha[c], v[c][i], r[c][i]);
-                sv[c][i] = si;
-                sh[c][i] = dinv ? si * di : si;
-                ss[c] = fma(si, si, ss[c]);
-            }
-        }
-    }
+    walk<K, U, 2>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[2], double) {
+            in[0] = r[c][i];
+            in[1] = v[c][i];
+        },
+        [&](int c, int i, const double(&in)[2], double di) {
+            const double si = fma(-alpha[c], in[1], in[0]);
+            sv[c][i] = si;
+            sh[c][i] = dinv ? si * di : si;
+            ss[c] = fma(si, si, ss[c]);
+        });
     block_sum_n(ss);
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -261,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void bicg_dot2_kernel(int n, const double
                                                              double* __restrict__ s, const int* __restrict__ flags, int c0)
 {
     bool on[K];
-    if (!running<K>(flags, c0, on)) return;
+    if (!running<K>(column_flags(flags), c0, on)) return;
     const double* t[K];
     const double* sv[K];
     double acc[2 * K];  // t.s of the K columns, then t.t
@@ -271,39 +196,16 @@ __global__ __launch_bounds__(kThreads) void bicg_dot2_kernel(int n, const double
         sv[c] = SV + (size_t)(c0 + c) * n;
         acc[c] = acc[K + c] = 0.0;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {
-        double tv[K][U], sv4[K][U];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                tv[c][u] = t[c][i + u * stride];
-                sv4[c][u] = sv[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                acc[c] = fma(tv[c][u], sv4[c][u], acc[c]);
-                acc[K + c] = fma(tv[c][u], tv[c][u], acc[K + c]);
-            }
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c]) continue;
-                acc[c] = fma(t[c][i], sv[c][i], acc[c]);
-                acc[K + c] = fma(t[c][i], t[c][i], acc[K + c]);
-            }
-        }
-    }
+    walk<K, U, 2>(
+        n, on, NoShared{},
+        [&](int c, int i, double(&in)[2], int) {
+            in[0] = t[c][i];
+            in[1] = sv[c][i];
+        },
+        [&](int c, int, const double(&in)[2], int) {
+            acc[c] = fma(in[0], in[1], acc[c]);
+            acc[K + c] = fma(in[0], in[0], acc[K + c]);
+        });
     block_sum_n(acc);
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -326,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const doub
                                                                int* __restrict__ flags, int c0, int cur, double thr)
 {
     bool on[K];
-    if (!running<K>(flags, c0, on)) return;
+    if (!running<K>(column_flags(flags), c0, on)) return;
     constexpr int slots[6] = {B_RHO0, B_RV, B_SS, B_BB, B_TS, B_TT};  // (B_RHO0: + 2 cur)
     double sums[6 * K];
 #pragma unroll
@@ -362,7 +264,7 @@ __global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const doub
         half[c] = on[c] && uniform(sums[2 * K + c] <= thr * bb);  // s is small enough
         full[c] = on[c] && !half[c];
         if (full[c] && uniform(!usable_divisor(tt) || !isfinite(omega[c]))) {
-            set_status(flags, c0 + c, ST_BREAKDOWN);
+            set_status(column_flags(flags), c0 + c, ST_BREAKDOWN);
             full[c] = false;
         }
         any = any || full[c];
@@ -377,48 +279,24 @@ __global__ __launch_bounds__(kThreads) void bicg_update_kernel(int n, const doub
         }
     }
     if (any) {
-        int i = i0;
-        for (; i + (U - 1) * stride < n; i += U * stride) {
-            double pv[K][U], shv[K][U], sv4[K][U], tv[K][U], rhv[K][U], xv[K][U];
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!full[c]) continue;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pv[c][u] = p[c][i + u * stride];
-                    shv[c][u] = __builtin_nontemporal_load(&sh[c][i + u * stride]);  // s^, s and t are dead after this kernel, x is not
-                    sv4[c][u] = __builtin_nontemporal_load(&sv[c][i + u * stride]);  // read again before the next update: streamed
-                    tv[c][u] = __builtin_nontemporal_load(&t[c][i + u * stride]);    // past the caches, which hold the matrix's tail
-                    xv[c][u] = __builtin_nontemporal_load(&x[c][i + u * stride]);
-                    rhv[c][u] = rh[c][i + u * stride];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!full[c]) continue;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    __builtin_nontemporal_store(fma(omega[c], shv[c][u], fma(alpha[c], pv[c][u], xv[c][u])), &x[c][i + u * stride]);
-                    const double ri = fma(-omega[c], tv[c][u], sv4[c][u]);
-                    r[c][i + u * stride] = ri;
-                    rho[c] = fma(rhv[c][u], ri, rho[c]);
-                    rr[c] = fma(ri, ri, rr[c]);
-                }
-            }
-        }
-        if constexpr (U > 1) {
-            for (; i < n; i += stride) {
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    if (!full[c]) continue;
-                    x[c][i] = fma(omega[c], sh[c][i], fma(alpha[c], p[c][i], x[c][i]));
-                    const double ri = fma(-omega[c], t[c][i], sv[c][i]);
-                    r[c][i] = ri;
-                    rho[c] = fma(rh[c][i], ri, rho[c]);
-                    rr[c] = fma(ri, ri, rr[c]);
-                }
-            }
-        }
+        enum { PV, SHV, SVV, TV, XV, RHV, NV };
+        walk<K, U, NV>(
+            n, full, NoShared{},
+            [&](int c, int i, double(&in)[NV], int) {
+                in[PV] = p[c][i];
+                in[SHV] = __builtin_nontemporal_load(&sh[c][i]);  // s^, s and t are dead after this kernel, x is not
+                in[SVV] = __builtin_nontemporal_load(&sv[c][i]);  // read again before the next update: streamed
+                in[TV] = __builtin_nontemporal_load(&t[c][i]);    // past the caches, which hold the matrix's tail
+                in[XV] = __builtin_nontemporal_load(&x[c][i]);
+                in[RHV] = rh[c][i];
+            },
+            [&](int c, int i, const double(&in)[NV], int) {
+                __builtin_nontemporal_store(fma(omega[c], in[SHV], fma(alpha[c], in[PV], in[XV])), &x[c][i]);
+                const double ri = fma(-omega[c], in[TV], in[SVV]);
+                r[c][i] = ri;
+                rho[c] = fma(in[RHV], ri, rho[c]);
+                rr[c] = fma(ri, ri, rr[c]);
+            });
     }
     if (!any && !any_half) return;
     double out[2 * K];
@@ -448,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const d
                                                                   int cur, double thr)
 {
     bool on[K];
-    if (!running<K>(flags, c0, on)) return;
+    if (!running<K>(column_flags(flags), c0, on)) return;
     constexpr int slots[8] = {B_SS, B_RR, B_BB, B_RHO0, B_RHO0, B_RV, B_TS, B_TT};  // (the B_RHO0s: + 2 cur, + 2 (cur ^ 1))
     double sums[8 * K];
 #pragma unroll
@@ -473,53 +351,27 @@ __global__ __launch_bounds__(kThreads) void bicg_direction_kernel(int n, const d
         omega[c] = sums[6 * K + c] / sums[7 * K + c];
         beta[c] = (rho_new / rho) * (alpha / omega[c]);
         if (on[c] && uniform(sums[c] <= thr * bb || sums[K + c] <= thr * bb)) {
-            set_status(flags, c0 + c, ST_CONVERGED);
+            set_status(column_flags(flags), c0 + c, ST_CONVERGED);
             on[c] = false;
         }
         if (on[c] && uniform(!usable_divisor(rho) || !usable_divisor(omega[c]) || !isfinite(rho_new) || !isfinite(beta[c]))) {
-            set_status(flags, c0 + c, ST_BREAKDOWN);
+            set_status(column_flags(flags), c0 + c, ST_BREAKDOWN);
             on[c] = false;
         }
         any = any || on[c];
     }
     if (!any) return;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {
-        double pv[K][U], rv[K][U], vv[K][U], dv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                pv[c][u] = p[c][i + u * stride];
-                rv[c][u] = r[c][i + u * stride];
-                vv[c][u] = __builtin_nontemporal_load(&v[c][i + u * stride]);  // v is dead after this kernel
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const double zi = dinv ? rv[c][u] * dv[u] : rv[c][u], wi = dinv ? vv[c][u] * dv[u] : vv[c][u];
-                p[c][i + u * stride] = fma(beta[c], fma(-omega[c], wi, pv[c][u]), zi);
-            }
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-            const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c]) continue;
-                const double zi = dinv ? r[c][i] * di : r[c][i], wi = dinv ? v[c][i] * di : v[c][i];
-                p[c][i] = fma(beta[c], fma(-omega[c], wi, p[c][i]), zi);
-            }
-        }
-    }
+    walk<K, U, 3>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[3], double) {
+            in[0] = p[c][i];
+            in[1] = r[c][i];
+            in[2] = __builtin_nontemporal_load(&v[c][i]);  // v is dead after this kernel
+        },
+        [&](int c, int i, const double(&in)[3], double di) {
+            const double zi = dinv ? in[1] * di : in[1], wi = dinv ? in[2] * di : in[2];
+            p[c][i] = fma(beta[c], fma(-omega[c], wi, in[0]), zi);
+        });
 }
 
 // grid strides per trip: four wherever the loads of a trip fit the registers, fewer for the wide update and direction kernels

@@ -28,6 +28,7 @@
 #include "cg_shared.h"
 #include "ehyb_internal.h"
 #include "solve_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -60,11 +61,10 @@ __global__ __launch_bounds__(kThreads) void cg_init_kernel(int n, const double* 
 // One iteration of k independent solves on the same matrix that share every multiply (ehyb_pcg_multi) launches the three vector
 // kernels K columns wide (K <= 4 per launch, ceil(k / 4) launches each); the one-vector solve (ehyb_pcg, and the ehyb_cg_*_step
 // building blocks) launches them with K = 1.  Column j keeps its own alpha, beta and stopping test and its own set of partial
-// slots (s + j * A_COUNT * kMaxGrid; column 0's set is the one-vector layout); every kernel walks the indices with the same grid
-// and four-stride unroll and does the same arithmetic in the same order per column, so column j is ehyb_pcg(b_j) wherever the
-// multiply is (plain storage).  One thread serves the K columns at one index: the inv_diag load is shared and K times the loads
-// are in flight.  A column whose active flag is 0 (converged or broken down) is skipped: its x, r, p and partials stay as they
-// are.  A one-vector launch passes no flags (active = null: its column is live; K = 1 only, the wider kernels' code stays as it is).
+// slots (s + j * A_COUNT * kMaxGrid; column 0's set is the one-vector layout); the walk is vec_walk.h's at four strides per
+// trip, so column j is ehyb_pcg(b_j) wherever the multiply is (plain storage).  A column whose active flag is 0 (converged or
+// broken down) is skipped: its x, r, p and partials stay as they are.  A one-vector launch passes no flags (active = null: its
+// column is live; K = 1 only, the wider kernels' code stays as it is).
 
 // columns c0 .. c0 + K - 1: P, Q, R with leading dimension n, X with ldx.  pq = p . q
 template <int K>
@@ -127,52 +127,25 @@ __global__ __launch_bounds__(kThreads) void cg_multi_update_kernel(int n, const 
         r[c] = R + (size_t)(c0 + c) * n;
         x[c] = X + (size_t)(c0 + c) * ldx;
     }
-    // four grid strides per trip, the loads of every column first: sixteen (twenty with a preconditioner) loads in flight per
-    // thread and column instead of four -- a thread sees only seven elements of the bench matrix's vectors, and one load round
-    // trip per element was most of this kernel's time.  q is dead after this kernel and x is not read again before the next
-    // update: both streamed past the caches, which hold the matrix's tail.
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double pv[K][4], qv[K][4], xv[K][4], rv[K][4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                pv[c][u] = p[c][i + u * stride];
-                qv[c][u] = __builtin_nontemporal_load(&q[c][i + u * stride]);
-                xv[c][u] = __builtin_nontemporal_load(&x[c][i + u * stride]);
-                rv[c][u] = r[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                __builtin_nontemporal_store(fma(alpha[c], pv[c][u], xv[c][u]), &x[c][i + u * stride]);
-                const double ri = fma(-alpha[c], qv[c][u], rv[c][u]);
-                r[c][i + u * stride] = ri;
-                rz[c] = fma(ri, dinv ? ri * dv[u] : ri, rz[c]);
-                rr[c] = fma(ri, ri, rr[c]);
-            }
-        }
-    }
-    for (; i < n; i += stride) {
-        const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            x[c][i] = fma(alpha[c], p[c][i], x[c][i]);
-            const double ri = fma(-alpha[c], q[c][i], r[c][i]);
+    // four grid strides per trip: sixteen (twenty with a preconditioner) loads in flight per thread and column instead of
+    // four -- a thread sees only seven elements of the bench matrix's vectors, and one load round trip per element was most of
+    // this kernel's time.  q is dead after this kernel and x is not read again before the next update: both streamed past the
+    // caches, which hold the matrix's tail.
+    walk<K, kWalkU, 4>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[4], double) {
+            in[0] = p[c][i];
+            in[1] = __builtin_nontemporal_load(&q[c][i]);
+            in[2] = __builtin_nontemporal_load(&x[c][i]);
+            in[3] = r[c][i];
+        },
+        [&](int c, int i, const double(&in)[4], double di) {
+            __builtin_nontemporal_store(fma(alpha[c], in[0], in[2]), &x[c][i]);
+            const double ri = fma(-alpha[c], in[1], in[3]);
             r[c][i] = ri;
             rz[c] = fma(ri, dinv ? ri * di : ri, rz[c]);
             rr[c] = fma(ri, ri, rr[c]);
-        }
-    }
+        });
 #pragma unroll
     for (int c = 0; c < K; ++c) {
         sums[c] = rz[c];
@@ -212,34 +185,13 @@ __global__ __launch_bounds__(kThreads) void cg_multi_direction_kernel(int n, con
         r[c] = R + (size_t)(c0 + c) * n;
         p[c] = P + (size_t)(c0 + c) * n;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double pv[K][4], rv[K][4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                pv[c][u] = p[c][i + u * stride];
-                rv[c][u] = r[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) p[c][i + u * stride] = fma(beta[c], pv[c][u], dinv ? rv[c][u] * dv[u] : rv[c][u]);
-        }
-    }
-    for (; i < n; i += stride) {
-        const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c)
-            if (on[c]) p[c][i] = fma(beta[c], p[c][i], dinv ? r[c][i] * di : r[c][i]);
-    }
+    walk<K, kWalkU, 2>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[2], double) {
+            in[0] = p[c][i];
+            in[1] = r[c][i];
+        },
+        [&](int c, int i, const double(&in)[2], double di) { p[c][i] = fma(beta[c], in[0], dinv ? in[1] * di : in[1]); });
 }
 
 // the kernels of one iteration for columns c0 .. c0 + K - 1 (dot: p . q is not a by-product of the multiply)

@@ -27,6 +27,7 @@
 #include "ehyb_internal.h"
 #include "pcg_loop.h"
 #include "solve_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -45,42 +46,15 @@ __global__ __launch_bounds__(kThreads) void cheb_multi_start_kernel(int n, const
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         acc[c] = 0.0;
     }
-    // four grid strides per trip, a column's loads first, as the CG kernels walk
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
+    walk<K, kWalkU, 1>(
+        n, on, InvDiag{dinv}, [&](int c, int i, double(&in)[1], double) { in[0] = R[(size_t)(c0 + c) * n + i]; },
+        [&](int c, int i, const double(&in)[1], double dvi) {
             const size_t o = (size_t)(c0 + c) * n + i;
-            double rv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) rv[u] = R[o + u * stride];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double di = coef * (dinv ? rv[u] * dv[u] : rv[u]);
-                D[o + u * stride] = di;
-                Z[o + u * stride] = di;
-                acc[c] = fma(rv[u], di, acc[c]);
-            }
-        }
-    }
-    for (; i < n; i += stride) {
-        const double dvi = dinv ? dinv[i] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            const size_t o = (size_t)(c0 + c) * n + i;
-            const double ri = R[o];
-            const double di = coef * (dinv ? ri * dvi : ri);
+            const double di = coef * (dinv ? in[0] * dvi : in[0]);
             D[o] = di;
             Z[o] = di;
-            acc[c] = fma(ri, di, acc[c]);
-        }
-    }
+            acc[c] = fma(in[0], di, acc[c]);
+        });
     if (rz < 0) return;  // (a kernel argument: the whole launch returns)
     block_sum_n(acc);
     if (threadIdx.x == 0) {
@@ -106,53 +80,27 @@ __global__ __launch_bounds__(kThreads) void cheb_multi_step_kernel(int n, const 
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         acc[c] = 0.0;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
+    enum { WV, TV, PV, ZV, RV, NV };
+    walk<K, kWalkU, NV>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[NV], double) {
             const size_t o = (size_t)(c0 + c) * n + i;
-            double wv[4], tv[4], pv[4], zv[4], rv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                wv[u] = __builtin_nontemporal_load(&Win[o + u * stride]);
-                tv[u] = __builtin_nontemporal_load(&T[o + u * stride]);
-                pv[u] = D[o + u * stride];
-                zv[u] = Z[o + u * stride];
-                rv[u] = rz >= 0 ? R[o + u * stride] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double wi = wv[u] - tv[u];
-                const double di = fma(a, pv[u], b * (dinv ? wi * dv[u] : wi));
-                const double zi = zv[u] + di;
-                Wout[o + u * stride] = wi;
-                D[o + u * stride] = di;
-                Z[o + u * stride] = zi;
-                acc[c] = fma(rv[u], zi, acc[c]);
-            }
-        }
-    }
-    for (; i < n; i += stride) {
-        const double dvi = dinv ? dinv[i] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
+            in[WV] = __builtin_nontemporal_load(&Win[o]);
+            in[TV] = __builtin_nontemporal_load(&T[o]);
+            in[PV] = D[o];
+            in[ZV] = Z[o];
+            in[RV] = rz >= 0 ? R[o] : 0.0;
+        },
+        [&](int c, int i, const double(&in)[NV], double dvi) {
             const size_t o = (size_t)(c0 + c) * n + i;
-            const double wi = Win[o] - T[o];
-            const double di = fma(a, D[o], b * (dinv ? wi * dvi : wi));
-            const double zi = Z[o] + di;
-            const double ri = rz >= 0 ? R[o] : 0.0;
+            const double wi = in[WV] - in[TV];
+            const double di = fma(a, in[PV], b * (dinv ? wi * dvi : wi));
+            const double zi = in[ZV] + di;
             Wout[o] = wi;
             D[o] = di;
             Z[o] = zi;
-            acc[c] = fma(ri, zi, acc[c]);
-        }
-    }
+            acc[c] = fma(in[RV], zi, acc[c]);
+        });
     if (rz < 0) return;
     block_sum_n(acc);
     if (threadIdx.x == 0) {

@@ -17,6 +17,7 @@
 
 #include "coarse.h"
 #include "pcg_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -131,48 +132,21 @@ __global__ __launch_bounds__(kThreads) void coarse_prolong_kernel(int n, int nc,
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         acc[c] = 0.0;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double dv[4];
-        int mu[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-            mu[u] = map[i + u * stride];
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            const size_t o = (size_t)(c0 + c) * n + i;
-            const double* Cc = Cv + (size_t)(c0 + c) * nc;
-            double rv[4], cv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                rv[u] = R[o + u * stride];
-                cv[u] = Cc[mu[u]];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double zi = dinv ? fma(rv[u], dv[u], cv[u]) : rv[u] + cv[u];
-                Z[o + u * stride] = zi;
-                acc[c] = fma(rv[u], zi, acc[c]);
-            }
-        }
-    }
-    for (; i < n; i += stride) {
-        const double dvi = dinv ? dinv[i] : 1.0;
-        const int mi = map[i];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            const size_t o = (size_t)(c0 + c) * n + i;
-            const double ri = R[o], ci = Cv[(size_t)(c0 + c) * nc + mi];
-            const double zi = dinv ? fma(ri, dvi, ci) : ri + ci;
-            Z[o] = zi;
-            acc[c] = fma(ri, zi, acc[c]);
-        }
-    }
+    struct Row {  // what the columns share at a row: 1/diag and the aggregate
+        double dinv;
+        int agg;
+    };
+    walk<K, kWalkU, 2>(
+        n, on, [&](int i) { return Row{dinv ? dinv[i] : 1.0, map[i]}; },
+        [&](int c, int i, double(&in)[2], Row row) {
+            in[0] = R[(size_t)(c0 + c) * n + i];
+            in[1] = Cv[(size_t)(c0 + c) * nc + row.agg];
+        },
+        [&](int c, int i, const double(&in)[2], Row row) {
+            const double zi = dinv ? fma(in[0], row.dinv, in[1]) : in[0] + in[1];
+            Z[(size_t)(c0 + c) * n + i] = zi;
+            acc[c] = fma(in[0], zi, acc[c]);
+        });
     if (rz < 0) return;  // (a kernel argument: the whole launch returns)
     block_sum_n(acc);
     if (threadIdx.x == 0) {
@@ -281,7 +255,8 @@ __device__ __forceinline__ double coarse_vec_term(const double (&w)[NV], const d
 }
 
 // z = dinv .* r + s (dinv null: r + s), s as above; rz >= 0: partials of r.z into r.z slot number rz.  The grid, the walk and the
-// tail of coarse_prolong_kernel; a row's W is loaded once for the K columns.
+// tail of coarse_prolong_kernel; a row's W is loaded once for the K columns.  The loops are written out here: a trip goes stride
+// by stride, one row of W in registers at a time, where the walk of vec_walk.h would load four rows before the first store.
 template <int K, int NV>
 __global__ __launch_bounds__(kThreads) void coarse_prolong_vec_kernel(int n, int nc, const int32_t* __restrict__ agg,
                                                                       const int32_t* __restrict__ off, const double* __restrict__ W,

@@ -28,6 +28,7 @@
 
 #include "fsai.h"
 #include "pcg_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -218,28 +219,9 @@ __global__ __launch_bounds__(kThreads) void fsai_tt_kernel(int n, const double* 
         on[c] = (K == 1 && !active) || active[c0 + c] != 0;
         acc[c] = 0.0;
     }
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            const size_t o = (size_t)(c0 + c) * n + i;
-            double tv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) tv[u] = T[o + u * stride];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[c] = fma(tv[u], tv[u], acc[c]);
-        }
-    }
-    for (; i < n; i += stride) {
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-            const double ti = T[(size_t)(c0 + c) * n + i];
-            acc[c] = fma(ti, ti, acc[c]);
-        }
-    }
+    walk<K, kWalkU, 1>(
+        n, on, NoShared{}, [&](int c, int i, double(&in)[1], int) { in[0] = T[(size_t)(c0 + c) * n + i]; },
+        [&](int c, int, const double(&in)[1], int) { acc[c] = fma(in[0], in[0], acc[c]); });
     block_sum_n(acc);
     if (threadIdx.x == 0) {
 #pragma unroll

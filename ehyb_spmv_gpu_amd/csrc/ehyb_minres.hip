@@ -35,6 +35,7 @@
 
 #include "ehyb_internal.h"
 #include "solve_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -47,39 +48,12 @@ namespace {
 enum { M_BB = 0, M_ZQ = 1, M_BETA0 = 2, M_COUNT = 4 };
 enum { S_DBAR = 0, S_EPS = 1, S_PHIBAR = 2, S_CS = 3, S_SN = 4, S_BETA_OLD = 5, S_COUNT = 6 };
 enum { T_FLAGS = 2 * S_COUNT, T_COUNT = T_FLAGS + 1 };
-enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
-enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
-
-// a decision every thread of the workgroup takes alike (it comes from the status words, the state or sums in the fixed order),
-// as a scalar: the branches on it are not divergent
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
 
 __device__ __forceinline__ double* tail_of(double* tail, int col) { return tail + (size_t)col * T_COUNT; }
-__device__ __forceinline__ int* flags_of(double* tail, int col) { return (int*)(tail_of(tail, col) + T_FLAGS); }
-
-// on[c]: column c0 + c was running when the workgroup entered, the same in every thread (a sibling workgroup of the launch may
-// set a status).  -> any column running
-template <int K>
-__device__ __forceinline__ bool running(double* tail, int c0, bool (&on)[K])
+// column col's status word and counter, for running and set_status (vec_reduce.h)
+__device__ __forceinline__ auto column_flags(double* tail)
 {
-    __shared__ int st[K];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < K; ++c) st[c] = __atomic_load_n(&flags_of(tail, c0 + c)[F_STATUS], __ATOMIC_RELAXED);
-    }
-    __syncthreads();
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        on[c] = uniform(st[c] == ST_RUNNING);
-        any = any || on[c];
-    }
-    return any;
-}
-
-__device__ __forceinline__ void set_status(double* tail, int col, int status)
-{
-    if (threadIdx.x == 0) __atomic_store_n(&flags_of(tail, col)[F_STATUS], status, __ATOMIC_RELAXED);
+    return [=](int col) { return (int*)(tail_of(tail, col) + T_FLAGS); };
 }
 
 __device__ __forceinline__ bool converged(double phibar, double bb_sum, double thr)
@@ -90,11 +64,8 @@ __device__ __forceinline__ bool converged(double phibar, double bb_sum, double t
 
 // ------------------------------------------------------------------ the vector kernels, K columns per launch
 // Columns c0 .. c0 + K - 1 of vectors with leading dimension n (B: ldb, X: ldx); K <= 4 per launch (kMultiMaxK, for_each_group
-// of solve_loop.h), K = 1 for the one-vector solve and the ehyb_minres_*_step building blocks.  Every kernel walks the indices
-// with the grid and the per-thread order of the one-vector kernel and does the same arithmetic in the same order per column,
-// so a column's partials and scalars are the one-vector solve's bits.  One thread serves the K columns at one index: one
-// inv_diag load for all of them, and the loads of a trip are issued before its first store.  U grid strides per trip: a thread
-// accumulates in rising index order whatever U is.  A column whose status is set is skipped.
+// of solve_loop.h), K = 1 for the one-vector solve and the ehyb_minres_*_step building blocks.  The walk is vec_walk.h's, U grid
+// strides per trip, so a column's partials and scalars are the one-vector solve's bits.  A column whose status is set is skipped.
 
 // ra = b - q (q = A x0), z = M^-1 ra; partials of beta_1^2 = ra.z (slot M_BETA0) and of b.M^-1 b.  Takes no tail: the caller
 // plants the first state and the flags once it has read the sums.
@@ -136,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void minres_dot_kernel(int n, const doubl
                                                               double* __restrict__ s, double* tail, int c0, int cur, double thr)
 {
     bool on[K];
-    if (!running<K>(tail, c0, on)) return;
+    if (!running<K>(column_flags(tail), c0, on)) return;
     double bb[K];
 #pragma unroll
     for (int c = 0; c < K; ++c) bb[c] = on[c] ? partials_of(slot<M_COUNT>(s, c0 + c, M_BB)) : 0.0;
@@ -151,39 +122,19 @@ __global__ __launch_bounds__(kThreads) void minres_dot_kernel(int n, const doubl
         q[c] = Q + (size_t)(c0 + c) * n;
         acc[c] = 0.0;
         if (on[c] && uniform(converged(tail_of(tail, c0 + c)[cur * S_COUNT + S_PHIBAR], bb[c], thr))) {
-            set_status(tail, c0 + c, ST_CONVERGED);
+            set_status(column_flags(tail), c0 + c, ST_CONVERGED);
             on[c] = false;
         }
         any = any || on[c];
     }
     if (!any) return;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {  // U grid strides per trip, as ehyb_cg.hip's update kernel
-        double av[K][U], bv[K][U];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                av[c][u] = z[c][i + u * stride];
-                bv[c][u] = q[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[c] = fma(av[c][u], bv[c][u], acc[c]);
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-#pragma unroll
-            for (int c = 0; c < K; ++c)
-                if (on[c]) acc[c] = fma(z[c][i], q[c][i], acc[c]);
-        }
-    }
+    walk<K, U, 2>(
+        n, on, NoShared{},
+        [&](int c, int i, double(&in)[2], int) {
+            in[0] = z[c][i];
+            in[1] = q[c][i];
+        },
+        [&](int c, int, const double(&in)[2], int) { acc[c] = fma(in[0], in[1], acc[c]); });
     block_sum_n(acc);
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -201,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void minres_lanczos_kernel(int n, const d
                                                                   int cur)
 {
     bool on[K];
-    if (!running<K>(tail, c0, on)) return;
+    if (!running<K>(column_flags(tail), c0, on)) return;
     double sums[2 * K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
@@ -214,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void minres_lanczos_kernel(int n, const d
     double* rb[K];
     double* z[K];
     double beta[K], ab[K], bo[K], b2n[K];
-    bool first[K], any = false, any_first = false, any_later = false;
+    bool first[K], later[K], any = false, any_first = false, any_later = false;
 #pragma unroll
     for (int c = 0; c < K; ++c) {
         q[c] = Q + (size_t)(c0 + c) * n;
@@ -229,73 +180,43 @@ __global__ __launch_bounds__(kThreads) void minres_lanczos_kernel(int n, const d
         bo[c] = beta[c] / beta_old;
         first[c] = uniform(beta_old == 0.0);
         if (on[c] && uniform(!isfinite(zq) || !(b2 > 0) || !isfinite(b2) || !isfinite(ab[c]) || (!first[c] && !isfinite(bo[c])))) {
-            set_status(tail, c0 + c, ST_BREAKDOWN);
+            set_status(column_flags(tail), c0 + c, ST_BREAKDOWN);
             on[c] = false;
         }
+        later[c] = on[c] && !first[c];
+        first[c] = on[c] && first[c];
         any = any || on[c];
-        any_first = any_first || (on[c] && first[c]);
-        any_later = any_later || (on[c] && !first[c]);
+        any_first = any_first || first[c];
+        any_later = any_later || later[c];
     }
     if (!any) return;
-    const int stride = (int)gridDim.x * kThreads;
-    const int i0 = blockIdx.x * kThreads + threadIdx.x;
-    if (any_first) {  // the columns in their first iteration (once per solve): one plain pass
-        for (int i = i0; i < n; i += stride) {
-            const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c] || !first[c]) continue;
-                const double rn = fma(-ab[c], ra[c][i], q[c][i] / beta[c]);
-                const double zi = dinv ? rn * di : rn;
-                rb[c][i] = rn;
-                z[c][i] = zi;
-                b2n[c] = fma(rn, zi, b2n[c]);
-            }
-        }
+    // what both formulas do with the new residual rn
+    const auto put = [&](int c, int i, double rn, double di) {
+        const double zi = dinv ? rn * di : rn;
+        rb[c][i] = rn;
+        z[c][i] = zi;
+        b2n[c] = fma(rn, zi, b2n[c]);
+    };
+    if (any_first) {  // the columns in their first iteration (once per solve): one plain pass, rb is not read
+        walk<K, 1, 2>(
+            n, first, InvDiag{dinv},
+            [&](int c, int i, double(&in)[2], double) {
+                in[0] = q[c][i];
+                in[1] = ra[c][i];
+            },
+            [&](int c, int i, const double(&in)[2], double di) { put(c, i, fma(-ab[c], in[1], in[0] / beta[c]), di); });
     }
     if (any_later) {
-        int i = i0;
-        for (; i + (U - 1) * stride < n; i += U * stride) {
-            double qv[K][U], av[K][U], bv[K][U], dv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c] || first[c]) continue;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    qv[c][u] = q[c][i + u * stride];
-                    av[c][u] = ra[c][i + u * stride];
-                    bv[c][u] = rb[c][i + u * stride];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c] || first[c]) continue;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const double rn = fma(-bo[c], bv[c][u], fma(-ab[c], av[c][u], qv[c][u] / beta[c]));
-                    const double zi = dinv ? rn * dv[u] : rn;
-                    rb[c][i + u * stride] = rn;
-                    z[c][i + u * stride] = zi;
-                    b2n[c] = fma(rn, zi, b2n[c]);
-                }
-            }
-        }
-        if constexpr (U > 1) {
-            for (; i < n; i += stride) {
-                const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    if (!on[c] || first[c]) continue;
-                    const double rn = fma(-bo[c], rb[c][i], fma(-ab[c], ra[c][i], q[c][i] / beta[c]));
-                    const double zi = dinv ? rn * di : rn;
-                    rb[c][i] = rn;
-                    z[c][i] = zi;
-                    b2n[c] = fma(rn, zi, b2n[c]);
-                }
-            }
-        }
+        walk<K, U, 3>(
+            n, later, InvDiag{dinv},
+            [&](int c, int i, double(&in)[3], double) {
+                in[0] = q[c][i];
+                in[1] = ra[c][i];
+                in[2] = rb[c][i];
+            },
+            [&](int c, int i, const double(&in)[3], double di) {
+                put(c, i, fma(-bo[c], in[2], fma(-ab[c], in[1], in[0] / beta[c])), di);
+            });
     }
     block_sum_n(b2n);
     if (threadIdx.x == 0) {
@@ -316,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void minres_update_kernel(int n, const do
                                                                  double* tail, int c0, int cur)
 {
     bool on[K];
-    if (!running<K>(tail, c0, on)) return;
+    if (!running<K>(column_flags(tail), c0, on)) return;
     double sums[3 * K];
 #pragma unroll
     for (int c = 0; c < K; ++c) {
@@ -357,54 +278,26 @@ __global__ __launch_bounds__(kThreads) void minres_update_kernel(int n, const do
         next[c][S_BETA_OLD] = beta[c];
         if (on[c] && uniform(!isfinite(zq) || !(b2 > 0) || !isfinite(b2) || !isfinite(alpha) || !(b2n >= 0) || !isfinite(b2n) ||
                              !(gamma[c] > 0) || !isfinite(gamma[c]) || !isfinite(delta[c]) || !isfinite(phi[c]))) {
-            set_status(tail, c0 + c, ST_BREAKDOWN);
+            set_status(column_flags(tail), c0 + c, ST_BREAKDOWN);
             on[c] = false;
         }
         any = any || on[c];
     }
     if (!any) return;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + (U - 1) * stride < n; i += U * stride) {
-        double rv[K][U], av[K][U], bv[K][U], xv[K][U], dv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) dv[u] = dinv ? dinv[i + u * stride] : 1.0;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                rv[c][u] = ra[c][i + u * stride];
-                av[c][u] = wa[c][i + u * stride];
-                bv[c][u] = wb[c][i + u * stride];
-                xv[c][u] = x[c][i + u * stride];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            if (!on[c]) continue;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const double vi = (dinv ? rv[c][u] * dv[u] : rv[c][u]) / beta[c];
-                const double wn = fma(-delta[c], av[c][u], fma(-eps[c], bv[c][u], vi)) / gamma[c];
-                wb[c][i + u * stride] = wn;
-                x[c][i + u * stride] = fma(phi[c], wn, xv[c][u]);
-            }
-        }
-    }
-    if constexpr (U > 1) {
-        for (; i < n; i += stride) {
-            const double di = dinv ? dinv[i] : 1.0;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (!on[c]) continue;
-                const double vi = (dinv ? ra[c][i] * di : ra[c][i]) / beta[c];
-                const double wn = fma(-delta[c], wa[c][i], fma(-eps[c], wb[c][i], vi)) / gamma[c];
-                wb[c][i] = wn;
-                x[c][i] = fma(phi[c], wn, x[c][i]);
-            }
-        }
-    }
+    walk<K, U, 4>(
+        n, on, InvDiag{dinv},
+        [&](int c, int i, double(&in)[4], double) {
+            in[0] = ra[c][i];
+            in[1] = wa[c][i];
+            in[2] = wb[c][i];
+            in[3] = x[c][i];
+        },
+        [&](int c, int i, const double(&in)[4], double di) {
+            const double vi = (dinv ? in[0] * di : in[0]) / beta[c];
+            const double wn = fma(-delta[c], in[1], fma(-eps[c], in[2], vi)) / gamma[c];
+            wb[c][i] = wn;
+            x[c][i] = fma(phi[c], wn, in[3]);
+        });
     if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < K; ++c) {
@@ -412,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void minres_update_kernel(int n, const do
             double* out = tail_of(tail, c0 + c) + (cur ^ 1) * S_COUNT;
 #pragma unroll
             for (int w = 0; w < S_COUNT; ++w) out[w] = next[c][w];
-            flags_of(tail, c0 + c)[F_ITERS] += 1;
+            column_flags(tail)(c0 + c)[F_ITERS] += 1;
         }
     }
 }

@@ -3,13 +3,14 @@
 // from ehyb_pcg on the inner plan, which streams half the value bytes per multiply.  Two vector kernels of its own:
 //   refine_residual_kernel  r = b - q, partials of r.r and b.b, one per workgroup (put_partial: the fixed order of vec_reduce.h)
 //   refine_axpy_kernel      x += d
-// Both walk the vectors with four grid strides per trip, the loads first, as the CG kernels do.
+// Both walk the vectors as the CG kernels do (vec_walk.h, four grid strides per trip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "ehyb_internal.h"
 #include "solve_loop.h"
+#include "vec_walk.h"
 
 using namespace ehyb;
 
@@ -21,42 +22,33 @@ __global__ __launch_bounds__(kThreads) void refine_residual_kernel(int n, const 
                                                                    double* __restrict__ r, double* __restrict__ s)
 {
     double rr = 0.0, bb = 0.0;
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double bv[4], qv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) bv[u] = b[i + u * stride], qv[u] = q[i + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double ri = bv[u] - qv[u];
-            r[i + u * stride] = ri;
+    const bool live[1] = {true};  // one vector, always live
+    walk<1, kWalkU, 2>(
+        n, live, NoShared{},
+        [&](int, int i, double(&in)[2], int) {
+            in[0] = b[i];
+            in[1] = q[i];
+        },
+        [&](int, int i, const double(&in)[2], int) {
+            const double ri = in[0] - in[1];
+            r[i] = ri;
             rr = fma(ri, ri, rr);
-            bb = fma(bv[u], bv[u], bb);
-        }
-    }
-    for (; i < n; i += stride) {
-        const double bi = b[i], ri = bi - q[i];
-        r[i] = ri;
-        rr = fma(ri, ri, rr);
-        bb = fma(bi, bi, bb);
-    }
+            bb = fma(in[0], in[0], bb);
+        });
     put_partial(rr, s + R_RR * kMaxGrid);
     put_partial(bb, s + R_BB * kMaxGrid);
 }
 
 __global__ __launch_bounds__(kThreads) void refine_axpy_kernel(int n, const double* __restrict__ d, double* __restrict__ x)
 {
-    const int stride = (int)gridDim.x * kThreads;
-    int i = blockIdx.x * kThreads + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        double dv[4], xv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dv[u] = d[i + u * stride], xv[u] = x[i + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[i + u * stride] = xv[u] + dv[u];
-    }
-    for (; i < n; i += stride) x[i] += d[i];
+    const bool live[1] = {true};
+    walk<1, kWalkU, 2>(
+        n, live, NoShared{},
+        [&](int, int i, double(&in)[2], int) {
+            in[0] = d[i];
+            in[1] = x[i];
+        },
+        [&](int, int i, const double(&in)[2], int) { x[i] = in[1] + in[0]; });
 }
 
 }  // namespace

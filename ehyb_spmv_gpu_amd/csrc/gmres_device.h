@@ -34,10 +34,7 @@ enum {
     T_R = T_H + 2 * kCols,
     T_COUNT = T_R + kM * kM
 };
-enum { F_STATUS = 0, F_ITERS = 1, F_COUNT = 2 };
-enum { ST_RUNNING = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2 };
-
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+// (the status word's F_* and ST_* values and uniform() are vec_reduce.h's, the same for every solver)
 
 __device__ __forceinline__ double* gslot(double* s, int which) { return s + (size_t)which * kMaxGrid; }
 __device__ __forceinline__ const double* gslot(const double* s, int which) { return s + (size_t)which * kMaxGrid; }
