@@ -34,6 +34,7 @@ from .host import (  # noqa: F401
     lobpcg_rr,
     make_config,
     minres_inv_diag,
+    pad_square,
     partition_graph,
     rigid_body_modes,
     sizing,

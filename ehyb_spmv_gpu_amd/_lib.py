@@ -132,6 +132,31 @@ class MinresSlots(C.Structure):
         return {n: int(getattr(self, n)) for n in _MINRES_SLOT_NAMES}
 
 
+_LSQR_SLOT_NAMES = [
+    "slots", "slot_doubles", "slot_bb", "slot_beta0", "slot_alpha0", "tail_doubles", "state_doubles",
+    "state_rhobar", "state_phibar", "state_cs2", "state_sn2", "state_z", "state_xxnorm", "state_res2", "state_anorm2",
+    "state_rnorm", "state_arnorm", "state_xnorm", "state_bnorm",
+    "flags_at", "flag_status", "flag_iters", "flag_count", "status_running", "status_converged", "status_breakdown",
+]
+
+
+class LsqrSlots(C.Structure):
+    """ehyb_lsqr_slots (include/ehyb.h): the slot, state and flag layout behind the ehyb_lsqr_*_step building blocks"""
+    _fields_ = [(n, C.c_int32) for n in _LSQR_SLOT_NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in _LSQR_SLOT_NAMES}
+
+
+class LsqrInfo(C.Structure):
+    """ehyb_lsqr_info (include/ehyb.h): how a column of ehyb_lsqr ended"""
+    _fields_ = [("istop", C.c_int32), ("iters", C.c_int32), ("rnorm", C.c_double), ("arnorm", C.c_double), ("anorm", C.c_double),
+                ("xnorm", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _GMRES_SLOT_NAMES = [
     "slots", "slot_doubles", "slot_bb", "slot_ww", "slot_c0", "max_restart", "tail_doubles",
     "flags_at", "flag_status", "flag_iters", "flag_count",
@@ -311,6 +336,16 @@ SIGNATURES = {
     "ehyb_minres_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
     "ehyb_minres_lanczos_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_minres_update_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_lsqr": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _P(LsqrInfo)]),
+    "ehyb_lsqr_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp,
+                                  _P(LsqrInfo)]),
+    "ehyb_lsqr_layout": (C.c_int, [_P(LsqrSlots)]),
+    "ehyb_lsqr_init_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ehyb_lsqr_start_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_lsqr_wstart_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "ehyb_lsqr_ustep_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, _vp]),
+    "ehyb_lsqr_vstep_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "ehyb_lsqr_update_step": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp]),
     "ehyb_gmres": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
     "ehyb_gmres_t": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
     "ehyb_gmres_layout": (C.c_int, [_P(GmresSlots)]),

@@ -270,6 +270,19 @@ class Matrix:
         _check(self.lib.ehyb_matrix_reorder_like(C.byref(self.c), C.byref(other.c)), "ehyb_matrix_reorder_like")
         return self
 
+    def transposed_like(self, cfg=None):
+        """A^T on this matrix's permutation and partitions, for the plan_t of Plan.lsqr.  This matrix has been through reorder():
+        its entries are taken back to the original numbering, transposed, and handed to reorder_like(self), so nothing of the
+        unpermuted matrix needs to be kept.  Build the plan with symmetric pairs off: Plan(At, make_config(sym_pairs=2, ...))."""
+        lst = self.reorder_list.astype(np.int64)
+        old_of = np.empty(self.n, dtype=np.int64)
+        old_of[lst] = np.arange(self.n)
+        rows, cols, vals = old_of[self.J], old_of[self.I], self.V
+        order = np.lexsort((cols, rows))
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=self.n))])
+        t = Matrix.from_csr(indptr, cols[order], vals[order], cfg, symmetric=False)
+        return t.reorder_like(self)
+
     def reorder_dropin(self):
         """matrixReorder(m) / matrixReorder_unsym(m) exactly as the reference's driver calls them
         (solver_test.c:369-374; the C++-linkage symbols of include/reordering.h): no configuration,
@@ -704,6 +717,40 @@ class Plan:
         allow_breakdown: then a broken column holds its last good iterate."""
         return self._solve("ehyb_minres_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
+    def _lsqr(self, name, B, plan_t, X0, scalars, stream, allow_breakdown, multi):
+        n, k = self.n, 1
+        B = np.ascontiguousarray(np.atleast_2d(B) if multi else B, dtype=np.float64)
+        if multi:
+            k, nb = B.shape
+            assert nb == n, (nb, n)
+        db = DeviceBuffer(k * n).upload(B.ravel())
+        dx = DeviceBuffer(k * n).upload(np.zeros(k * n) if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).ravel())
+        info = (_lib.LsqrInfo * k)()
+        vectors = (C.c_void_p(db.ptr), n, C.c_void_p(dx.ptr), n, k) if multi else (C.c_void_p(db.ptr), C.c_void_p(dx.ptr))
+        rc = getattr(self.lib, name)(self.h, plan_t.h if plan_t is not None else None, *vectors, *scalars, C.c_void_p(stream), info)
+        if rc != 0 and not (allow_breakdown and b"breakdown" in self.lib.ehyb_last_error()):
+            raise EhybError(rc, name)
+        out = [i.as_dict() for i in info]
+        return (dx.download().reshape(k, n), out) if multi else (dx.download(), out[0])
+
+    def lsqr(self, b, plan_t=None, x0=None, damp=0.0, atol=1e-10, btol=1e-10, max_iter=1000, check_every=10, allow_breakdown=False,
+             stream=0):
+        """ehyb_lsqr: LSQR for min ||b - A x||_2 (damp > 0: + damp^2 ||x - x0||^2) on the device; a rectangular matrix goes in
+        padded square (pad_square), b padded with zeros.  plan_t: a Plan of A^T in this plan's numbering (Matrix.transposed_like),
+        this plan itself for a symmetric A, or None: every A^T multiply is spmv_t on this plan (reproducible up to the order of
+        summation only; raises EhybError, code 1, on a plan spmv_t_supported refuses).  b, x0 in the permuted numbering.
+        -> (x, info) with info = {"istop", "iters", "rnorm", "arnorm", "anorm", "xnorm"}; istop 0 = x0 already solves, 1 / 2 = the
+        stop test that held, 7 = max_iter, -1 = breakdown.  A breakdown raises EhybError, unless allow_breakdown: then x is the
+        last good iterate."""
+        return self._lsqr("ehyb_lsqr", b, plan_t, x0, (damp, atol, btol, max_iter, check_every), stream, allow_breakdown, False)
+
+    def lsqr_multi(self, B, plan_t=None, X0=None, damp=0.0, atol=1e-10, btol=1e-10, max_iter=1000, check_every=10, allow_breakdown=False,
+                   stream=0):
+        """ehyb_lsqr_multi: k independent LSQR solves that share both multiplies of every iteration; B, X0 (k, n) in the permuted
+        numbering, column j solved as lsqr(B[j]) would -- with a plan_t in plain storage bit for bit.  -> (X (k, n), list of k
+        info dicts).  A breakdown in any column raises EhybError, unless allow_breakdown."""
+        return self._lsqr("ehyb_lsqr_multi", B, plan_t, X0, (damp, atol, btol, max_iter, check_every), stream, allow_breakdown, True)
+
     def gmres(self, b, x0=None, restart=30, ortho_passes=2, max_iter=1000, rtol=1e-10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_gmres: restarted GMRES(restart) for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag
         is given -- for the systems on which bicgstab breaks down or diverges; restart 0 = 30, at most 64; ortho_passes 1 or 2
@@ -1102,6 +1149,18 @@ def minres_inv_diag(diag):
     """The positive diagonal preconditioner of Plan.minres from the matrix's diagonal: 1 / |a_ii|, and 1 where a_ii = 0."""
     d = np.abs(np.asarray(diag, dtype=np.float64))
     return np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 1.0)
+
+
+def pad_square(indptr, indices, data, shape):
+    """The m x n CSR matrix padded with empty rows or columns to max(m, n) square -> (indptr, indices, data) for Matrix.from_csr:
+    what Plan.lsqr takes for a rectangular matrix, with b padded by zeros; the padded entries of x come back as 0.0."""
+    m, n = int(shape[0]), int(shape[1])
+    indptr = np.asarray(indptr, dtype=np.int64)
+    indices = np.asarray(indices, dtype=np.int32)
+    assert indptr.shape == (m + 1,) and (indices.size == 0 or (0 <= indices.min() and indices.max() < n))
+    if m < n:
+        indptr = np.concatenate([indptr, np.full(n - m, indptr[-1], dtype=np.int64)])
+    return indptr, indices, np.asarray(data, dtype=np.float64)
 
 
 def lobpcg_rr(G, H, nb):

@@ -1443,6 +1443,115 @@ int ehyb_minres_update_step(int n, const double* ra_dev, const double* inv_diag_
                             double* x_dev, double* s_dev, int cur, void* stream);
 
 /*
+ * LSQR (Paige-Saunders) for min ||b - A x||_2 on the plan's matrix, entirely on the device: the solver for over- and
+ * under-determined, inconsistent and singular systems (the minimum-norm solution) and, with damp > 0, for the Tikhonov problem
+ * min ||b - A x||^2 + damp^2 ||x - x0||^2 -- what scipy.sparse.linalg.lsqr covers.  The plan is square: an m x n matrix is padded
+ * with empty rows or columns to max(m, n) and b with zeros; the padded entries of every vector stay +0.0 throughout, so LSQR on
+ * the padded system is LSQR on the rectangular one.  The method multiplies by A and by A^T:
+ *   plan_t == NULL  every A^T multiply is ehyb_spmv_t(plan).  What ehyb_spmv_t_supported refuses is refused here with its message,
+ *                   before any device work.  That multiply adds with atomics: results are reproducible up to the order of
+ *                   summation only.
+ *   plan_t          a plan of A^T in the numbering of `plan` (ehyb_matrix_reorder_like of the transpose of the unpermuted matrix,
+ *                   then a plan with symmetric pairs off); same number of rows, over all rows.  The multiply is ehyb_spmv_walk /
+ *                   ehyb_spmm on it, in a fixed order of summation.
+ *   plan_t == plan  the caller's statement that A is symmetric; the only way to run on symmetric pair storage.
+ * b_dev, x_dev, stream, check_every as ehyb_minres: x_dev holds the initial guess x0 on entry and the solution on return, stream
+ * NULL = a private stream, check_every <= 0 = 10 (odd values rounded up to even).  info may be NULL.
+ * Stored per column: x, the Lanczos vectors unnormalised -- U = beta u, V = alpha v, as ehyb_minres stores its residuals, so no
+ * pass scales a vector --, the direction w and one product vector t.  Start:
+ *   U = b - A x0;  beta_1^2 = U.U;  bnorm = beta_1;  t = A^T U;  V = t / beta_1;  alpha_1^2 = V.V;  w = V / alpha_1
+ *   the carried state (rhobar, phibar, cs2, sn2, z, xxnorm, res2, anorm^2) = (alpha_1, beta_1, -1, 0, 0, 0, 0, 0) and the numbers
+ *   of the stop tests (rnorm, arnorm, xnorm, bnorm) = (beta_1, alpha_1 beta_1, 0, beta_1).
+ * Per iteration, with alpha, beta of the iteration before:
+ *   t = A V;  U = t / alpha - (alpha / beta) U;  beta'^2 = U.U;  anorm^2 += alpha^2 + beta'^2 + damp^2
+ *   beta' > 0:  t = A^T U;  V = t / beta' - (beta' / alpha) V;  alpha'^2 = V.V.   beta' = 0:  alpha' = 0, V untouched
+ *   rhobar1 = hypot(rhobar, damp);  cs1 = rhobar / rhobar1;  sn1 = damp / rhobar1;  psi = sn1 phibar;  phibar = cs1 phibar
+ *   rho = hypot(rhobar1, beta');  cs = rhobar1 / rho;  sn = beta' / rho;  theta = sn alpha';  rhobar' = -cs alpha'
+ *   phi = cs phibar;  phibar' = sn phibar;  tau = sn phi
+ *   x += (phi / rho) w;   alpha' > 0:  w = V / alpha' - (theta / rho) w
+ *   delta = sn2 rho;  gbar = -cs2 rho;  rhs = phi - delta z;  zbar = rhs / gbar;  xnorm = sqrt(xxnorm + zbar^2)
+ *   gamma = hypot(gbar, theta);  cs2' = gbar / gamma;  sn2' = theta / gamma;  z' = rhs / gamma;  xxnorm' = xxnorm + z'^2
+ *   res2' = res2 + psi^2;  rnorm = sqrt(phibar'^2 + res2')  (phibar may be negative);  arnorm = alpha' |tau|
+ * Two multiplies and three vector kernels per iteration -- ustep, vstep, update --; alpha^2 and beta^2 of iterations of parity c live
+ * in slots of their own, so an even and an odd iteration differ in arguments only and are replayed from one hipGraph
+ * (cfg.graphs = 2: plain launches).  Sums are re-added from per-workgroup partials in a fixed order, no atomics; the state is
+ * carried in two copies per column, one per parity: an iteration of parity c reads copy c and workgroup 0 of its update kernel
+ * writes copy c ^ 1, so no launch reads a word that it writes.
+ * Stopping is decided on the device after every iteration, by the rules of ehyb_minres: the update kernel leaves the status alone,
+ * the ustep kernel of the next iteration makes the tests on the state copy it reads, and the host makes the same tests on what
+ * it read (at the start and at max_iter too).  In this order:
+ *   test 1  rnorm <= btol bnorm + atol anorm xnorm       (anorm = sqrt(anorm^2): the Frobenius-norm estimate of [A; damp I])
+ *   test 2  arnorm <= atol anorm rnorm
+ * istop: 0 = beta_1 = 0 or alpha_1 = 0, x0 already solves, x untouched; 1, 2 = the test that held (at the start only test 1 with
+ * btol >= 1 can hold); 7 = max_iter iterations done; -1 = breakdown.  beta' = 0 or alpha' = 0 is the lucky end, not a breakdown:
+ * the update still runs and then arnorm = 0, so test 2 holds.  There is no condition-number limit (scipy's conlim).
+ * Breakdown: a non-finite b.b, beta^2, alpha^2, rho or phi / rho, or a zero rho -- the convergence tests come first.  The kernel that
+ * meets a breakdown changes nothing and every later one returns at once: x is the last iterate whose update had finite scalars,
+ * iters the device's counter.  A breakdown returns EHYB_ERR_ARG ("breakdown" in ehyb_last_error) after every output is written; so
+ * does a NaN in b or x0, with x unchanged.  With a plan_t in plain storage x and every field of info are the same bits for every
+ * check_every, for graphs and plain launches, for a given or a private stream, and from run to run.
+ * EHYB_ERR_ARG, in this order: a null plan, b or x; max_iter < 0; a negative or NaN damp, atol or btol; a plan not over all rows; a
+ * plan_t of another dimension or not over all rows; with plan_t NULL what ehyb_spmv_t_supported refuses.  Then EHYB_ERR_STATE for
+ * a plan, then a plan_t, never uploaded -- all before any device work.
+ *
+ * ehyb_lsqr_multi: k INDEPENDENT such solves that share the multiplies: ehyb_spmm on plan and on plan_t, as wide as
+ * ehyb_spmm_max_k of each allows; with plan_t NULL the transposed side runs column by column.  The vector kernels run up to four
+ * columns wide; every column has its own slots, state copies, status word and counter, and a column whose status is set is skipped
+ * by every vector kernel while the others go on.  info: k entries or NULL.  With a plan_t in plain storage column j equals
+ * ehyb_lsqr on b_j bit for bit, but for rows the residual splits into several segments (ehyb_spmm).  If any column broke down the
+ * call returns EHYB_ERR_ARG after every output is written.  EHYB_ERR_ARG for k < 1, ldb or ldx < n, then what ehyb_lsqr rejects,
+ * in its order.
+ *
+ * The six vector kernels as building blocks, one launch each with slot_doubles / 2 workgroups on k = 1 .. 4 columns of leading
+ * dimension n.  s_dev: k sets of `slots` slots of `slot_doubles` doubles, column j's set at j * slots * slot_doubles, and behind
+ * the last set k tails of tail_doubles: in column j's tail at double state_doubles * c + state_* the state of parity c, at double
+ * flags_at the two ints of the flags (flag_status, flag_iters).  beta^2 and alpha^2 number c (0/1) live in slots slot_beta0 + c and
+ * slot_alpha0 + c; cur (0/1, masked with & 1) is the parity of the iteration.  Every step but init and start returns at once,
+ * writing nothing, when the status is not status_running on entry; a step that sets the status writes nothing else.
+ *   init     U = b - t (t = A x0); partials of U.U (slot beta0) and of b.b.  Takes no tail
+ *   start    V = t / beta_1 (t = A^T U, beta_1^2 from slot beta0); partials of V.V (slot alpha0).  A beta_1^2 that is zero or not
+ *            finite: nothing is written.  Takes no tail: the caller plants the first state and the flags
+ *   wstart   w = V / alpha_1 (slot alpha0); a zero or non-finite alpha_1^2: breakdown
+ *   ustep    the stop tests on state copy cur: converged.  Else a non-finite or non-positive alpha^2[cur] or beta^2[cur] or a
+ *            non-finite alpha / beta: breakdown.  Else U over U, partials of beta^2[cur ^ 1]
+ *   vstep    the same conditions on alpha^2[cur], a non-finite beta^2[cur ^ 1] or beta' / alpha: breakdown.  beta^2[cur ^ 1] = 0:
+ *            nothing.  Else V over V, partials of alpha^2[cur ^ 1]
+ *   update   a non-finite beta^2[cur ^ 1] or (beta' > 0) alpha^2[cur ^ 1], a zero or non-finite rho, a non-finite phi / rho or
+ *            theta / rho: breakdown.  Else x, w (alpha' > 0), state copy cur ^ 1, counter + 1
+ * EHYB_ERR_ARG for n < 0, a null pointer, k outside 1 .. 4.  All asynchronous on `stream`.
+ */
+typedef struct ehyb_lsqr_info {
+    int32_t istop;    /* 0 = x0 already solves (beta_1 = 0 or alpha_1 = 0), 1 = test 1, 2 = test 2, 7 = max_iter, -1 = breakdown */
+    int32_t iters;    /* the device's counter */
+    double  rnorm;    /* sqrt(||b - A x||^2 + damp^2 ||x - x0||^2) by the recurrence */
+    double  arnorm;   /* estimate of ||A^T r - damp^2 (x - x0)|| */
+    double  anorm;    /* Frobenius-norm estimate of [A; damp I] */
+    double  xnorm;    /* estimate of ||x - x0|| */
+} ehyb_lsqr_info;
+int ehyb_lsqr(ehyb_plan* plan, ehyb_plan* plan_t, const double* b_dev, double* x_dev, double damp, double atol, double btol,
+              int max_iter, int check_every, void* stream, ehyb_lsqr_info* info);
+int ehyb_lsqr_multi(ehyb_plan* plan, ehyb_plan* plan_t, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k,
+                    double damp, double atol, double btol, int max_iter, int check_every, void* stream, ehyb_lsqr_info* info);
+typedef struct ehyb_lsqr_slots {
+    int32_t slots, slot_doubles;
+    int32_t slot_bb, slot_beta0, slot_alpha0;
+    int32_t tail_doubles, state_doubles;
+    int32_t state_rhobar, state_phibar, state_cs2, state_sn2, state_z, state_xxnorm, state_res2, state_anorm2;
+    int32_t state_rnorm, state_arnorm, state_xnorm, state_bnorm;
+    int32_t flags_at, flag_status, flag_iters, flag_count;
+    int32_t status_running, status_converged, status_breakdown;
+} ehyb_lsqr_slots;
+int ehyb_lsqr_layout(ehyb_lsqr_slots* out);
+int ehyb_lsqr_init_step(int n, int k, const double* b_dev, const double* t_dev, double* u_dev, double* s_dev, void* stream);
+int ehyb_lsqr_start_step(int n, int k, const double* t_dev, double* v_dev, double* s_dev, void* stream);
+int ehyb_lsqr_wstart_step(int n, int k, const double* v_dev, double* w_dev, double* s_dev, void* stream);
+int ehyb_lsqr_ustep_step(int n, int k, const double* t_dev, double* u_dev, double* s_dev, int cur, double atol, double btol,
+                         void* stream);
+int ehyb_lsqr_vstep_step(int n, int k, const double* t_dev, double* v_dev, double* s_dev, int cur, void* stream);
+int ehyb_lsqr_update_step(int n, int k, const double* v_dev, double* w_dev, double* x_dev, double* s_dev, int cur, double damp,
+                          void* stream);
+
+/*
  * Restarted GMRES(restart) for a general (unsymmetric) A x = b on the plan's matrix, entirely on the device, right-preconditioned
  * with M = diag(A) -- the solver for the systems on which ehyb_bicgstab breaks down or diverges: its residual never grows, and it
  * breaks down only on a singular system.  inv_diag_dev, b_dev, x_dev, stream and the outputs as ehyb_bicgstab: inv_diag_dev NULL =
