@@ -209,6 +209,7 @@ SIGNATURES = {
     "ehyb_matrix_key": (C.c_uint64, [_mp]),
     "ehyb_plan_save": (C.c_int, [_vp, _ip, C.c_uint64, C.c_char_p]),
     "ehyb_plan_load": (C.c_int, [C.c_char_p, C.c_uint64, _P(_vp), _ip]),
+    "ehyb_plan_check": (C.c_int, [_vp]),
     "ehyb_plan_stats": (C.c_int, [_vp, _P(Stats)]),
     "ehyb_plan_resident_bytes": (C.c_int64, [_vp]),
     "ehyb_ell_slab_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -12,13 +12,7 @@
 
 using namespace ehyb;
 
-int ehyb_spmm_max_k(const ehyb_plan* P, int* k_max)
-{
-    clear_error();
-    if (!P || !k_max) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_spmm_max_k: null argument");
-    *k_max = plan_spmm_width(P);
-    return EHYB_OK;
-}
+// (ehyb_spmm_max_k is host arithmetic: plan.cpp)
 
 int ehyb_spmm(ehyb_plan* P, const double* X, int64_t ldx, double* Y, int64_t ldy, int k, void* stream, int walk)
 {

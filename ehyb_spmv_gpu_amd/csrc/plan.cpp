@@ -212,6 +212,15 @@ int ehyb_plan_device_cols(const ehyb_plan* plan, uint32_t* words_out, uint32_t* 
     return EHYB_OK;
 }
 
+// Widest pass of ehyb_spmm on the plan (the rule: include/ehyb.h; host arithmetic, no device)
+int ehyb_spmm_max_k(const ehyb_plan* P, int* k_max)
+{
+    clear_error();
+    if (!P || !k_max) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_spmm_max_k: null argument");
+    *k_max = plan_spmm_width(P);
+    return EHYB_OK;
+}
+
 // The value streams ehyb_plan_upload sends for this plan (cfg.val_f32)
 int ehyb_plan_device_value_bytes(const ehyb_plan* plan, int64_t* ell_bytes, int64_t* er_bytes)
 {

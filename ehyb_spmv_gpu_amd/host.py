@@ -421,6 +421,12 @@ class Plan:
             self.upload()
         return self, perm
 
+    def check(self):
+        """ehyb_plan_check: raises EhybError (code 6, the first array, index and rule named) if a kernel or a host routine
+        would index outside one of the plan's arrays; what ehyb_plan_load applies to a file.  Needs no device."""
+        _check(self.lib.ehyb_plan_check(self.h), "ehyb_plan_check")
+        return self
+
     @property
     def stats(self):
         st = Stats()

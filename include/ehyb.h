@@ -350,6 +350,16 @@ void ehyb_plan_destroy(ehyb_plan* plan);
 uint64_t ehyb_matrix_key(const matrixCOO* m);
 int ehyb_plan_save(const ehyb_plan* plan, const int* reorder_list, uint64_t matrix_key, const char* path);
 int ehyb_plan_load(const char* path, uint64_t expect_key, ehyb_plan** plan, int* reorder_list);
+/*
+ * The content check ehyb_plan_load applies after its size checks, callable on any plan; host arithmetic only, no device.
+ * EHYB_OK when every index a kernel or a host routine forms from the plan's arrays lies inside the array it indexes, for
+ * every entry point a plan can be given to (ehyb_spmv, _phase, _walk, _part, ehyb_spmv_t, ehyb_spmm up to ehyb_spmm_max_k,
+ * the solvers' multiplies, the transcoder of ehyb_plan_upload); else EHYB_ERR_FORMAT, and ehyb_last_error names the first
+ * array, index and rule that failed.  It is about safety, not about the product: values may hold any bits, and a column
+ * that stays inside its window cannot be told from another matrix.  The panel streams of a plan whose panel form was built
+ * on the device are on the device alone and are not looked at.
+ */
+int ehyb_plan_check(const ehyb_plan* plan);
 
 /* Format metrics; the first five are the ones the reference prints
  * (convert.c:140,310; spmv.cu:82). */
