@@ -1349,6 +1349,9 @@ int ehyb_spmv_part(ehyb_plan* P, const double* x, double* y, void* stream, int s
     (void)ehyb_plan_col_segs(P, &n_segs);
     if (seg_begin < 0 || seg_end > n_segs || seg_begin > seg_end) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_spmv_part: column segments [%d, %d) of %d", seg_begin, seg_end, n_segs);
     if (H.direct || H.inline_er) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: this plan multiplies in one launch (direct shape or inline residual): it has no parts");
+    // (every refusal in front of the first launch: a refused call enqueues nothing)
+    const bool split = P->cfg.row_split > 0;
+    if ((flags & EHYB_PART_LAST_FOREIGN) && !split) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: EHYB_PART_LAST_FOREIGN needs a plan built with cfg.row_split");
     hipStream_t st = (hipStream_t)stream;
     int rc = EHYB_OK;
     if (flags & EHYB_PART_FIRST) rc = launch_ell(P, x, y, st, false);
@@ -1361,11 +1364,7 @@ int ehyb_spmv_part(ehyb_plan* P, const double* x, double* y, void* stream, int s
     }
     // the closing pass: all row blocks, or -- with cfg.row_split -- the foreign rows first (EHYB_PART_LAST_FOREIGN, as soon as
     // segment 0's pass 1 is enqueued) and the rows in front of the split at the end
-    const bool split = P->cfg.row_split > 0;
-    if (rc == EHYB_OK && (flags & EHYB_PART_LAST_FOREIGN)) {
-        if (!split) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_spmv_part: EHYB_PART_LAST_FOREIGN needs a plan built with cfg.row_split");
-        rc = launch_panel_reduce(P, y, 0, 1, st, 0, PANEL_ROWS_FROM_SPLIT);
-    }
+    if (rc == EHYB_OK && (flags & EHYB_PART_LAST_FOREIGN)) rc = launch_panel_reduce(P, y, 0, 1, st, 0, PANEL_ROWS_FROM_SPLIT);
     if (rc == EHYB_OK && (flags & EHYB_PART_LAST)) rc = launch_panel_reduce(P, y, 0, 1, st, 0, split ? PANEL_ROWS_BEFORE_SPLIT : PANEL_ROWS_ALL);
     return rc;
 }

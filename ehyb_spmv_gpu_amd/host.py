@@ -561,7 +561,8 @@ class Plan:
         _check(self.lib.ehyb_debug_launched_clear(self.h), "ehyb_debug_launched_clear")
 
     def spmv_part(self, x_dev, y_dev, stream, seg_begin, seg_end, flags):
-        """ehyb_spmv_part: flags 1 = the ELL launch first, 2 = the closing pass (EHYB_PART_FIRST / _LAST)."""
+        """ehyb_spmv_part: flags 1 = the ELL launch first, 2 = the closing pass, 4 = the closing pass over the rows from cfg.row_split
+        on (EHYB_PART_FIRST / _LAST / _LAST_FOREIGN).  A refused call has enqueued nothing."""
         _check(self.lib.ehyb_spmv_part(self.h, C.c_void_p(x_dev), C.c_void_p(y_dev), C.c_void_p(stream), seg_begin, seg_end, flags),
                "ehyb_spmv_part")
 

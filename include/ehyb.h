@@ -753,10 +753,17 @@ int ehyb_debug_launched_t(const ehyb_plan* plan, uint8_t* out, int cap);
  * The multiply in PARTS, for a caller that receives x segment by segment (multi-GPU, ehyb_plan_create_host_segs):
  *   flags & EHYB_PART_FIRST   the ELL launch (window columns: all inside column segment 0) runs first;
  *   column segments [seg_begin, seg_end): pass 1 of the panel-form residual over the panels of those segments
- *                             (needs x of those columns only);
- *   flags & EHYB_PART_LAST    pass 2 of the panel form (every pass 1 must have been enqueued on `stream` before) --
+ *                             (needs x of those columns only, and writes no y);
+ *   flags & EHYB_PART_LAST    pass 2 of the panel form (every pass 1 must have been enqueued on `stream` before; reads no x) --
  *                             or, for a plan whose residual is in CSR form, the residual launch (all of x).
  * ehyb_spmv == one call with every segment and both flags.  Parts of one multiply go to ONE stream, in order.
+ * "Window columns: all inside column segment 0" holds for the plan of a rank: segment 0 covers the own columns of the plan's
+ * partitions (its rows) and cfg.n_top > 1 keeps every window, contiguous part and gathered columns, inside them (dist.py:
+ * RankLocalMatrix; a plan with cfg.row_split is built with every window given up).  On any other plan -- segments cut through a single-GPU matrix, tests/test_gpu_parts.py -- the FIRST launch
+ * reads whatever columns its windows hold, and all of x must be there.
+ * A refused call (EHYB_ERR_ARG: segments outside the plan; EHYB_ERR_STATE: a plan that multiplies in one launch, or
+ * EHYB_PART_LAST_FOREIGN on a plan without cfg.row_split) has enqueued nothing.
+ * tests/test_gpu_parts_exact.py pins all of this bit for bit, with every column that has not arrived poisoned.
  */
 enum { EHYB_PART_FIRST = 1, EHYB_PART_LAST = 2,
        EHYB_PART_LAST_FOREIGN = 4 /* panel form with cfg.row_split: pass 2 over the row blocks from row_split on only (they have entries in
