@@ -696,6 +696,18 @@ class Plan:
         return self._solve("ehyb_pcg_fsai_multi", B, X0, None, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True, inner=fsai,
                            counters=1, diag=False)
 
+    def cg_bic(self, b, bic, x0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_pcg_bic: CG on this plan with the block incomplete Cholesky preconditioner z = P^T (L L^T)^-1 P r of `bic` (a Bic of
+        the reordered matrix this plan was built from; there is no inv_diag: L carries the scaling).  -> (x, iterations, relative
+        residual).  A breakdown raises EhybError, unless allow_breakdown: then the residual is NaN."""
+        return self._solve("ehyb_pcg_bic", b, x0, None, (max_iter, rtol, check_every), stream, allow_breakdown, inner=bic, counters=1, diag=False)
+
+    def cg_bic_multi(self, B, bic, X0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_pcg_bic_multi: k independent cg_bic solves that share every multiply; B, X0 (k, n), column j solved as cg_bic(B[j])
+        would -- with plain storage bit for bit.  -> (X (k, n), iterations (k,), relative residuals (k,))."""
+        return self._solve("ehyb_pcg_bic_multi", B, X0, None, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True, inner=bic,
+                           counters=1, diag=False)
+
     def bicgstab(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_bicgstab: BiCGSTAB for an unsymmetric system on the device, right Jacobi-preconditioned if inv_diag is given;
         b, x0, inv_diag in the permuted numbering.  -> (x, iterations, relative residual).  A breakdown raises EhybError,
@@ -1128,6 +1140,135 @@ class Fsai:
     def destroy(self):
         if self.h:
             self.lib.ehyb_fsai_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+BIC_ARRAYS = {"block_ptr": (0, np.int32), "perm": (1, np.int32), "row_ptr": (2, np.int64), "cols": (3, np.int32), "vals": (4, np.float64),
+              "dinv": (5, np.float64), "level_f": (6, np.int32), "level_b": (7, np.int32), "shift": (8, np.float64), "counts": (9, np.int64)}
+BIC_MAX_BLOCK = 20480         # EHYB_BIC_MAX_BLOCK
+BIC_ORDERS = {"stored": 0, "colour": 1}
+
+
+class Bic:
+    """ehyb_bic: the block incomplete Cholesky preconditioner of Plan.cg_bic for a reordered symmetric matrix -- the matrix the plan
+    was built from.  An IC(0) factor of every diagonal block, applied by two triangular solves in one workgroup's LDS.
+    block_rows 0: whole partitions (cut where longer than EHYB_BIC_MAX_BLOCK); order "stored": the rows as they stand,
+    "colour": greedy colouring inside every block (a few levels, more iterations).  upload=False keeps it on the host (no GPU
+    needed)."""
+
+    def __init__(self, matrix, block_rows=0, order="stored", upload=True):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self.n = matrix.n
+        self.order = order
+        _check(self.lib.ehyb_bic_create_host(C.byref(matrix.c), int(block_rows), BIC_ORDERS[order], C.byref(self.h)), "ehyb_bic_create_host")
+        if upload:
+            self.upload()
+
+    @classmethod
+    def raw(cls, block_ptr, row_ptr, cols, vals, dinv, upload=True):
+        """ehyb_bic_create_raw: an object from a caller's strictly lower L in CSR form (block-local columns) and dinv, with the
+        identity order -- for tests of the kernels."""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.order = _lib.load(), C.c_void_p(), "stored"
+        bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        cl = np.ascontiguousarray(cols, dtype=np.int32)
+        vl = np.ascontiguousarray(vals, dtype=np.float64)
+        dv = np.ascontiguousarray(dinv, dtype=np.float64)
+        self.n = len(dv)
+        assert rp.shape == (self.n + 1,) and len(cl) == len(vl) == rp[-1] and len(bp) >= 2
+        if len(cl) == 0:            # (an empty array has no address worth passing; one unread element)
+            cl, vl = np.zeros(1, dtype=np.int32), np.zeros(1)
+        _check(self.lib.ehyb_bic_create_raw(self.n, len(bp) - 1, _ptr(bp, C.c_int32), _ptr(rp, C.c_int64), _ptr(cl, C.c_int32), _ptr(vl, C.c_double),
+                                            _ptr(dv, C.c_double), C.byref(self.h)), "ehyb_bic_create_raw")
+        if upload:
+            self.upload()
+        return self
+
+    def upload(self):
+        _check(self.lib.ehyb_bic_upload(self.h), "ehyb_bic_upload")
+        return self
+
+    def array(self, name):
+        """ehyb_bic_host_array: "block_ptr" (nb + 1,), "perm" (n,), "row_ptr" (n + 1,) int64, "cols" (block-local positions) and
+        "vals" (nnz(L),) -- L in CSR form in position order, strictly lower part --, "dinv", "level_f", "level_b" (n,), "shift"
+        (nb,), "counts" (4,) -- copies"""
+        which, dtype = BIC_ARRAYS[name]
+        p, cnt = C.c_void_p(), C.c_int64()
+        _check(self.lib.ehyb_bic_host_array(self.h, which, C.byref(p), C.byref(cnt)), "ehyb_bic_host_array")
+        if cnt.value == 0 or not p.value:
+            return np.zeros(0, dtype=dtype)
+        buf = (C.c_char * (cnt.value * np.dtype(dtype).itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=dtype, count=cnt.value).copy()
+
+    @property
+    def max_k(self):
+        """ehyb_bic_max_k: the columns one launch of the apply kernel serves"""
+        return int(self.lib.ehyb_bic_max_k(self.h))
+
+    @property
+    def blocks(self):
+        return int(self.array("counts")[0])
+
+    @property
+    def shifted_blocks(self):
+        return int(self.array("counts")[1])
+
+    @property
+    def fallback_blocks(self):
+        return int(self.array("counts")[2])
+
+    @property
+    def levels(self):
+        """the most levels of any block, forward or backward"""
+        return int(self.array("counts")[3])
+
+    @property
+    def stream_info(self):
+        """ehyb_bic_stream_info -> (bytes of the two device streams, their entries without padding, the workgroup size)"""
+        b, e, t = C.c_int64(), C.c_int64(), C.c_int()
+        _check(self.lib.ehyb_bic_stream_info(self.h, C.byref(b), C.byref(e), C.byref(t)), "ehyb_bic_stream_info")
+        return b.value, e.value, t.value
+
+    def apply(self, R, ld=None, active=None, Z0=None, stream=0):
+        """ehyb_bic_apply: Z = P^T (L L^T)^-1 P R for host vectors (permuted numbering): R (n,) -> z (n,), or R (k, n) -> Z (k, n),
+        staged on the device with leading dimension ld (default n).  Z starts as Z0 (k, n) (default NaN); active (k,) flags:
+        ehyb_bic_apply_step, which leaves the columns whose flag is 0 as they were."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        one = R.ndim == 1
+        R2 = R.reshape(1, -1) if one else R
+        k, n = R2.shape
+        assert n == self.n, (n, self.n)
+        ld = n if ld is None else int(ld)
+        assert ld >= n
+        staged, start = np.zeros((k, ld)), np.full((k, ld), np.nan)
+        staged[:, :n] = R2
+        if Z0 is not None:
+            start[:, :n] = np.asarray(Z0, dtype=np.float64).reshape(k, n)
+        dr, dz = DeviceBuffer(k * ld).upload(staged.ravel()), DeviceBuffer(k * ld).upload(start.ravel())
+        if active is None:
+            _check(self.lib.ehyb_bic_apply(self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(stream)), "ehyb_bic_apply")
+        else:
+            flags = np.zeros(k + (k & 1), dtype=np.int32)       # (a DeviceBuffer holds doubles: two int32 each)
+            flags[:k] = np.asarray(active, dtype=np.int32)
+            da = DeviceBuffer(len(flags) // 2).upload(flags.view(np.float64))
+            _check(self.lib.ehyb_bic_apply_step(self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(da.ptr), C.c_void_p(stream)),
+                   "ehyb_bic_apply_step")
+        _check(self.lib.ehyb_dev_sync(), "ehyb_dev_sync")
+        Z = dz.download().reshape(k, ld)
+        self.last_pad = Z[:, n:]          # what lies between the columns: untouched (NaN) if the kernel keeps to its rows
+        return Z[0, :n].copy() if one else Z[:, :n].copy()
+
+    def destroy(self):
+        if self.h:
+            self.lib.ehyb_bic_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

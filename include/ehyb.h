@@ -1318,6 +1318,95 @@ int  ehyb_fsai_factor_step(int n, const int32_t* a_ptr, const int32_t* a_cols, c
 int  ehyb_fsai_tt_step(int n, const double* t_dev, double* s_dev, int rz, void* stream);
 
 /*
+ * PCG WITH BLOCK INCOMPLETE CHOLESKY (BIC): block Jacobi whose blocks are IC(0) factors -- non-overlapping additive Schwarz --
+ * applied as two triangular solves that never leave a workgroup's LDS.  The chains of dependent levels the FSAI section speaks
+ * of are long only if the factor spans the matrix; here a factor spans one block of at most EHYB_BIC_MAX_BLOCK rows (what fits
+ * the LDS of one workgroup), so a level ends at a workgroup barrier, not at a kernel boundary, and no workgroup waits for
+ * another.  M^-1 = P^T (L L^T)^-1 P, L block diagonal.  Everything lives in the numbering of the matrix after
+ * ehyb_matrix_reorder, and the matrix is taken to be symmetric: only its lower triangle (columns j <= i of row i) is read.  A
+ * column is taken to be stored at most once per row.
+ *
+ * Definition.
+ *   Blocks.  Every partition of m->partBoundary is cut into ceil(rows / cap) runs of consecutive rows of nearly equal length, the
+ *   first runs one longer; cap = min(block_rows > 0 ? block_rows : infinity, EHYB_BIC_MAX_BLOCK); block_rows = 0: whole partitions
+ *   (of at most EHYB_BIC_MAX_BLOCK rows).  Every block has at least one row (an empty partition gives none).
+ *   Local order, internal to the object: PERM[p] is the row at position p; within a block the positions are a permutation of
+ *   its rows.  EHYB_BIC_ORDER_STORED: the identity.  EHYB_BIC_ORDER_COLOUR: greedy colouring -- the rows of the block in rising
+ *   order take the smallest colour no already-coloured in-block neighbour holds (both triangles count, the diagonal does not),
+ *   positions by (colour, row).  Rows of one colour are independent of one another, so the levels never exceed the colours.
+ *   Factor.  A_b: the block's entries with row and column inside it, in local order (an entry (i, j), j < i, of the matrix lands
+ *   in row max(pos i, pos j), column min).  L on the pattern of tril(A_b), L L^T ~ A_b, row by row with columns c rising:
+ *   l_ic = (a_ic - sum_k l_ik l_ck) / l_cc over the k < c present in both rows, rising k; l_ii = sqrt(a_ii - sum_k l_ik^2), rising
+ *   k.  The host rounds every product and difference.  DINV[i] = 1 / l_ii is stored, and the solves multiply by it.
+ *   Breakdown.  A pivot that is not a positive finite number refactors the WHOLE block from A_b + alpha diag(A_b) (a_ii + alpha
+ *   a_ii, rounded twice), alpha = 2^-10, 2^-9, ..., 2^10 in turn; SHIFT[b] is the alpha that worked, 0 where none was needed.  If
+ *   none works the block takes its Jacobi form: l_ii = sqrt(a_ii), the stored pattern stays with zero values, SHIFT[b] = -1.  An
+ *   a_ii that is missing or not a positive finite number: EHYB_ERR_ARG, "not positive definite" in ehyb_last_error.
+ *   Levels.  LEVEL_F[p] = 1 + max LEVEL_F[q] over the strictly lower entries (p, q) of row p, 0 if it has none; LEVEL_B[p] = 1 +
+ *   max LEVEL_B[q] over the q > p with l_qp stored, 0 if there is none.
+ *
+ * ehyb_bic_create_host (no GPU needed; the result does not depend on the number of OpenMP threads: blocks are dealt to threads
+ *   whole).  order: EHYB_BIC_ORDER_STORED / _COLOUR.  EHYB_ERR_ARG before any work: a null pointer, block_rows < 0, another
+ *   order, a matrix without partition data, a column outside the matrix.
+ * ehyb_bic_create_raw (for tests of the kernels): an object from a caller's strictly lower L in CSR form (block-local columns,
+ *   rising) and dinv, with the identity order; the levels by the rule above.  EHYB_ERR_ARG: a column >= its row's position or
+ *   outside the block, an unsorted row, an empty block or one longer than EHYB_BIC_MAX_BLOCK.
+ * ehyb_bic_host_array: which = EHYB_BIC_BLOCK_PTR int32[nb + 1], _PERM int32[n], _ROW_PTR int64[n + 1], _COLS int32[nnz(L)]
+ *   (block-local positions), _VALS double[nnz(L)] (L in CSR form in position order, strictly lower part), _DINV double[n],
+ *   _LEVEL_F / _LEVEL_B int32[n], _SHIFT double[nb], _COUNTS int64[4] {blocks, shifted blocks, fallback blocks, most levels of
+ *   any block in either direction}.
+ * ehyb_bic_max_k: min(4, EHYB_BIC_MAX_BLOCK / longest block): the columns one launch of the apply kernel serves.
+ * ehyb_bic_upload: two streams, one for the forward solve (the rows of L) and one for the backward solve (the rows of L^T: the
+ *   values are stored twice, which keeps atomic adds out of the LDS and every sum in a fixed order).  A stream holds the rows
+ *   grouped by level, within a level in falling length, a 16-bit block-local column per entry, laid out [entry][lane] so that
+ *   consecutive lanes read consecutive addresses, pass by pass; a pass holds only the rows that reach it (the rows fall in
+ *   length: jagged, not padded to the longest row).  Every value and column word is read once per apply: 10 bytes per entry
+ *   and what a row lacks of its own last pass, 12 per row and direction, a word per round and per pass.  A row is summed by a
+ *   group of g lanes, g a power of two 1 .. 64 chosen per level:
+ *   the widest with rows_of_the_level * g <= the workgroup's threads and g <= mean row length of the level / 2 (a narrow level
+ *   of long rows gets wide groups, a wide level of short rows one lane per row).  The workgroup has a quarter of the longest
+ *   block's rows in threads, in whole waves, 64 .. 1024.  ehyb_bic_destroy releases both sides; NULL is allowed.
+ *   ehyb_bic_stream_info: the bytes of the two streams, their entries without padding, the workgroup size.
+ * ehyb_bic_apply: Z = P^T (L L^T)^-1 P R for k columns (ldr, ldz >= n) on the stream -- one workgroup per block, most expensive
+ *   blocks first, the block's rows x kk doubles in LDS (kk <= ehyb_bic_max_k; wider calls go in passes), loaded through PERM,
+ *   solved forward and backward in place, stored through PERM.  The only synchronisation is the workgroup barrier between
+ *   levels; every thread executes the same number, taken from the block's record.  Lane j of a group adds its terms in rising
+ *   stream order (fused multiply-adds), the group's sums go through a fixed shuffle tree: the bits of a column do not depend on k.
+ * ehyb_bic_apply_step (for tests of the kernel): ehyb_bic_apply with the columns' flags, int[k] on the device, as the solver
+ *   passes them: a column whose flag is 0 is left as it was.
+ * ehyb_pcg_bic / ehyb_pcg_bic_multi: arguments (there is no inv_diag: L carries the scaling), stopping, breakdown, graphs and
+ *   outputs as ehyb_pcg_fsai / ehyb_pcg_fsai_multi -- the same loop.  Per iteration: q = A p, p.q, the update kernel without a
+ *   preconditioner, Z = M^-1 R (a column whose flag is 0 is left untouched), the partials of r.z (bic_rz_kernel, fixed-order
+ *   sums, slot rz of ehyb_cg_layout), the direction kernel.  The plan of A may use any storage; the object reads m, not the
+ *   plan.  With plain storage for A, x, iters_done and rel_residual are the same bits from run to run, for graphs and plain
+ *   launches, on any stream and for any check_every, and column j of a k-column solve equals the one-vector solve.
+ *   In this order: EHYB_ERR_ARG for what ehyb_pcg rejects, then for a null object or one with another number of rows;
+ *   EHYB_ERR_STATE for a plan, then an object, that was never uploaded.  All before any device work.
+ * Out of scope: fp32 storage of L, a numeric phase on the device, overlapping blocks, ILU for GMRES / BiCGSTAB, several GPUs.
+ */
+#define EHYB_BIC_MAX_BLOCK 20480
+enum { EHYB_BIC_ORDER_STORED = 0, EHYB_BIC_ORDER_COLOUR = 1 };
+enum {
+    EHYB_BIC_BLOCK_PTR = 0, EHYB_BIC_PERM = 1, EHYB_BIC_ROW_PTR = 2, EHYB_BIC_COLS = 3, EHYB_BIC_VALS = 4, EHYB_BIC_DINV = 5,
+    EHYB_BIC_LEVEL_F = 6, EHYB_BIC_LEVEL_B = 7, EHYB_BIC_SHIFT = 8, EHYB_BIC_COUNTS = 9
+};
+typedef struct ehyb_bic ehyb_bic;
+int  ehyb_bic_create_host(const matrixCOO* m, int block_rows, int order, ehyb_bic** out);
+int  ehyb_bic_create_raw(int n, int nb, const int32_t* block_ptr, const int64_t* row_ptr, const int32_t* cols, const double* vals,
+                         const double* dinv, ehyb_bic** out);
+int  ehyb_bic_host_array(const ehyb_bic* f, int which, const void** ptr, int64_t* count);
+int  ehyb_bic_max_k(const ehyb_bic* f);
+int  ehyb_bic_upload(ehyb_bic* f);
+void ehyb_bic_destroy(ehyb_bic* f);
+int  ehyb_bic_stream_info(const ehyb_bic* f, int64_t* bytes, int64_t* entries, int* threads);
+int  ehyb_bic_apply(ehyb_bic* f, const double* R_dev, int64_t ldr, double* Z_dev, int64_t ldz, int k, void* stream);
+int  ehyb_bic_apply_step(ehyb_bic* f, const double* R_dev, int64_t ldr, double* Z_dev, int64_t ldz, int k, const int* active_dev, void* stream);
+int  ehyb_pcg_bic(ehyb_plan* plan, ehyb_bic* f, const double* b_dev, double* x_dev, int max_iter, double rtol, int check_every,
+                  void* stream, int* iters_done, double* rel_residual);
+int  ehyb_pcg_bic_multi(ehyb_plan* plan, ehyb_bic* f, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k, int max_iter,
+                        double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+
+/*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
  * ehyb_spmv_gpu_amd/dist.py (HaloCG), where q = A p goes through the halo exchange.  s is the partial-sum
  * array: `slots` slots of `slot_doubles` doubles (ehyb_cg_layout).  Every rank launches the same grid, so an
