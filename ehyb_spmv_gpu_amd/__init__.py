@@ -39,6 +39,7 @@ from .host import (  # noqa: F401
     partition_graph,
     rigid_body_modes,
     sizing,
+    small_svd,
     spmv_gpu_ehyb,
     tune_decide,
     vector_recover,

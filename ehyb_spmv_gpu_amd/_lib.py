@@ -373,6 +373,11 @@ SIGNATURES = {
     "ehyb_eigsh_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "ehyb_eigsh_scale_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_eigsh_rotate_step": (C.c_int, [C.c_int, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "ehyb_svds": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _vp, C.c_int64, _vp, C.c_int64, _vp, _ip, _ip, _ip, _ip,
+                            _dp]),
+    "ehyb_svds_basis": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip]),
+    "ehyb_small_svd": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "ehyb_svds_next_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "ehyb_lobpcg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _vp, C.c_int64, _vp, _ip,
                               _ip, _ip, _dp]),
     "ehyb_lobpcg_rr": (C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip]),

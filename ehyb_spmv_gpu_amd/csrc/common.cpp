@@ -444,6 +444,119 @@ int ehyb_sym_eig(int m, const double* T, int ldt, double* evals, double* Y)
     return EHYB_OK;
 }
 
+// The singular value decomposition of a small dense matrix by one-sided (Hestenes) cyclic Jacobi (the projected problem of
+// ehyb_svds): sweeps over the column pairs p < q in a fixed order, each pair rotated until a_p . a_q is at most rows 2^-53 |a_p| |a_q|;
+// the rotations accumulate in Y, the column norms are sigma and the normalised columns X.  The matrix itself is rotated, never
+// M^T M: a small sigma keeps the digits its column has.  The entries are first scaled by a power of two (exactly) so that the
+// largest is near one and no square over- or underflows.  Both factors are polished by one Newton-Schulz step at the end.  A fixed
+// sweep limit and a fixed order: the same input gives the same bits.
+int ehyb_small_svd(int rows, int cols, const double* M, int ldm, double* sigma, double* X, double* Y)
+{
+    clear_error();
+    constexpr int kMax = EHYB_SVDS_MAX_BASIS + 1;
+    if (cols < 1 || rows < cols || rows > kMax || !M || ldm < rows || !sigma || !X || !Y)
+        EHYB_FAIL(EHYB_ERR_ARG, "ehyb_small_svd: bad arguments (rows %d, cols %d, 1 <= cols <= rows <= %d; ldm %d)", rows, cols, kMax, ldm);
+    std::vector<double> A((size_t)rows * cols), V((size_t)cols * cols, 0.0);
+    double big = 0.0;
+    for (int j = 0; j < cols; ++j)
+        for (int i = 0; i < rows; ++i) {
+            const double v = M[(size_t)j * ldm + i];
+            if (!std::isfinite(v)) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_small_svd: entry (%d, %d) is not finite", i, j);
+            A[(size_t)j * rows + i] = v;
+            big = std::max(big, std::fabs(v));
+        }
+    const int shift = big > 0 ? std::ilogb(big) : 0;
+    for (double& v : A) v = std::scalbn(v, -shift);
+    for (int i = 0; i < cols; ++i) V[(size_t)i * cols + i] = 1.0;
+    auto dot = [&](const double* a, const double* b, int len) {
+        double t = 0.0;
+        for (int i = 0; i < len; ++i) t += a[i] * b[i];
+        return t;
+    };
+    // the rounding of a_p . a_q itself is of this size: a tighter test would go on rotating noise, and every needless rotation
+    // costs Y an ulp of orthogonality -- which a restart of ehyb_svds hands on to the kept vectors
+    const double tol = rows * 0x1p-53;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p + 1 < cols; ++p)
+            for (int q = p + 1; q < cols; ++q) {
+                double *ap = &A[(size_t)p * rows], *aq = &A[(size_t)q * rows];
+                const double app = dot(ap, ap, rows), aqq = dot(aq, aq, rows), apq = dot(ap, aq, rows);
+                if (apq == 0.0 || std::fabs(apq) <= tol * std::sqrt(app) * std::sqrt(aqq)) continue;
+                const double zeta = (aqq - app) / (2.0 * apq);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(zeta * zeta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int i = 0; i < rows; ++i) {
+                    const double x = ap[i], y = aq[i];
+                    ap[i] = c * x - s * y;
+                    aq[i] = s * x + c * y;
+                }
+                double *vp = &V[(size_t)p * cols], *vq = &V[(size_t)q * cols];
+                for (int i = 0; i < cols; ++i) {
+                    const double x = vp[i], y = vq[i];
+                    vp[i] = c * x - s * y;
+                    vq[i] = s * x + c * y;
+                }
+                rotated = true;
+            }
+        if (!rotated) break;
+    }
+    std::vector<double> norm(cols);
+    std::vector<int> order(cols);
+    for (int j = 0; j < cols; ++j) {
+        norm[j] = std::sqrt(dot(&A[(size_t)j * rows], &A[(size_t)j * rows], rows));
+        order[j] = j;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return norm[x] > norm[y]; });
+    for (int j = 0; j < cols; ++j) {
+        const int o = order[j];
+        sigma[j] = std::scalbn(norm[o], shift);
+        memcpy(Y + (size_t)j * cols, &V[(size_t)o * cols], (size_t)cols * sizeof(double));
+        for (int i = 0; i < rows; ++i) X[(size_t)j * rows + i] = norm[o] > 0 ? A[(size_t)o * rows + i] / norm[o] : 0.0;
+    }
+    // a zero sigma: the unit vector that the columns set so far leave most of, orthogonalised twice against them
+    for (int j = 0; j < cols; ++j) {
+        if (sigma[j] > 0) continue;
+        std::vector<double> best(rows), e(rows);
+        double best_norm = -1.0;
+        for (int k = 0; k < rows; ++k) {
+            std::fill(e.begin(), e.end(), 0.0);
+            e[k] = 1.0;
+            for (int pass = 0; pass < 2; ++pass)
+                for (int l = 0; l < cols; ++l) {
+                    if (l >= j && !(sigma[l] > 0)) continue;  // not set yet (those before j have been completed)
+                    const double* xl = X + (size_t)l * rows;
+                    const double d = dot(xl, e.data(), rows);
+                    for (int i = 0; i < rows; ++i) e[i] -= d * xl[i];
+                }
+            const double en = std::sqrt(dot(e.data(), e.data(), rows));
+            if (en > best_norm) {
+                best_norm = en;
+                best = e;
+            }
+        }
+        for (int i = 0; i < rows; ++i) X[(size_t)j * rows + i] = best[i] / best_norm;
+    }
+    // The rotations leave X^T X and Y^T Y off the identity by some rows 2^-52, and a restart of ehyb_svds hands that on to the kept
+    // vectors, restart after restart.  One Newton-Schulz step, Z += Z (I - Z^T Z) / 2, moves Z by half its defect -- below what
+    // the residuals can see -- to the nearest orthonormal columns, and leaves a defect of a few ulps.
+    auto polish = [&](double* Z, int r, int c) {
+        std::vector<double> E((size_t)c * c), Zn((size_t)r * c);
+        for (int a = 0; a < c; ++a)
+            for (int b = 0; b < c; ++b) E[(size_t)b * c + a] = 0.5 * ((a == b ? 1.0 : 0.0) - dot(Z + (size_t)a * r, Z + (size_t)b * r, r));
+        for (int b = 0; b < c; ++b)
+            for (int i = 0; i < r; ++i) {
+                double t = 0.0;
+                for (int a = 0; a < c; ++a) t += Z[(size_t)a * r + i] * E[(size_t)b * c + a];
+                Zn[(size_t)b * r + i] = Z[(size_t)b * r + i] + t;
+            }
+        memcpy(Z, Zn.data(), Zn.size() * sizeof(double));
+    };
+    polish(X, rows, cols);
+    polish(Y, cols, cols);
+    return EHYB_OK;
+}
+
 }  // extern "C"
 
 // C++-linkage names of reordering.h (reference reordering.h:6-10).

@@ -32,6 +32,7 @@
 
 #include "ehyb_internal.h"
 #include "solve_loop.h"
+#include "transpose_pair.h"
 #include "vec_walk.h"
 
 using namespace ehyb;
@@ -443,22 +444,15 @@ double device_order_sum(const double* part, int grid)
     return total;
 }
 
-// The checks of both entry points, in the order of include/ehyb.h; all before any device work.
+// The checks of both entry points, in the order of include/ehyb.h; all before any device work.  Those of the pair (plan, plan_t)
+// are transpose_pair.h's, shared with ehyb_svds.hip.
 int lsqr_checks(const char* who, const ehyb_plan* P, const ehyb_plan* PT, bool args_ok, double damp, double atol, double btol, int max_iter)
 {
     if (!P || !args_ok) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
     if (max_iter < 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: max_iter %d", who, max_iter);
     if (!(damp >= 0) || !(atol >= 0) || !(btol >= 0)) EHYB_FAIL(EHYB_ERR_ARG, "%s: damp %g, atol %g, btol %g", who, damp, atol, btol);
-    if (P->host.row_begin != 0 || P->host.row_end != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "%s: needs a plan over all rows", who);
-    if (PT && PT->host.n_cols != P->host.n_cols)
-        EHYB_FAIL(EHYB_ERR_ARG, "%s: plan_t has %d rows, plan %d (pad a rectangular matrix to square)", who, PT->host.n_cols, P->host.n_cols);
-    if (PT && (PT->host.row_begin != 0 || PT->host.row_end != PT->host.n_cols))
-        EHYB_FAIL(EHYB_ERR_ARG, "%s: needs a plan_t over all rows", who);
-    int rc;
-    if (!PT && (rc = ehyb_spmv_t_supported(P)) != EHYB_OK) return rc;  // (the form is named in ehyb_last_error)
-    if ((rc = solve_uploaded(who, P)) != EHYB_OK) return rc;
-    if (PT && !PT->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: plan_t not uploaded (no CPU fallback exists)", who);
-    return EHYB_OK;
+    const int rc = pair_args(who, P, PT);
+    return rc != EHYB_OK ? rc : pair_uploaded(who, P, PT);
 }
 
 // The one driver: k solves that share both multiplies.  Every column has its own slots, state, status word and counter and is
@@ -475,15 +469,8 @@ int lsqr_solve(const char* who, bool name_column, ehyb_plan* P, ehyb_plan* PT, c
     const size_t tail_at = (size_t)k * L_COUNT * kMaxGrid;
     double* tail = s + tail_at;
     const hipStream_t st = L.st;
-    // T = A^T U: one ehyb_spmm on the plan of A^T, or column by column on the plan of A
-    const auto multiply_t = [&](const double* in, double* out, int walk) -> int {
-        if (PT) return ehyb_spmm(PT, in, n, out, n, k, st, walk);
-        for (int j = 0; j < k; ++j) {
-            const int e = ehyb_spmv_t(P, in + (size_t)j * n, out + (size_t)j * n, st);
-            if (e != EHYB_OK) return e;
-        }
-        return EHYB_OK;
-    };
+    // T = A^T U: one ehyb_spmm on the plan of A^T, or column by column on the plan of A (transpose_pair.h)
+    const auto multiply_t = [&](const double* in, double* out, int walk) -> int { return ::multiply_t(P, PT, in, out, n, k, st, walk); };
 
     int rc = ehyb_spmm(P, X, ldx, t, n, k, st, EHYB_WALK_LAST_TO_FIRST);
     if (rc != EHYB_OK) return rc;

@@ -812,6 +812,47 @@ class Plan:
         X = dv.download().reshape(-1, ldv)[:f, :n].copy() if dv else None
         return evals[:f].copy(), X, info
 
+    def svds(self, nsv, plan_t=None, basis=0, max_restarts=300, tol=1e-10, v0=None, vectors=True, allow_breakdown=False, stream=0):
+        """ehyb_svds: the nsv (1 .. 16) largest singular values of the plan's matrix with their left and right singular vectors,
+        by thick-restart Golub-Kahan-Lanczos bidiagonalisation on the device; a rectangular matrix goes in padded square
+        (pad_square).  plan_t as in lsqr: a Plan of A^T in this plan's numbering (Matrix.transposed_like), this plan itself for a
+        symmetric A, or None: every A^T multiply is spmv_t on this plan (reproducible up to the order of summation only).  basis
+        0 = min(max(2 nsv + 1, 20), 64), at most 64; v0 (None: the start vector of eigsh) and the vectors in the permuted numbering.
+        -> (s (found,) falling, U (found, n), V (found, n) or None with vectors=False, info) with info = {"found", "nconv",
+        "multiplies" (A and A^T together), "restarts", "resid" (found,), "status" ("ok" or "breakdown")}; A V[i] = s[i] U[i] by
+        construction and resid[i] estimates ||A^T U[i] - s[i] V[i]||; nconv < found means max_restarts ran out; found < nsv means
+        the matrix has no more (a multiple sigma is found once).  The smallest singular values are out of reach of this method.  A
+        breakdown (a non-finite quantity) raises EhybError, unless allow_breakdown: then found = nconv = 0 and s, U, V are empty."""
+        n, nsv = self.n, int(nsv)
+        ld = n + (n & 1)
+        d0 = None if v0 is None else DeviceBuffer(n).upload(v0)
+        du = dv = None
+        if vectors:
+            du = DeviceBuffer(max(nsv, 1) * ld).upload(np.zeros(max(nsv, 1) * ld))
+            dv = DeviceBuffer(max(nsv, 1) * ld).upload(np.zeros(max(nsv, 1) * ld))
+        svals, resid = np.zeros(max(nsv, 1)), np.zeros(max(nsv, 1))
+        found, nconv, mult, rest = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self.lib.ehyb_svds(self.h, plan_t.h if plan_t is not None else None, C.c_void_p(d0.ptr) if d0 else None, nsv, int(basis),
+                                int(max_restarts), tol, _ptr(svals, C.c_double), C.c_void_p(du.ptr) if du else None, ld,
+                                C.c_void_p(dv.ptr) if dv else None, ld, C.c_void_p(stream), C.byref(found), C.byref(nconv), C.byref(mult),
+                                C.byref(rest), _ptr(resid, C.c_double))
+        broke = rc != 0 and b"breakdown" in self.lib.ehyb_last_error()
+        if rc != 0 and not (allow_breakdown and broke):
+            raise EhybError(rc, "ehyb_svds")
+        f = found.value
+        info = {"found": f, "nconv": nconv.value, "multiplies": mult.value, "restarts": rest.value, "resid": resid[:f].copy(),
+                "status": "breakdown" if broke else "ok"}
+        U = du.download().reshape(-1, ld)[:f, :n].copy() if du else None
+        V = dv.download().reshape(-1, ld)[:f, :n].copy() if dv else None
+        return svals[:f].copy(), U, V, info
+
+    def norm2(self, plan_t=None, tol=1e-6, stream=0):
+        """An estimate of ||A||_2: sigma_0 of svds(1) at relative residual tol.  It is a Ritz value, which approaches ||A||_2 FROM
+        INSIDE: never above ||A||_2 in exact arithmetic and below it by at most about tol^2 ||A||_2 once converged.  A caller that
+        needs an upper bound widens it.  0.0 for a zero matrix."""
+        s = self.svds(1, plan_t=plan_t, tol=tol, vectors=False, stream=stream)[0]
+        return float(s[0]) if len(s) else 0.0
+
     def lobpcg(self, nev, block=0, coarse=None, inv_diag=None, X0=None, max_iter=500, tol=1e-8, anorm=0.0, vectors=True,
                allow_breakdown=False, stream=0):
         """ehyb_lobpcg: the nev (1 .. 8) smallest eigenpairs of the plan's symmetric matrix by LOBPCG on the device, with a block
@@ -1309,6 +1350,19 @@ def pad_square(indptr, indices, data, shape):
     if m < n:
         indptr = np.concatenate([indptr, np.full(n - m, indptr[-1], dtype=np.int64)])
     return indptr, indices, np.asarray(data, dtype=np.float64)
+
+
+def small_svd(M):
+    """ehyb_small_svd: M = X diag(sigma) Y^T for a dense (rows, cols) matrix with 1 <= cols <= rows <= 65 by one-sided Jacobi on
+    the host -> (X (rows, cols) with orthonormal columns, sigma (cols,) falling, Y (cols, cols) orthogonal).  The same input gives
+    the same bits.  Raises EhybError (code 1) for a size out of range or a non-finite entry."""
+    M = np.asfortranarray(M, dtype=np.float64)
+    assert M.ndim == 2
+    rows, cols = M.shape
+    sigma, X, Y = np.zeros(max(cols, 1)), np.zeros((rows, max(cols, 1)), order="F"), np.zeros((max(cols, 1), max(cols, 1)), order="F")
+    _check(_lib.load().ehyb_small_svd(rows, cols, _ptr(M, C.c_double), max(rows, 1), _ptr(sigma, C.c_double), _ptr(X, C.c_double),
+                                      _ptr(Y, C.c_double)), "ehyb_small_svd")
+    return np.ascontiguousarray(X), sigma, np.ascontiguousarray(Y)
 
 
 def lobpcg_rr(G, H, nb):

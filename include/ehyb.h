@@ -1823,6 +1823,100 @@ int ehyb_eigsh_rotate_step(int n, int64_t ld_src, const double* src_dev, int64_t
                            int mc, int kc, void* stream);
 
 /*
+ * The nsv LARGEST singular values of the plan's matrix with their left and right singular vectors -- what
+ * scipy.sparse.linalg.svds(which="LM") covers --, by Golub-Kahan-Lanczos bidiagonalisation with full two-sided
+ * reorthogonalisation (classical Gram-Schmidt twice on each side: the two passes of ehyb_gmres) and a thick restart with Ritz
+ * vectors (Baglama and Reichel 2005, restarted as ehyb_eigsh restarts), the vectors on the device.  It works on A and A^T
+ * directly: eigsh of A^T A would square the condition number, eigsh of [0 A; A^T 0] would double every vector and find every
+ * sigma twice.  The host looks once per restart cycle: it takes the SVD of the projected matrix B (at most 64 x 64,
+ * ehyb_small_svd), decides convergence and uploads the two rotations.  Ritz values approach the singular values from inside:
+ * sigma_0 is never above ||A||_2 in exact arithmetic.  A MULTIPLE sigma is found ONCE, as ehyb_eigsh finds a multiple eigenvalue
+ * once.  NOT covered: the smallest singular values (plain Ritz values converge too slowly there; harmonic Ritz values or
+ * shift-and-invert would be needed), a block version, one-sided reorthogonalisation, more than one column per pass.
+ * Setting.  The plan is over all rows and square: an m x n matrix goes in padded with empty rows or columns to max(m, n), as
+ *   ehyb_lsqr takes it; the padded entries of every u and v are then 0 but for the start vector's share of a null space.  plan_t,
+ *   plan_t == plan and plan_t == NULL mean what they mean for ehyb_lsqr: a plan of A^T in the numbering of `plan`; the caller's
+ *   statement that A is symmetric (the only way to run on symmetric pair storage); every A^T multiply is ehyb_spmv_t(plan).
+ *   nsv 1 .. EHYB_SVDS_MAX_NSV; basis 0 = min(max(2 nsv + 1, 20), 64), else nsv + 2 .. EHYB_SVDS_MAX_BASIS; the effective basis
+ *   m = min(basis, n); keep = nsv + (m - nsv) / 2 (ehyb_svds_basis: the rule of ehyb_eigsh_basis, nsv for nev).
+ *   Start vector: v0_dev, NULL = v_i = 1 + (i mod 7) / 8; normalised to p_0.  A zero or non-finite norm: breakdown.
+ * Bases.  P holds the right vectors, m + 1 columns starting with p_0 = v0 / ||v0||; Q holds the left vectors, m columns; both
+ *   column-major with leading dimension n + (n & 1).  The multiplies read their input straight from a basis column.
+ * Step j, for j = k .. m - 1, where k kept triplets exist (0 in the first cycle):
+ *   Left half.  w = A p_j.  Twice: c_i = q_i.w for i < j, all from the same w; w -= sum c_i q_i; h_i += c_i (at j = 0 only the norm
+ *     is taken).  alpha^2 = w.w.  Column j of the projected matrix: B[i, j] = h_i for i < j.  A non-finite h or alpha^2:
+ *     breakdown.  alpha^2 <= 2^-90 (h.h + alpha^2): a LEFT COLLAPSE -- A p_j lies in the span of Q.  The multiply counts; the cycle
+ *     ends with J = j + 1 right vectors, Jl = j left vectors and beta = 0; no q_j is written.  Else B[j, j] = alpha = sqrt(alpha^2)
+ *     and q_j = w / alpha, a true division.
+ *   Right half.  w = A^T q_j.  Twice: dots and update against p_0 .. p_j.  Its coefficients g are checked for finiteness and
+ *     otherwise discarded: B is measured by the left halves only.  beta^2 = w.w.  beta^2 <= 2^-90 (g.g + beta^2): an invariant
+ *     subspace (a right collapse), J = Jl = j + 1 and beta = 0.  Else p_{j+1} = w / beta.
+ *   The counter counts multiplies, two per full step.  After a collapse the remaining launches of the cycle return at once.  The
+ *   host tells a left collapse from a right one by the parity of the multiplies the cycle made.
+ *   The collapse rules are a net for EXACT cases (a zero matrix, an identity, a start vector in an invariant subspace): they ask
+ *   that the orthogonalisation removed all but 2^-45 of w.  On a matrix that is rank-deficient only to rounding (a dense 12 x 12
+ *   of rank 5) what is left of w is noise of relative size 1e-13, above the threshold: the solve runs on through noise vectors
+ *   and still returns correct triplets, the extra ones with sigma near zero.
+ * Cycle end, on the host.  B[:Jl, :J] = X Sigma Y^T by ehyb_small_svd, sigma falling.  res_i = |beta X[Jl - 1, i]|, which is
+ *   ||A^T u_i - sigma_i v_i||; A v_i = sigma_i u_i holds by construction.  want = min(nsv, Jl).  nconv = the number of leading
+ *   triplets with res_i <= tol sigma_0; counting stops at the first that fails.  Stop when nconv == want, on a collapse of either
+ *   kind, or after max_restarts restarts.  A zero matrix collapses at j = 0 with Jl = 0: found = 0 and EHYB_OK.
+ * Restart.  kk = min(keep, J - 1).  New p_i = P y_i and new q_i = Q x_i for i < kk; new p_kk = old p_J.  B = diag(sigma_0 ..
+ *   sigma_{kk-1}).  The next cycle starts at j = kk; the left half of that step re-measures the arrow column beta X[J-1, i] through
+ *   the full orthogonalisation: the host never plants it.  Two launches of the rotation kernel of ehyb_eigsh, P then Q, go through
+ *   one spare buffer of keep + 1 columns, each with its device-to-device copy back; the final U and V are the same kernel writing
+ *   into the caller's arrays.  Device vectors in all: 2 m + keep + 3.
+ * Outputs: svals[i] = sigma_i for i < want; U_dev column i (at U_dev + i ldu) = Q x_i and V_dev column i (at V_dev + i ldv) = P y_i,
+ * unit length, in the permuted numbering; resid[i] = res_i; *found = want; *nconv, *multiplies (A and A^T together), *restarts.
+ * Any of the host outputs, U_dev and V_dev may be NULL; ldu (ldv) even and >= n where U_dev (V_dev) is given; U_dev, V_dev and
+ * v0_dev 16-byte aligned.  stream NULL = a private stream.  EHYB_OK also when nconv < nsv after max_restarts and when a collapse
+ * leaves fewer than nsv triplets.  A non-finite quantity: EHYB_ERR_ARG with "breakdown" in ehyb_last_error after every scalar
+ * output is written -- found = nconv = 0, U_dev and V_dev untouched.
+ * Per full step: two multiplies (A and A^T walk in opposite directions, alternating), four dots, four updates (the kernels of
+ * ehyb_gmres on its slots and tail) and two launches of the one new kernel.  The first cycle and a cycle after a short restart
+ * (kk < keep) are plain launches; the steady cycle (j = keep .. m - 1) is captured once as a linear hipGraph and replayed
+ * (cfg.graphs = 2: plain launches).  The host arithmetic is deterministic and every device sum is re-added from per-workgroup
+ * partials in a fixed order: with a plan_t in plain storage every output is the same bits from run to run, for graphs and plain
+ * launches, for a given or a private stream; through ehyb_spmv_t (plan_t NULL: atomic adds), symmetric pair storage or a
+ * panel-form residual up to the order of summation.
+ * EHYB_ERR_ARG, in this order and before any device work: a null plan; nsv or basis outside its range or max_restarts < 0; a
+ * negative or NaN tol; a plan not over all rows; a plan_t of another dimension or not over all rows; with plan_t NULL what
+ * ehyb_spmv_t_supported refuses (the texts of ehyb_lsqr under the name ehyb_svds); an odd ldu or ldv or one below n with a
+ * non-NULL array; a misaligned U_dev, V_dev or v0_dev.  Then EHYB_ERR_STATE for a plan, then a plan_t, never uploaded.
+ *
+ * ehyb_svds_basis (host only): ehyb_eigsh_basis with nsv for nev.  No argument check.
+ *
+ * ehyb_small_svd (host only, no device): M = X Sigma Y^T for the dense rows x cols matrix M (column-major, leading dimension ldm),
+ * 1 <= cols <= rows <= EHYB_SVDS_MAX_BASIS + 1, by one-sided (Hestenes) cyclic Jacobi with a fixed pair order and a fixed sweep
+ * limit: the same input gives the same bits.  sigma (cols) falling; X rows x cols, column-major with leading dimension rows,
+ * orthonormal columns; Y cols x cols, leading dimension cols, orthogonal.  A zero sigma gets a completed orthonormal column of X.
+ * Each factor ends with one Newton-Schulz step, Z += Z (I - Z^T Z) / 2, so that its defect is a few ulps whatever the rotations left.
+ * The matrix itself is rotated, never M^T M, so a small sigma keeps its digits.  ehyb_svds hands it B^T -- tall when the collapse
+ * was a left one -- and swaps the factors.  EHYB_ERR_ARG for sizes out of range, ldm < rows, a null pointer or a non-finite entry.
+ *
+ * The new kernel one launch with slot_doubles / 2 workgroups, on the slots and tail of ehyb_gmres_layout; dst_dev a basis with the
+ * even leading dimension ld_dst >= n, dst_dev and w_dev 16-byte aligned.  It returns at once, writing nothing, when the status is
+ * not status_running; a breakdown sets status_breakdown and writes nothing else.
+ *   side 0 (left), j = 0 .. 63: alpha^2 from slot_ww, h_0 .. h_{j-1} from Hessenberg copy 1; the rules of the left half above:
+ *           R[0 .. j - 1, j] = h, R[j, j] = alpha (0 at a collapse), counter + 1; a collapse sets status_converged and writes no
+ *           vector; else column j of dst_dev (Q) = w / alpha.
+ *   side 1 (right), j = 0 .. 63: beta^2 from slot_ww, g_0 .. g_j from Hessenberg copy 1, read for the tests only;
+ *           gt_at + j + 1 = beta (0 at a collapse), counter + 1; else column j + 1 of dst_dev (P) = w / beta.
+ *   side 1, j = -1: the start.  w.w zero or non-finite: status_breakdown; else gt_at + 0 = sqrt(w.w), column 0 = w / sqrt(w.w);
+ *           the counter stays.
+ * EHYB_ERR_ARG for n < 0 or a null pointer; then side or j outside its range; then an odd ld_dst or one below n, a misaligned
+ * vector.  Asynchronous on `stream`.
+ */
+#define EHYB_SVDS_MAX_BASIS 64
+#define EHYB_SVDS_MAX_NSV 16
+int ehyb_svds(ehyb_plan* plan, ehyb_plan* plan_t, const double* v0_dev, int nsv, int basis, int max_restarts, double tol,
+              double* svals, double* U_dev, int64_t ldu, double* V_dev, int64_t ldv, void* stream, int* found, int* nconv,
+              int* multiplies, int* restarts, double* resid);
+int ehyb_svds_basis(int nsv, int basis, int n, int* m, int* keep);
+int ehyb_small_svd(int rows, int cols, const double* M, int ldm, double* sigma, double* X, double* Y);
+int ehyb_svds_next_step(int n, int64_t ld_dst, double* dst_dev, const double* w_dev, double* s_dev, int side, int j, void* stream);
+
+/*
  * The nev SMALLEST eigenpairs of the plan's SYMMETRIC matrix by LOBPCG (locally optimal block preconditioned conjugate gradients),
  * the vectors on the device.  Where ehyb_eigsh finds a multiple eigenvalue once and is slowest at the low end of a stiffness-like
  * spectrum, this is a block method (a block of nb vectors finds up to nb copies of an eigenvalue) that takes a preconditioner.
