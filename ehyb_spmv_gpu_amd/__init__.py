@@ -8,6 +8,7 @@ from . import host  # noqa: F401
 from .host import (  # noqa: F401
     ARRAYS,
     Bic,
+    Bilu,
     EHYB_PART_AUTO,
     EHYB_PART_CONTIGUOUS,
     EHYB_PART_DEGREE,

@@ -334,6 +334,20 @@ SIGNATURES = {
     "ehyb_bic_apply_step": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, _vp]),
     "ehyb_pcg_bic": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
     "ehyb_pcg_bic_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_bilu_create_host": (C.c_int, [_mp, C.c_int, C.c_int, _P(_vp)]),
+    "ehyb_bilu_create_raw": (C.c_int, [C.c_int, C.c_int, _P(C.c_int32), _i64p, _P(C.c_int32), _dp, _i64p, _P(C.c_int32), _dp, _dp, _P(_vp)]),
+    "ehyb_bilu_host_array": (C.c_int, [_vp, C.c_int, _P(_vp), _i64p]),
+    "ehyb_bilu_max_k": (C.c_int, [_vp]),
+    "ehyb_bilu_upload": (C.c_int, [_vp]),
+    "ehyb_bilu_destroy": (None, [_vp]),
+    "ehyb_bilu_stream_info": (C.c_int, [_vp, _i64p, _i64p, _ip]),
+    "ehyb_bilu_apply": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp]),
+    "ehyb_bilu_apply_step": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, _vp]),
+    "ehyb_gmres_bilu": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _ip, _dp]),
+    "ehyb_bicgstab_bilu": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_bicgstab_bilu_multi": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _ip, _dp]),
+    "ehyb_bilu_gmres_combine_step": (C.c_int, [C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
+    "ehyb_bilu_gmres_add_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_layout": (C.c_int, [_P(BicgstabSlots)]),
     "ehyb_bicgstab_init_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehyb_bicgstab_dot_step": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp]),

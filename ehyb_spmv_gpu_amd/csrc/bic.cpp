@@ -16,9 +16,9 @@
 
 using namespace ehyb;
 
-namespace {
+int ehyb::bic_host_threads() { return std::max(1, std::min(omp_get_max_threads(), default_host_threads())); }
 
-int bic_host_threads() { return std::max(1, std::min(omp_get_max_threads(), default_host_threads())); }
+namespace {
 
 inline bool positive_finite(double v) { return v > 0 && std::isfinite(v); }
 
@@ -102,9 +102,41 @@ int ehyb::bic_group_log2(int threads, int w, int64_t entries)
     return gl;
 }
 
+// IC: L as stored, L^T -- the rows of L in rising order deal their entries to the columns, so a row of L^T rises too; a block's
+// entries of L^T lie where its entries of L do --, 1 / l_ii in both directions
 void ehyb::bic_build_streams(const ehyb_bic& f, int threads, BicStreams* out)
 {
     const int n = f.n, nb = f.nb;
+    std::vector<int64_t> tp((size_t)n + 1, 0);
+    std::vector<int32_t> tcols(f.cols.size());
+    std::vector<double> tvals(f.vals.size());
+#pragma omp parallel for schedule(dynamic, 1) num_threads(bic_host_threads())
+    for (int b = 0; b < nb; ++b) {
+        const int r0 = f.block_ptr[b], rows = f.block_ptr[b + 1] - r0;
+        int64_t* t = &tp[r0];  // t[p + 1]: the length of row p of L^T, then the row's end
+        for (int p = 0; p < rows; ++p)
+            for (int64_t e = f.row_ptr[(size_t)r0 + p]; e < f.row_ptr[(size_t)r0 + p + 1]; ++e) ++t[(size_t)f.cols[e] + 1];
+        std::vector<int64_t> at((size_t)rows);
+        int64_t run = f.row_ptr[r0];
+        for (int p = 0; p < rows; ++p) {
+            at[p] = run;
+            run += t[(size_t)p + 1];
+            t[(size_t)p + 1] = run;
+        }
+        for (int p = 0; p < rows; ++p)
+            for (int64_t e = f.row_ptr[(size_t)r0 + p]; e < f.row_ptr[(size_t)r0 + p + 1]; ++e) {
+                const int64_t q = at[f.cols[e]]++;
+                tcols[q] = p;
+                tvals[q] = f.vals[e];
+            }
+    }
+    const BicTriangle tri[2] = {{f.row_ptr.data(), f.cols.data(), f.vals.data(), f.dinv.data(), f.level_f.data()},
+                                {tp.data(), tcols.data(), tvals.data(), f.dinv.data(), f.level_b.data()}};
+    bic_build_streams(n, nb, f.block_ptr.data(), tri, threads, out);
+}
+
+void ehyb::bic_build_streams(int n, int nb, const int32_t* block_ptr, const BicTriangle (&tri)[2], int threads, BicStreams* out)
+{
     out->threads = threads;
     out->blocks.assign((size_t)nb, BicBlock{});
     out->meta.assign((size_t)2 * n, 0);
@@ -118,31 +150,15 @@ void ehyb::bic_build_streams(const ehyb_bic& f, int threads, BicStreams* out)
     std::vector<Part> parts((size_t)nb);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(bic_host_threads())
     for (int b = 0; b < nb; ++b) {
-        const int r0 = f.block_ptr[b], rows = f.block_ptr[b + 1] - r0;
+        const int r0 = block_ptr[b], rows = block_ptr[b + 1] - r0;
         Part& P = parts[b];
-        // the rows of L^T: the rows of L in rising order deal their entries to the columns, so a row of L^T rises too
-        std::vector<int64_t> tp((size_t)rows + 1, 0);
-        for (int p = 0; p < rows; ++p)
-            for (int64_t e = f.row_ptr[(size_t)r0 + p]; e < f.row_ptr[(size_t)r0 + p + 1]; ++e) ++tp[(size_t)f.cols[e] + 1];
-        for (int p = 0; p < rows; ++p) tp[(size_t)p + 1] += tp[p];
-        std::vector<int32_t> tcols((size_t)tp[rows]);
-        std::vector<double> tvals((size_t)tp[rows]);
-        {
-            std::vector<int64_t> at(tp.begin(), tp.end() - 1);
-            for (int p = 0; p < rows; ++p)
-                for (int64_t e = f.row_ptr[(size_t)r0 + p]; e < f.row_ptr[(size_t)r0 + p + 1]; ++e) {
-                    const int64_t q = at[f.cols[e]]++;
-                    tcols[q] = p;
-                    tvals[q] = f.vals[e];
-                }
-        }
         BicBlock& B = out->blocks[b];
         B.row0 = r0, B.rows = rows;
         for (int dir = 0; dir < 2; ++dir) {
-            const int64_t* rp = dir == 0 ? &f.row_ptr[r0] : tp.data();
-            const int32_t* cl = dir == 0 ? f.cols.data() : tcols.data();
-            const double* vl = dir == 0 ? f.vals.data() : tvals.data();
-            const int32_t* level = dir == 0 ? &f.level_f[r0] : &f.level_b[r0];
+            const int64_t* rp = tri[dir].row_ptr + r0;
+            const int32_t* cl = tri[dir].cols;
+            const double* vl = tri[dir].vals;
+            const int32_t* level = tri[dir].level + r0;
             int nlev = 0;
             for (int p = 0; p < rows; ++p) nlev = std::max(nlev, level[p] + 1);
             B.nlev[dir] = nlev;
@@ -189,7 +205,7 @@ void ehyb::bic_build_streams(const ehyb_bic& f, int threads, BicStreams* out)
                 for (int r = 0; r < w; ++r) {
                     const int p = ord[at + r];
                     out->meta[slot + r] = (uint32_t)p | (uint32_t)len_of(p) << 16;
-                    out->dinv[slot + r] = f.dinv[(size_t)r0 + p];
+                    out->dinv[slot + r] = tri[dir].dinv[(size_t)r0 + p];
                 }
                 slot += w, at += w;
                 P.cost += 8;  // a barrier, a few waves' worth of passes
@@ -224,12 +240,9 @@ void ehyb::bic_build_streams(const ehyb_bic& f, int threads, BicStreams* out)
 }
 
 // ------------------------------------------------------------------ the object
-extern "C" int ehyb_bic_create_host(const matrixCOO* m, int block_rows, int order, ehyb_bic** out)
+// the checks of *_create_host on the matrix, after the null pointers
+int ehyb::bic_check_matrix(const char* who, const matrixCOO* m, int block_rows, int order)
 {
-    const char* who = "ehyb_bic_create_host";
-    clear_error();
-    if (!m || !m->rowIdx || !m->J || !m->V || m->dimension < 1 || !out) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
-    *out = nullptr;
     if (block_rows < 0) EHYB_FAIL(EHYB_ERR_ARG, "%s: block_rows %d (0: whole partitions)", who, block_rows);
     if (order != EHYB_BIC_ORDER_STORED && order != EHYB_BIC_ORDER_COLOUR) EHYB_FAIL(EHYB_ERR_ARG, "%s: order %d (0 or 1)", who, order);
     const int n = m->dimension;
@@ -243,23 +256,81 @@ extern "C" int ehyb_bic_create_host(const matrixCOO* m, int block_rows, int orde
         for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
             if (m->J[e] < 0 || m->J[e] >= n) EHYB_FAIL(EHYB_ERR_ARG, "%s: row %d holds column %d, outside the matrix", who, i, m->J[e]);
     }
-    std::unique_ptr<ehyb_bic> f(new (std::nothrow) ehyb_bic);
-    if (!f) EHYB_FAIL(EHYB_ERR_ALLOC, "%s: out of memory", who);
-    f->n = n;
-    f->order = order;
-    const int threads = bic_host_threads();
+    return EHYB_OK;
+}
 
-    // ---- blocks: every partition in ceil(rows / cap) runs of nearly equal length, the first runs one longer
+// blocks: every partition in ceil(rows / cap) runs of nearly equal length, the first runs one longer
+void ehyb::bic_cut_blocks(const matrixCOO* m, int block_rows, ehyb_bic* f)
+{
     const int cap = block_rows > 0 ? std::min(block_rows, EHYB_BIC_MAX_BLOCK) : EHYB_BIC_MAX_BLOCK;
-    f->block_ptr.push_back(0);
+    f->block_ptr.assign(1, 0);
     for (int p = 0; p < m->nParts; ++p) {
         const int rows = m->partBoundary[p + 1] - m->partBoundary[p];
         if (rows < 1) continue;
         const int runs = (rows + cap - 1) / cap, base = rows / runs, longer = rows % runs;
         for (int r = 0; r < runs; ++r) f->block_ptr.push_back(f->block_ptr.back() + base + (r < longer ? 1 : 0));
     }
-    const int nb = f->nb = (int)f->block_ptr.size() - 1;
-    for (int b = 0; b < nb; ++b) f->max_block = std::max(f->max_block, f->block_ptr[b + 1] - f->block_ptr[b]);
+    f->nb = (int)f->block_ptr.size() - 1;
+    f->max_block = 0;
+    for (int b = 0; b < f->nb; ++b) f->max_block = std::max(f->max_block, f->block_ptr[b + 1] - f->block_ptr[b]);
+}
+
+// the local order of the block of rows r0 .. r1 - 1
+void ehyb::bic_block_order(const matrixCOO* m, int r0, int r1, int order, bool both_triangles, int32_t* perm, int32_t* pos)
+{
+    const int rows = r1 - r0;
+    if (order == EHYB_BIC_ORDER_STORED) {
+        for (int i = r0; i < r1; ++i) perm[i] = i, pos[i] = i - r0;
+        return;
+    }
+    // the block's graph, every edge both ways -- from the lower triangle, or from both (an edge stored in both is then listed
+    // twice, which the colouring does not see); rows in rising order take the smallest colour no coloured neighbour holds
+    const auto edge = [&](int i, int j) { return j >= r0 && (both_triangles ? j < r1 && j != i : j < i); };
+    std::vector<int32_t> deg((size_t)rows + 1, 0);
+    for (int i = r0; i < r1; ++i)
+        for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
+            if (edge(i, m->J[e])) ++deg[(size_t)(i - r0) + 1], ++deg[(size_t)(m->J[e] - r0) + 1];
+    for (int p = 0; p < rows; ++p) deg[(size_t)p + 1] += deg[p];
+    std::vector<int32_t> adj((size_t)deg[rows]), at(deg.begin(), deg.end() - 1);
+    for (int i = r0; i < r1; ++i)
+        for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
+            if (edge(i, m->J[e])) adj[at[i - r0]++] = m->J[e] - r0, adj[at[m->J[e] - r0]++] = i - r0;
+    // (a row may have more neighbours than the block has rows when edges are listed twice: colours stay below rows all the same)
+    std::vector<int32_t> colour((size_t)rows, -1), mark((size_t)rows + 1, -1), count;
+    for (int p = 0; p < rows; ++p) {
+        for (int e = deg[p]; e < deg[p + 1]; ++e)
+            if (colour[adj[e]] >= 0) mark[colour[adj[e]]] = p;
+        int c = 0;
+        while (mark[c] == p) ++c;
+        colour[p] = c;
+        if (c >= (int)count.size()) count.resize((size_t)c + 1, 0);
+        ++count[c];
+    }
+    std::vector<int32_t> start(count.size() + 1, 0);
+    for (size_t c = 0; c < count.size(); ++c) start[c + 1] = start[c] + count[c];
+    for (int p = 0; p < rows; ++p) {  // positions by (colour, row)
+        const int to = start[colour[p]]++;
+        perm[(size_t)r0 + to] = r0 + p;
+        pos[(size_t)r0 + p] = to;
+    }
+}
+
+extern "C" int ehyb_bic_create_host(const matrixCOO* m, int block_rows, int order, ehyb_bic** out)
+{
+    const char* who = "ehyb_bic_create_host";
+    clear_error();
+    if (!m || !m->rowIdx || !m->J || !m->V || m->dimension < 1 || !out) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    const int rc = bic_check_matrix(who, m, block_rows, order);
+    if (rc != EHYB_OK) return rc;
+    const int n = m->dimension;
+    std::unique_ptr<ehyb_bic> f(new (std::nothrow) ehyb_bic);
+    if (!f) EHYB_FAIL(EHYB_ERR_ALLOC, "%s: out of memory", who);
+    f->n = n;
+    f->order = order;
+    const int threads = bic_host_threads();
+    bic_cut_blocks(m, block_rows, f.get());
+    const int nb = f->nb;
 
     // ---- the local order and the lengths of the rows of tril(A_b) in it
     f->perm.resize((size_t)n);
@@ -267,39 +338,8 @@ extern "C" int ehyb_bic_create_host(const matrixCOO* m, int block_rows, int orde
     f->row_ptr.assign((size_t)n + 1, 0);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (int b = 0; b < nb; ++b) {
-        const int r0 = f->block_ptr[b], r1 = f->block_ptr[b + 1], rows = r1 - r0;
-        if (order == EHYB_BIC_ORDER_STORED) {
-            for (int i = r0; i < r1; ++i) f->perm[i] = i, pos[i] = i - r0;
-        } else {
-            // the block's graph from the lower triangle, both ways; rows in rising order take the smallest colour no coloured
-            // neighbour holds (the neighbours coloured so far are the lower ones: j < i)
-            std::vector<int32_t> deg((size_t)rows + 1, 0);
-            for (int i = r0; i < r1; ++i)
-                for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
-                    if (m->J[e] >= r0 && m->J[e] < i) ++deg[(size_t)(i - r0) + 1], ++deg[(size_t)(m->J[e] - r0) + 1];
-            for (int p = 0; p < rows; ++p) deg[(size_t)p + 1] += deg[p];
-            std::vector<int32_t> adj((size_t)deg[rows]), at(deg.begin(), deg.end() - 1);
-            for (int i = r0; i < r1; ++i)
-                for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
-                    if (m->J[e] >= r0 && m->J[e] < i) adj[at[i - r0]++] = m->J[e] - r0, adj[at[m->J[e] - r0]++] = i - r0;
-            std::vector<int32_t> colour((size_t)rows, -1), mark((size_t)rows + 1, -1), count;
-            for (int p = 0; p < rows; ++p) {
-                for (int e = deg[p]; e < deg[p + 1]; ++e)
-                    if (colour[adj[e]] >= 0) mark[colour[adj[e]]] = p;
-                int c = 0;
-                while (mark[c] == p) ++c;
-                colour[p] = c;
-                if (c >= (int)count.size()) count.resize((size_t)c + 1, 0);
-                ++count[c];
-            }
-            std::vector<int32_t> start(count.size() + 1, 0);
-            for (size_t c = 0; c < count.size(); ++c) start[c + 1] = start[c] + count[c];
-            for (int p = 0; p < rows; ++p) {  // positions by (colour, row)
-                const int to = start[colour[p]]++;
-                f->perm[(size_t)r0 + to] = r0 + p;
-                pos[(size_t)r0 + p] = to;
-            }
-        }
+        const int r0 = f->block_ptr[b], r1 = f->block_ptr[b + 1];
+        bic_block_order(m, r0, r1, order, false, f->perm.data(), pos.data());
         for (int i = r0; i < r1; ++i)
             for (int e = m->rowIdx[i]; e < m->rowIdx[i + 1]; ++e)
                 if (m->J[e] >= r0 && m->J[e] < i) ++f->row_ptr[(size_t)r0 + std::max(pos[i], pos[m->J[e]]) + 1];

@@ -7,6 +7,8 @@
 
 #include "ehyb.h"
 
+struct ehyb_bic;
+
 namespace ehyb {
 
 // What the apply kernel reads of one block.  Direction 0: the forward solve with L, 1: the backward solve with L^T.
@@ -48,8 +50,37 @@ constexpr uint16_t kBicNoEntry = 0xFFFF;
 // the workgroup size for a longest block, and the lanes per row (log2) of a level of w rows whose lengths add up to `entries`
 int bic_threads(int longest_block);
 int bic_group_log2(int threads, int w, int64_t entries);
-// the streams of f for workgroups of `threads` (bic_threads(f.max_block) at upload)
+// One triangle of a block-diagonal factor, strictly off the diagonal, in CSR form over all positions (row_ptr [n + 1], cols
+// block-local and rising in a row), the number its solve multiplies a row by (dinv [n]), and the levels of its solve (level [n]).
+struct BicTriangle {
+    const int64_t* row_ptr;
+    const int32_t* cols;
+    const double* vals;
+    const double* dinv;
+    const int32_t* level;
+};
+// The streams for workgroups of `threads` (bic_threads(longest block) at upload): tri[0] the strictly lower triangle of the forward
+// solve, tri[1] the strictly upper one of the backward solve, each  x = (x - sum v x[col]) * dinv.  IC passes L, L^T and 1 / l_ii
+// twice (the overload on ehyb_bic), ILU passes L with ones and U with 1 / u_ii (bilu.cpp).
+void bic_build_streams(int n, int nb, const int32_t* block_ptr, const BicTriangle (&tri)[2], int threads, BicStreams* out);
 void bic_build_streams(const ehyb_bic& f, int threads, BicStreams* out);
+
+// What ehyb_bic and ehyb_bilu share of the host side (bic.cpp): the checks of *_create_host on the matrix, its blocks (block_ptr,
+// nb, max_block of f), and the local order of one block -- perm[r0 .. r1) and pos[r0 .. r1), the block-local position of a row.
+// both_triangles: the colouring counts every in-block off-diagonal entry as an edge (the pattern of A_b + A_b^T), not only
+// those of the lower triangle (a symmetric matrix: the same graph).
+int bic_check_matrix(const char* who, const matrixCOO* m, int block_rows, int order);
+void bic_cut_blocks(const matrixCOO* m, int block_rows, ehyb_bic* f);
+void bic_block_order(const matrixCOO* m, int r0, int r1, int order, bool both_triangles, int32_t* perm, int32_t* pos);
+int bic_host_threads();
+
+// What they share of the device side (ehyb_bic.hip): the streams S of f's blocks onto the device (f->perm with them), the apply
+// on them -- k columns in passes of ehyb_bic_max_k; active NULL: every column, else column c is served where the int at
+// active[c * astride] is nonzero (inverted: zero -- a solver's status word, 0 while the column runs) --, and the release.
+int bic_upload_streams(const char* who, ehyb_bic* f, const BicStreams& S);
+int bic_apply_columns(const ehyb_bic* f, void* stream, const double* R, long long ldr, double* Z, long long ldz, int k, const int* active,
+                      int astride = 1, bool inverted = false);
+void bic_release_device(ehyb_bic* f);
 
 }  // namespace ehyb
 

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "bic.h"
+#include "bilu.h"
 #include "pcg_loop.h"
 #include "vec_walk.h"
 
@@ -42,7 +43,8 @@ __global__ __launch_bounds__(kBicMaxThreads) void ehyb_bic_apply_kernel(int n, c
                                                                         const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ meta,
                                                                         const double* __restrict__ dinv, const uint16_t* __restrict__ cols,
                                                                         const double* __restrict__ vals, const double* __restrict__ R, long long ldr,
-                                                                        double* __restrict__ Z, long long ldz, const int* __restrict__ active, int c0)
+                                                                        double* __restrict__ Z, long long ldz, const int* __restrict__ active, int astride,
+                                                                        int inverted, int c0)
 {
     extern __shared__ __attribute__((aligned(16))) double xs[];
     const BicBlock B = blocks[order[blockIdx.x]];
@@ -52,7 +54,9 @@ __global__ __launch_bounds__(kBicMaxThreads) void ehyb_bic_apply_kernel(int n, c
     bool any = false;
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-        on[c] = !active || active[c0 + c] != 0;
+        // column c's flag: the word at active[(c0 + c) * astride], on where it is nonzero -- or, inverted, where it is zero (a
+        // solver's status word, 0 while the column runs)
+        on[c] = !active || (active[(size_t)(c0 + c) * astride] != 0) != (inverted != 0);
         any = any || on[c];
     }
     if (!any) return;  // (the same in every thread)
@@ -167,28 +171,35 @@ void launch_rz(int n, int grid, hipStream_t st, const double* R, const double* Z
 }
 
 template <int K>
-void launch_apply(const ehyb_bic* f, hipStream_t st, const double* R, long long ldr, double* Z, long long ldz, const int* active, int c0)
+void launch_apply(const ehyb_bic* f, hipStream_t st, const double* R, long long ldr, double* Z, long long ldz, const int* active, int astride, int inverted,
+                  int c0)
 {
     const size_t lds = (size_t)f->max_block * K * sizeof(double);
     hipLaunchKernelGGL(ehyb_bic_apply_kernel<K>, dim3(f->nb), dim3(f->threads), lds, st, f->n, f->d_blocks, f->d_order, f->d_perm, f->d_rounds, f->d_cnt, f->d_meta,
-                       f->d_dinv, f->d_cols, f->d_vals, R, ldr, Z, ldz, active, c0);
+                       f->d_dinv, f->d_cols, f->d_vals, R, ldr, Z, ldz, active, astride, inverted, c0);
 }
 
-// Z = (L L^T)^-1 R for k columns, in passes of ehyb_bic_max_k columns
-int apply_columns(const ehyb_bic* f, hipStream_t st, const double* R, long long ldr, double* Z, long long ldz, int k, const int* active)
+}  // namespace
+
+// Z = (L L^T)^-1 R -- or (L U)^-1 R: whatever the streams hold -- for k columns, in passes of ehyb_bic_max_k columns
+int ehyb::bic_apply_columns(const ehyb_bic* f, void* stream, const double* R, long long ldr, double* Z, long long ldz, int k, const int* active,
+                            int astride, bool inverted)
 {
+    const hipStream_t st = (hipStream_t)stream;
     const int kmax = ehyb_bic_max_k(f);
     for (int c0 = 0; c0 < k; c0 += kmax) {
         switch (std::min(kmax, k - c0)) {
-        case 1: launch_apply<1>(f, st, R, ldr, Z, ldz, active, c0); break;
-        case 2: launch_apply<2>(f, st, R, ldr, Z, ldz, active, c0); break;
-        case 3: launch_apply<3>(f, st, R, ldr, Z, ldz, active, c0); break;
-        default: launch_apply<4>(f, st, R, ldr, Z, ldz, active, c0); break;
+        case 1: launch_apply<1>(f, st, R, ldr, Z, ldz, active, astride, inverted, c0); break;
+        case 2: launch_apply<2>(f, st, R, ldr, Z, ldz, active, astride, inverted, c0); break;
+        case 3: launch_apply<3>(f, st, R, ldr, Z, ldz, active, astride, inverted, c0); break;
+        default: launch_apply<4>(f, st, R, ldr, Z, ldz, active, astride, inverted, c0); break;
         }
     }
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }
+
+namespace {
 
 template <typename T>
 hipError_t to_device(T** d, const T* h, size_t count)
@@ -198,7 +209,9 @@ hipError_t to_device(T** d, const T* h, size_t count)
     return e;
 }
 
-void release_device(ehyb_bic* f)
+}  // namespace
+
+void ehyb::bic_release_device(ehyb_bic* f)
 {
     for (void* p : {(void*)f->d_blocks, (void*)f->d_order, (void*)f->d_perm, (void*)f->d_rounds, (void*)f->d_cnt, (void*)f->d_meta, (void*)f->d_dinv, (void*)f->d_cols,
                     (void*)f->d_vals})
@@ -211,42 +224,8 @@ void release_device(ehyb_bic* f)
     f->uploaded = false;
 }
 
-// in this order: what the plain solver rejects (done by the caller), the object, then the uploads
-int bic_args(const char* who, const ehyb_plan* P, const ehyb_bic* f)
+int ehyb::bic_upload_streams(const char* who, ehyb_bic* f, const BicStreams& S)
 {
-    if (!f) EHYB_FAIL(EHYB_ERR_ARG, "%s: null bic object", who);
-    if (f->n != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "%s: the bic object has %d rows, the plan %d", who, f->n, P->host.n_cols);
-    int rc = solve_uploaded(who, P);
-    if (rc != EHYB_OK) return rc;
-    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: bic object not uploaded", who);
-    return EHYB_OK;
-}
-
-// The one driver: the loop of pcg_loop.h, one multiply with A per iteration (walks alternating), the two solves and the
-// partials of r.z between update and direction.  The arguments are checked.
-int bic_solve(const char* who, ehyb_plan* P, ehyb_bic* f, const double* B, int64_t ldb, double* X, int64_t ldx, int k, int max_iter, double rtol,
-              int check_every, void* stream, int* iters_done, double* rel_residual)
-{
-    auto precondition = [&](const PcgState& S, int, int rz) -> int {
-        const int rc = apply_columns(f, S.st, S.R, S.n, S.Z, S.n, k, S.active);
-        if (rc != EHYB_OK) return rc;
-        for_each_group(k, [&](auto K, int c0) { launch_rz<decltype(K)::value>(S.n, S.grid, S.st, S.R, S.Z, S.s, S.active, c0, rz); });
-        return EHYB_OK;
-    };
-    return pcg_solve(
-        who, "is the matrix symmetric positive definite?", P, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done, rel_residual, {},
-        [](const PcgState&) { return EHYB_OK; }, [](int it) { return walk_of(it); }, precondition);
-}
-
-}  // namespace
-
-extern "C" int ehyb_bic_upload(ehyb_bic* f)
-{
-    clear_error();
-    if (!f) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bic_upload: null argument");
-    if (f->uploaded) return EHYB_OK;
-    BicStreams S;
-    bic_build_streams(*f, bic_threads(f->max_block), &S);
     f->threads = S.threads;
     f->stream_bytes = S.bytes();
     f->stream_entries = S.real_entries;
@@ -267,47 +246,134 @@ extern "C" int ehyb_bic_upload(ehyb_bic* f)
     if (e == hipSuccess) e = to_device(&f->d_cols, S.cols.data(), S.cols.size());
     if (e == hipSuccess) e = to_device(&f->d_vals, S.vals.data(), S.vals.size());
     if (e != hipSuccess) {
-        release_device(f);
-        EHYB_FAIL(EHYB_ERR_HIP, "ehyb_bic_upload: %s", hipGetErrorString(e));
+        bic_release_device(f);
+        EHYB_FAIL(EHYB_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     f->uploaded = true;
     return EHYB_OK;
 }
 
+namespace {
+
+// in this order: what the plain solver rejects (done by the caller), the object, then the uploads
+int bic_args(const char* who, const ehyb_plan* P, const ehyb_bic* f)
+{
+    if (!f) EHYB_FAIL(EHYB_ERR_ARG, "%s: null bic object", who);
+    if (f->n != P->host.n_cols) EHYB_FAIL(EHYB_ERR_ARG, "%s: the bic object has %d rows, the plan %d", who, f->n, P->host.n_cols);
+    int rc = solve_uploaded(who, P);
+    if (rc != EHYB_OK) return rc;
+    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: bic object not uploaded", who);
+    return EHYB_OK;
+}
+
+// The one driver: the loop of pcg_loop.h, one multiply with A per iteration (walks alternating), the two solves and the
+// partials of r.z between update and direction.  The arguments are checked.
+int bic_solve(const char* who, ehyb_plan* P, ehyb_bic* f, const double* B, int64_t ldb, double* X, int64_t ldx, int k, int max_iter, double rtol,
+              int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    auto precondition = [&](const PcgState& S, int, int rz) -> int {
+        const int rc = bic_apply_columns(f, S.st, S.R, S.n, S.Z, S.n, k, S.active);
+        if (rc != EHYB_OK) return rc;
+        for_each_group(k, [&](auto K, int c0) { launch_rz<decltype(K)::value>(S.n, S.grid, S.st, S.R, S.Z, S.s, S.active, c0, rz); });
+        return EHYB_OK;
+    };
+    return pcg_solve(
+        who, "is the matrix symmetric positive definite?", P, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done, rel_residual, {},
+        [](const PcgState&) { return EHYB_OK; }, [](int it) { return walk_of(it); }, precondition);
+}
+
+}  // namespace
+
+extern "C" int ehyb_bic_upload(ehyb_bic* f)
+{
+    clear_error();
+    if (!f) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bic_upload: null argument");
+    if (f->uploaded) return EHYB_OK;
+    BicStreams S;
+    bic_build_streams(*f, bic_threads(f->max_block), &S);
+    return bic_upload_streams("ehyb_bic_upload", f, S);
+}
+
 extern "C" void ehyb_bic_destroy(ehyb_bic* f)
 {
     if (!f) return;
-    if (f->uploaded) release_device(f);
+    if (f->uploaded) bic_release_device(f);
     delete f;
 }
 
-extern "C" int ehyb_bic_stream_info(const ehyb_bic* f, int64_t* bytes, int64_t* entries, int* threads)
+namespace {
+
+// the three entry points both objects have, on the part they share; who: the entry point, what: the object's name in messages
+int stream_info_of(const char* who, const char* what, const ehyb_bic* f, int64_t* bytes, int64_t* entries, int* threads)
 {
     clear_error();
-    if (!f || !bytes || !entries || !threads) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bic_stream_info: null argument");
-    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "ehyb_bic_stream_info: bic object not uploaded");
+    if (!f || !bytes || !entries || !threads) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
+    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: %s object not uploaded", who, what);
     *bytes = f->stream_bytes, *entries = f->stream_entries, *threads = f->threads;
     return EHYB_OK;
 }
 
+// step: the flags are required
+int apply_of(const char* who, const char* what, const ehyb_bic* f, const double* R, int64_t ldr, double* Z, int64_t ldz, int k, bool step, const int* active,
+             void* stream)
+{
+    clear_error();
+    if (!f || !R || !Z || (step && !active)) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
+    if (k < 1 || ldr < f->n || ldz < f->n) EHYB_FAIL(EHYB_ERR_ARG, "%s: k = %d, ldr = %lld, ldz = %lld (k >= 1, both at least n = %d)", who, k, (long long)ldr, (long long)ldz, f->n);
+    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: %s object not uploaded", who, what);
+    return bic_apply_columns(f, stream, R, ldr, Z, ldz, k, active);
+}
+
+}  // namespace
+
+extern "C" int ehyb_bic_stream_info(const ehyb_bic* f, int64_t* bytes, int64_t* entries, int* threads)
+{
+    return stream_info_of("ehyb_bic_stream_info", "bic", f, bytes, entries, threads);
+}
+
 extern "C" int ehyb_bic_apply(ehyb_bic* f, const double* R, int64_t ldr, double* Z, int64_t ldz, int k, void* stream)
 {
-    const char* who = "ehyb_bic_apply";
-    clear_error();
-    if (!f || !R || !Z) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
-    if (k < 1 || ldr < f->n || ldz < f->n) EHYB_FAIL(EHYB_ERR_ARG, "%s: k = %d, ldr = %lld, ldz = %lld (k >= 1, both at least n = %d)", who, k, (long long)ldr, (long long)ldz, f->n);
-    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: bic object not uploaded", who);
-    return apply_columns(f, (hipStream_t)stream, R, ldr, Z, ldz, k, nullptr);
+    return apply_of("ehyb_bic_apply", "bic", f, R, ldr, Z, ldz, k, false, nullptr, stream);
 }
 
 extern "C" int ehyb_bic_apply_step(ehyb_bic* f, const double* R, int64_t ldr, double* Z, int64_t ldz, int k, const int* active, void* stream)
 {
-    const char* who = "ehyb_bic_apply_step";
+    return apply_of("ehyb_bic_apply_step", "bic", f, R, ldr, Z, ldz, k, true, active, stream);
+}
+
+// ------------------------------------------------------------------ ehyb_bilu: the same device side, fed with L and U (bilu.cpp)
+extern "C" int ehyb_bilu_upload(ehyb_bilu* f)
+{
     clear_error();
-    if (!f || !R || !Z || !active) EHYB_FAIL(EHYB_ERR_ARG, "%s: null argument", who);
-    if (k < 1 || ldr < f->n || ldz < f->n) EHYB_FAIL(EHYB_ERR_ARG, "%s: k = %d, ldr = %lld, ldz = %lld (k >= 1, both at least n = %d)", who, k, (long long)ldr, (long long)ldz, f->n);
-    if (!f->uploaded) EHYB_FAIL(EHYB_ERR_STATE, "%s: bic object not uploaded", who);
-    return apply_columns(f, (hipStream_t)stream, R, ldr, Z, ldz, k, active);
+    if (!f) EHYB_FAIL(EHYB_ERR_ARG, "ehyb_bilu_upload: null argument");
+    if (f->core.uploaded) return EHYB_OK;
+    BicTriangle tri[2];
+    bilu_triangles(*f, tri);
+    BicStreams S;
+    bic_build_streams(f->core.n, f->core.nb, f->core.block_ptr.data(), tri, bic_threads(f->core.max_block), &S);
+    return bic_upload_streams("ehyb_bilu_upload", &f->core, S);
+}
+
+extern "C" void ehyb_bilu_destroy(ehyb_bilu* f)
+{
+    if (!f) return;
+    if (f->core.uploaded) bic_release_device(&f->core);
+    delete f;
+}
+
+extern "C" int ehyb_bilu_stream_info(const ehyb_bilu* f, int64_t* bytes, int64_t* entries, int* threads)
+{
+    return stream_info_of("ehyb_bilu_stream_info", "bilu", f ? &f->core : nullptr, bytes, entries, threads);
+}
+
+extern "C" int ehyb_bilu_apply(ehyb_bilu* f, const double* R, int64_t ldr, double* Z, int64_t ldz, int k, void* stream)
+{
+    return apply_of("ehyb_bilu_apply", "bilu", f ? &f->core : nullptr, R, ldr, Z, ldz, k, false, nullptr, stream);
+}
+
+extern "C" int ehyb_bilu_apply_step(ehyb_bilu* f, const double* R, int64_t ldr, double* Z, int64_t ldz, int k, const int* active, void* stream)
+{
+    return apply_of("ehyb_bilu_apply_step", "bilu", f ? &f->core : nullptr, R, ldr, Z, ldz, k, true, active, stream);
 }
 
 extern "C" int ehyb_pcg_bic(ehyb_plan* P, ehyb_bic* f, const double* b, double* x, int max_iter, double rtol, int check_every, void* stream,

@@ -31,6 +31,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bilu.h"
 #include "ehyb_internal.h"
 #include "solve_loop.h"
 #include "vec_walk.h"
@@ -390,14 +391,14 @@ void launch_after_v(int grid, hipStream_t st, int n, const double* r, const doub
     hipLaunchKernelGGL((bicg_s_kernel<K, s_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, sv, sh, s, flags, c0, cur);
 }
 
-// ... and after t = A s^
+// ... and after t = A s^ (ph: the p^ of the update, p: what the direction kernel advances -- the same vector but for ehyb_bicgstab_bilu)
 template <int K>
-void launch_after_t(int grid, hipStream_t st, int n, double* p, const double* sh, const double* sv, const double* t, const double* rh,
+void launch_after_t(int grid, hipStream_t st, int n, const double* ph, double* p, const double* sh, const double* sv, const double* t, const double* rh,
                     const double* v, const double* dinv, double* x, long long ldx, double* r, double* s, int* flags, int c0, int cur,
                     double thr)
 {
     hipLaunchKernelGGL((bicg_dot2_kernel<K, kDotU>), dim3(grid), dim3(kThreads), 0, st, n, t, sv, s, flags, c0);
-    hipLaunchKernelGGL((bicg_update_kernel<K, update_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, p, sh, sv, t, rh, x, ldx, r, s,
+    hipLaunchKernelGGL((bicg_update_kernel<K, update_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, ph, sh, sv, t, rh, x, ldx, r, s,
                        flags, c0, cur, thr);
     hipLaunchKernelGGL((bicg_direction_kernel<K, direction_depth(K)>), dim3(grid), dim3(kThreads), 0, st, n, r, v, dinv, p, s, flags,
                        c0, cur, thr);
@@ -409,7 +410,12 @@ void launch_after_t(int grid, hipStream_t st, int n, double* p, const double* sh
 // goes on while any column is running.  A column that has nothing to do at the start, or a non-finite start, gets its status
 // planted before the first burst -- where some column does start and some does not, so never at k = 1.  The entry points have
 // made their checks (solve_loop.h); who: the entry point, name_column: whether the breakdown text says which column.
-int bicgstab_solve(const char* who, bool name_column, ehyb_plan* P, const double* dinv, const double* B, int64_t ldb, double* X,
+//   M (ehyb_bicgstab_bilu): the textbook right-preconditioned form with a general M.  The kernels run with dinv = NULL, which makes
+// them the unpreconditioned recurrences -- p = r + beta (p - omega v) on the unpreconditioned p, s = r - alpha v --, and the apply
+// kernel of ehyb_bic makes p^ = M^-1 p (one more vector) before v = A p^ and s^ = M^-1 s (over the copy of s the s kernel left in
+// s^) before t = A s^; the update kernel reads p^ and s^ as ever.  The apply reads the columns' status words as the vector kernels
+// do: a stopped column is skipped, its p^ and s^ stay.
+int bicgstab_solve(const char* who, bool name_column, ehyb_plan* P, const double* dinv, const ehyb_bilu* M, const double* B, int64_t ldb, double* X,
                    int64_t ldx, int k, int max_iter, double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
 {
     const int n = P->host.n_cols;
@@ -418,6 +424,8 @@ int bicgstab_solve(const char* who, bool name_column, ehyb_plan* P, const double
     double *r, *rh, *p, *v, *sv, *sh, *t, *s;
     // two ints per column behind the k sets of slots: one double each
     HIP_TRY(L.begin(stream, {&r, &rh, &p, &v, &sv, &sh, &t}, (size_t)n * k, &s, (size_t)k * B_COUNT, k));
+    double* ph = p;
+    if (M) HIP_TRY(L.more(&ph, (size_t)n * k));
     const size_t flags_at = (size_t)k * B_COUNT * kMaxGrid;
     int* flags = (int*)(s + flags_at);
     const hipStream_t st = L.st;
@@ -454,12 +462,14 @@ int bicgstab_solve(const char* who, bool name_column, ehyb_plan* P, const double
     rc = L.run(
         P, max_iter, it, [&] { return n_running > 0; },
         [&](int cur, bool) -> int {
-            int e = ehyb_spmm(P, p, n, v, n, k, st, EHYB_WALK_FIRST_TO_LAST);  // V = A P^, stopped columns included
+            int e = M ? bic_apply_columns(&M->core, st, p, n, ph, n, k, flags + F_STATUS, F_COUNT, true) : EHYB_OK;  // P^ = M^-1 P
             if (e != EHYB_OK) return e;
+            if ((e = ehyb_spmm(P, ph, n, v, n, k, st, EHYB_WALK_FIRST_TO_LAST)) != EHYB_OK) return e;  // V = A P^, stopped columns included
             for_each_group(k, [&](auto K, int c0) { launch_after_v<decltype(K)::value>(grid, st, n, r, rh, v, dinv, sv, sh, s, flags, c0, cur); });
+            if (M && (e = bic_apply_columns(&M->core, st, sv, n, sh, n, k, flags + F_STATUS, F_COUNT, true)) != EHYB_OK) return e;  // S^ = M^-1 S
             if ((e = ehyb_spmm(P, sh, n, t, n, k, st, EHYB_WALK_LAST_TO_FIRST)) != EHYB_OK) return e;  // T = A S^
             for_each_group(k, [&](auto K, int c0) {
-                launch_after_t<decltype(K)::value>(grid, st, n, p, sh, sv, t, rh, v, dinv, X, ldx, r, s, flags, c0, cur, thr);
+                launch_after_t<decltype(K)::value>(grid, st, n, ph, p, sh, sv, t, rh, v, dinv, X, ldx, r, s, flags, c0, cur, thr);
             });
             return EHYB_OK;
         },
@@ -494,7 +504,7 @@ extern "C" int ehyb_bicgstab(ehyb_plan* P, const double* dinv, const double* b, 
     const int rc = solve_prologue("ehyb_bicgstab", P, b && x, max_iter, rtol);
     if (rc != EHYB_OK) return rc;
     const int n = P->host.n_cols;
-    return bicgstab_solve("ehyb_bicgstab", false, P, dinv, b, n, x, n, 1, max_iter, rtol, check_every, stream, iters_done, rel_residual);
+    return bicgstab_solve("ehyb_bicgstab", false, P, dinv, nullptr, b, n, x, n, 1, max_iter, rtol, check_every, stream, iters_done, rel_residual);
 }
 
 // k right-hand sides, two multiplies per iteration
@@ -503,8 +513,29 @@ extern "C" int ehyb_bicgstab_multi(ehyb_plan* P, const double* dinv, const doubl
 {
     const int rc = multi_prologue("ehyb_bicgstab_multi", P, B && X, ldb, ldx, k, max_iter, rtol);
     if (rc != EHYB_OK) return rc;
-    return bicgstab_solve("ehyb_bicgstab_multi", true, P, dinv, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done,
+    return bicgstab_solve("ehyb_bicgstab_multi", true, P, dinv, nullptr, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done,
                           rel_residual);
+}
+
+// right-preconditioned with the block ILU(0) of `bilu`; the checks: what ehyb_bicgstab(_multi) rejects, the factor, the uploads
+extern "C" int ehyb_bicgstab_bilu(ehyb_plan* P, ehyb_bilu* bilu, const double* b, double* x, int max_iter, double rtol, int check_every,
+                                  void* stream, int* iters_done, double* rel_residual)
+{
+    const char* who = "ehyb_bicgstab_bilu";
+    int rc = solve_args(who, P, b && x, max_iter, rtol);
+    if (rc != EHYB_OK || (rc = bilu_solver_args(who, P, bilu)) != EHYB_OK) return rc;
+    const int n = P->host.n_cols;
+    return bicgstab_solve(who, false, P, nullptr, bilu, b, n, x, n, 1, max_iter, rtol, check_every, stream, iters_done, rel_residual);
+}
+
+extern "C" int ehyb_bicgstab_bilu_multi(ehyb_plan* P, ehyb_bilu* bilu, const double* B, int64_t ldb, double* X, int64_t ldx, int k, int max_iter,
+                                        double rtol, int check_every, void* stream, int* iters_done, double* rel_residual)
+{
+    const char* who = "ehyb_bicgstab_bilu_multi";
+    int rc = multi_args(who, P, ldb, ldx, k);
+    if (rc == EHYB_OK) rc = solve_args(who, P, B && X, max_iter, rtol);
+    if (rc != EHYB_OK || (rc = bilu_solver_args(who, P, bilu)) != EHYB_OK) return rc;
+    return bicgstab_solve(who, true, P, nullptr, bilu, B, ldb, X, ldx, k, max_iter, rtol, check_every, stream, iters_done, rel_residual);
 }
 
 // ------------------------------------------------------------------ building blocks for a caller that owns the loop

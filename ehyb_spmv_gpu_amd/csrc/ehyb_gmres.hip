@@ -30,6 +30,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "bilu.h"
 #include "ehyb_internal.h"
 #include "gmres_device.h"
 #include "solve_loop.h"
@@ -177,6 +178,7 @@ __global__ __launch_bounds__(kThreads) void gmres_next_kernel(int n, long long l
             vv.x = wv.x / hn;
             vv.y = wv.y / hn;
             store2(v + i, vv);
+            if (!z) continue;  // (a preconditioner that reads v where it lies: ehyb_gmres_bilu)
             if (dinv) {
                 const double2 d = load2(dinv + i);
                 vv.x *= d.x;
@@ -186,17 +188,17 @@ __global__ __launch_bounds__(kThreads) void gmres_next_kernel(int n, long long l
         } else {
             const double vi = w[i] / hn;
             v[i] = vi;
-            z[i] = dinv ? vi * dinv[i] : vi;
+            if (z) z[i] = dinv ? vi * dinv[i] : vi;
         }
     }
 }
 
 // J = counter - counter at the cycle start; R y = g[0 .. J) by back substitution (column by column, every workgroup for itself,
 // the same order in each); x += M^-1 (sum_{i < J} y_i v_i), the sum in rising i.  Does not look at the status: the steps before
-// a stop are applied.
+// a stop are applied.  comb (ehyb_gmres_bilu): the combination sum y_i v_i goes there and x stays -- M^-1 and the addition follow.
 __global__ __launch_bounds__(kThreads) void gmres_solve_x_kernel(int n, long long ld_, const double* __restrict__ V,
                                                                  const double* __restrict__ dinv, double* __restrict__ x,
-                                                                 const double* __restrict__ tail)
+                                                                 const double* __restrict__ tail, double* __restrict__ comb)
 {
     __shared__ double r_sh[kM * kM], g_sh[kM], y_sh[kM];
     __shared__ int j_sh;
@@ -241,6 +243,10 @@ __global__ __launch_bounds__(kThreads) void gmres_solve_x_kernel(int n, long lon
                 acc.x *= d.x;
                 acc.y *= d.y;
             }
+            if (comb) {
+                store2(comb + i, acc);
+                continue;
+            }
             double2 xv = load2(x + i);
             xv.x += acc.x;
             xv.y += acc.y;
@@ -249,7 +255,32 @@ __global__ __launch_bounds__(kThreads) void gmres_solve_x_kernel(int n, long lon
             double acc = 0.0;
             for (int c0 = 0; c0 < J; ++c0) acc = fma(y_sh[c0], V[(size_t)c0 * ld + i], acc);
             if (dinv) acc *= dinv[i];
-            x[i] += acc;
+            if (comb)
+                comb[i] = acc;
+            else
+                x[i] += acc;
+        }
+    }
+}
+
+// x += z, z = M^-1 (sum y_i v_i), if the cycle counted a step (J as in solve_x: without one, solve_x wrote no combination and z
+// holds nothing of this cycle).  Does not look at the status.
+__global__ __launch_bounds__(kThreads) void gmres_add_kernel(int n, const double* __restrict__ z, double* __restrict__ x,
+                                                             const double* __restrict__ tail)
+{
+    const int J = ((const int*)(tail + T_FLAGS))[F_ITERS] - ((const int*)(tail + T_CYCLE))[0];  // (the same word in every thread)
+    if (J <= 0 || J > kM) return;
+    const int stride = (int)gridDim.x * kThreads;
+    for (int p = blockIdx.x * kThreads + threadIdx.x; 2 * (long long)p < n; p += stride) {
+        const size_t i = 2 * (size_t)p;
+        if (i + 1 < (size_t)n) {
+            const double2 zv = load2(z + i);
+            double2 xv = load2(x + i);
+            xv.x += zv.x;
+            xv.y += zv.y;
+            store2(x + i, xv);
+        } else {
+            x[i] += z[i];
         }
     }
 }
@@ -261,7 +292,14 @@ struct Launcher {
     hipStream_t st;
     double *V, *w, *z, *s, *tail;
     const double* dinv;
+    const ehyb_bilu* M;  // ehyb_gmres_bilu: the preconditioner, applied by ehyb_bic_apply_kernel (dinv is NULL then)
 
+    // z = M^-1 (basis column j), read where it lies; like the vector kernels it returns at once when the status is set
+    int precondition(int j) const
+    {
+        if (!M) return EHYB_OK;
+        return bic_apply_columns(&M->core, st, V + (size_t)j * ld, ld, z, ld, 1, (const int*)(tail + T_FLAGS) + F_STATUS, 1, true);
+    }
     void start(const double* b) const { hipLaunchKernelGGL(gmres_start_kernel, dim3(grid), dim3(kThreads), 0, st, n, b, w, s, tail); }
     void dots(int cnt) const { hipLaunchKernelGGL(gmres_dots_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, cnt, s, tail); }
     void update(int cnt, int pass, int last) const
@@ -270,13 +308,22 @@ struct Launcher {
     }
     void next(int j, int passes, double thr) const
     {
-        hipLaunchKernelGGL(gmres_next_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, dinv, z, s, tail, j, passes, thr);
+        hipLaunchKernelGGL(gmres_next_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, w, dinv, M ? nullptr : z, s, tail, j, passes, thr);
     }
-    void solve_x(double* x) const { hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, dinv, x, tail); }
+    // x += M^-1 (sum y_i v_i); with M the combination goes through w (free at a cycle's end), one apply and the add kernel
+    int solve_x(double* x) const
+    {
+        hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(grid), dim3(kThreads), 0, st, n, ld, V, dinv, x, tail, M ? w : nullptr);
+        if (!M) return EHYB_OK;
+        const int rc = bic_apply_columns(&M->core, st, w, ld, z, ld, 1, nullptr);
+        if (rc != EHYB_OK) return rc;
+        hipLaunchKernelGGL(gmres_add_kernel, dim3(grid), dim3(kThreads), 0, st, n, z, x, tail);
+        return EHYB_OK;
+    }
 };
 
 // transposed: every multiply is ehyb_spmv_t (A^T x = b; no walk: the transposed launch has none)
-int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double* b, double* x, int m, int passes, int max_iter, double rtol,
+int gmres_solve(const char* who, ehyb_plan* P, bool transposed, const double* dinv, const ehyb_bilu* M, const double* b, double* x, int m, int passes, int max_iter, double rtol,
                 void* stream, int* iters_done, double* rel_residual)
 {
     const int n = P->host.n_cols;
@@ -288,7 +335,7 @@ int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double*
     HIP_TRY(hipMalloc((void**)&V.p, std::max<size_t>(1, ld * (size_t)(m + 1)) * sizeof(double)));
     const hipStream_t st = L.st;
     double* tail = s + (size_t)G_COUNT * kMaxGrid;
-    const Launcher K{L.grid, n, (long long)ld, st, V.p, w, z, s, tail, dinv};
+    const Launcher K{L.grid, n, (long long)ld, st, V.p, w, z, s, tail, dinv, M};
     const double thr = rtol * rtol;
     HIP_TRY(hipMemsetAsync(tail, 0, (size_t)T_COUNT * sizeof(double), st));
 
@@ -300,6 +347,7 @@ int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double*
         K.start(b);
         K.next(-1, passes, thr);
         for (int j = 0; j < steps; ++j) {
+            if ((rc = K.precondition(j)) != EHYB_OK) return rc;
             rc = multiply(z, w, j & 1 ? EHYB_WALK_LAST_TO_FIRST : EHYB_WALK_FIRST_TO_LAST);
             if (rc != EHYB_OK) return rc;
             for (int p = 0; p < passes; ++p) {
@@ -308,8 +356,7 @@ int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double*
             }
             K.next(j, passes, thr);
         }
-        K.solve_x(x);
-        return EHYB_OK;
+        return K.solve_x(x);
     };
 
     // a full cycle is captured once and replayed; cfg.graphs = 2 keeps the plain launches, and so does a capture that fails
@@ -342,11 +389,11 @@ int gmres_solve(ehyb_plan* P, bool transposed, const double* dinv, const double*
     if (f[F_STATUS] != ST_BREAKDOWN) return EHYB_OK;
     EHYB_FAIL(EHYB_ERR_ARG, "%s: breakdown after %d iterations (a non-finite b.b, r.r or Hessenberg entry, a zero or non-finite gamma, "
                             "or h_{j+1} = 0 short of convergence: a singular system)",
-              transposed ? "ehyb_gmres_t" : "ehyb_gmres", f[F_ITERS]);
+              who, f[F_ITERS]);
 }
 
 // the checks of both entry points, in the order ehyb.h states, then the solve
-int gmres_entry(const char* who, bool transposed, ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes,
+int gmres_entry(const char* who, bool transposed, ehyb_plan* P, const double* dinv, const ehyb_bilu* M, bool with_bilu, const double* b, double* x, int restart, int ortho_passes,
                 int max_iter, double rtol, void* stream, int* iters_done, double* rel_residual)
 {
     int rc = solve_args(who, P, b && x, max_iter, rtol);
@@ -354,8 +401,8 @@ int gmres_entry(const char* who, bool transposed, ehyb_plan* P, const double* di
     if (restart < 0 || restart > kM || ortho_passes < 0 || ortho_passes > 2)
         EHYB_FAIL(EHYB_ERR_ARG, "%s: restart %d (0 .. %d), ortho_passes %d (0 .. 2)", who, restart, kM, ortho_passes);
     if (transposed && (rc = ehyb_spmv_t_supported(P)) != EHYB_OK) return rc;  // (the form is named in ehyb_last_error)
-    if ((rc = solve_uploaded(who, P)) != EHYB_OK) return rc;
-    return gmres_solve(P, transposed, dinv, b, x, restart == 0 ? 30 : restart, ortho_passes == 1 ? 1 : 2, max_iter, rtol, stream, iters_done,
+    if ((rc = with_bilu ? bilu_solver_args(who, P, M) : solve_uploaded(who, P)) != EHYB_OK) return rc;
+    return gmres_solve(who, P, transposed, dinv, M, b, x, restart == 0 ? 30 : restart, ortho_passes == 1 ? 1 : 2, max_iter, rtol, stream, iters_done,
                        rel_residual);
 }
 
@@ -364,13 +411,20 @@ int gmres_entry(const char* who, bool transposed, ehyb_plan* P, const double* di
 extern "C" int ehyb_gmres(ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes, int max_iter,
                           double rtol, void* stream, int* iters_done, double* rel_residual)
 {
-    return gmres_entry("ehyb_gmres", false, P, dinv, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
+    return gmres_entry("ehyb_gmres", false, P, dinv, nullptr, false, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
 }
 
 extern "C" int ehyb_gmres_t(ehyb_plan* P, const double* dinv, const double* b, double* x, int restart, int ortho_passes, int max_iter,
                             double rtol, void* stream, int* iters_done, double* rel_residual)
 {
-    return gmres_entry("ehyb_gmres_t", true, P, dinv, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
+    return gmres_entry("ehyb_gmres_t", true, P, dinv, nullptr, false, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
+}
+
+// right-preconditioned with the block ILU(0) of `bilu`: z = M^-1 v_j by the apply kernel on the basis column where it lies
+extern "C" int ehyb_gmres_bilu(ehyb_plan* P, ehyb_bilu* bilu, const double* b, double* x, int restart, int ortho_passes, int max_iter,
+                               double rtol, void* stream, int* iters_done, double* rel_residual)
+{
+    return gmres_entry("ehyb_gmres_bilu", false, P, nullptr, bilu, true, b, x, restart, ortho_passes, max_iter, rtol, stream, iters_done, rel_residual);
 }
 
 // ------------------------------------------------------------------ building blocks for a caller that owns the loop
@@ -463,7 +517,29 @@ extern "C" int ehyb_gmres_solve_x_step(int n, int64_t ld, const double* V, const
     if (rc != EHYB_OK) return rc;
     if ((rc = check_pairs("ehyb_gmres_solve_x_step", n, ld, {V, dinv, x})) != EHYB_OK) return rc;
     hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, dinv, x,
-                       step_tail(s));
+                       step_tail(s), nullptr);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+// solve_x with the combination written to comb_dev and x untouched (ehyb_gmres_bilu)
+extern "C" int ehyb_bilu_gmres_combine_step(int n, int64_t ld, const double* V, double* comb, double* s, void* stream)
+{
+    int rc = check_step("ehyb_bilu_gmres_combine_step", n, {V, comb, s});
+    if (rc != EHYB_OK) return rc;
+    if ((rc = check_pairs("ehyb_bilu_gmres_combine_step", n, ld, {V, comb})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_solve_x_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, (long long)ld, V, nullptr, nullptr, step_tail(s), comb);
+    HIP_TRY(hipGetLastError());
+    return EHYB_OK;
+}
+
+// x += z if the cycle counted a step (ehyb_gmres_bilu's last kernel of a cycle)
+extern "C" int ehyb_bilu_gmres_add_step(int n, const double* z, double* x, double* s, void* stream)
+{
+    int rc = check_step("ehyb_bilu_gmres_add_step", n, {z, x, s});
+    if (rc != EHYB_OK) return rc;
+    if ((rc = check_pairs("ehyb_bilu_gmres_add_step", n, n + (n & 1), {z, x})) != EHYB_OK) return rc;
+    hipLaunchKernelGGL(gmres_add_kernel, dim3(kStepGrid), dim3(kThreads), 0, (hipStream_t)stream, n, z, x, step_tail(s));
     HIP_TRY(hipGetLastError());
     return EHYB_OK;
 }

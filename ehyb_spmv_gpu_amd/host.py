@@ -722,6 +722,25 @@ class Plan:
         The multiplies are as wide as spmm_max_k allows (build the plan with lds_doubles = 20480 // k)."""
         return self._solve("ehyb_bicgstab_multi", B, X0, inv_diag, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True)
 
+    def bicgstab_bilu(self, b, bilu, x0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_bicgstab_bilu: bicgstab right-preconditioned with the block ILU(0) z = P^T (L U)^-1 P r of `bilu` (a Bilu of the
+        reordered matrix this plan was built from) instead of the diagonal.  -> (x, iterations, relative residual), breakdowns as
+        bicgstab."""
+        return self._solve("ehyb_bicgstab_bilu", b, x0, None, (max_iter, rtol, check_every), stream, allow_breakdown, inner=bilu, counters=1, diag=False)
+
+    def bicgstab_bilu_multi(self, B, bilu, X0=None, max_iter=1000, rtol=1e-10, check_every=10, allow_breakdown=False, stream=0):
+        """ehyb_bicgstab_bilu_multi: k independent bicgstab_bilu solves that share both multiplies and both applies of every
+        iteration; B, X0 (k, n), column j solved as bicgstab_bilu(B[j]) would -- with plain storage bit for bit.  -> (X (k, n),
+        iterations (k,), relative residuals (k,))."""
+        return self._solve("ehyb_bicgstab_bilu_multi", B, X0, None, (max_iter, rtol, check_every), stream, allow_breakdown, multi=True, inner=bilu,
+                           counters=1, diag=False)
+
+    def gmres_bilu(self, b, bilu, x0=None, restart=30, ortho_passes=2, max_iter=1000, rtol=1e-10, allow_breakdown=False, stream=0):
+        """ehyb_gmres_bilu: gmres right-preconditioned with the block ILU(0) of `bilu` (a Bilu of the reordered matrix this plan was
+        built from) instead of the diagonal.  -> (x, steps, relative residual), breakdowns as gmres."""
+        return self._solve("ehyb_gmres_bilu", b, x0, None, (int(restart), int(ortho_passes), max_iter, rtol), stream, allow_breakdown, inner=bilu,
+                           counters=1, diag=False)
+
     def minres(self, b, x0=None, max_iter=1000, rtol=1e-10, check_every=10, inv_diag=None, allow_breakdown=False, stream=0):
         """ehyb_minres: MINRES for a symmetric, possibly indefinite system on the device; inv_diag: an optional POSITIVE
         diagonal preconditioner (minres_inv_diag gives 1 / |a_ii|); b, x0, inv_diag in the permuted numbering.
@@ -1202,13 +1221,18 @@ class Bic:
     block_rows 0: whole partitions (cut where longer than EHYB_BIC_MAX_BLOCK); order "stored": the rows as they stand,
     "colour": greedy colouring inside every block (a few levels, more iterations).  upload=False keeps it on the host (no GPU
     needed)."""
+    _PREFIX, _ARRAYS = "ehyb_bic", BIC_ARRAYS      # (Bilu: the same entry points under another name)
+
+    def _call(self, what, *args):
+        name = f"{self._PREFIX}_{what}"
+        _check(getattr(self.lib, name)(*args), name)
 
     def __init__(self, matrix, block_rows=0, order="stored", upload=True):
         self.lib = _lib.load()
         self.h = C.c_void_p()
         self.n = matrix.n
         self.order = order
-        _check(self.lib.ehyb_bic_create_host(C.byref(matrix.c), int(block_rows), BIC_ORDERS[order], C.byref(self.h)), "ehyb_bic_create_host")
+        self._call("create_host", C.byref(matrix.c), int(block_rows), BIC_ORDERS[order], C.byref(self.h))
         if upload:
             self.upload()
 
@@ -1234,16 +1258,16 @@ class Bic:
         return self
 
     def upload(self):
-        _check(self.lib.ehyb_bic_upload(self.h), "ehyb_bic_upload")
+        self._call("upload", self.h)
         return self
 
     def array(self, name):
         """ehyb_bic_host_array: "block_ptr" (nb + 1,), "perm" (n,), "row_ptr" (n + 1,) int64, "cols" (block-local positions) and
         "vals" (nnz(L),) -- L in CSR form in position order, strictly lower part --, "dinv", "level_f", "level_b" (n,), "shift"
         (nb,), "counts" (4,) -- copies"""
-        which, dtype = BIC_ARRAYS[name]
+        which, dtype = self._ARRAYS[name]
         p, cnt = C.c_void_p(), C.c_int64()
-        _check(self.lib.ehyb_bic_host_array(self.h, which, C.byref(p), C.byref(cnt)), "ehyb_bic_host_array")
+        self._call("host_array", self.h, which, C.byref(p), C.byref(cnt))
         if cnt.value == 0 or not p.value:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * (cnt.value * np.dtype(dtype).itemsize)).from_address(p.value)
@@ -1252,7 +1276,7 @@ class Bic:
     @property
     def max_k(self):
         """ehyb_bic_max_k: the columns one launch of the apply kernel serves"""
-        return int(self.lib.ehyb_bic_max_k(self.h))
+        return int(getattr(self.lib, f"{self._PREFIX}_max_k")(self.h))
 
     @property
     def blocks(self):
@@ -1275,7 +1299,7 @@ class Bic:
     def stream_info(self):
         """ehyb_bic_stream_info -> (bytes of the two device streams, their entries without padding, the workgroup size)"""
         b, e, t = C.c_int64(), C.c_int64(), C.c_int()
-        _check(self.lib.ehyb_bic_stream_info(self.h, C.byref(b), C.byref(e), C.byref(t)), "ehyb_bic_stream_info")
+        self._call("stream_info", self.h, C.byref(b), C.byref(e), C.byref(t))
         return b.value, e.value, t.value
 
     def apply(self, R, ld=None, active=None, Z0=None, stream=0):
@@ -1295,13 +1319,12 @@ class Bic:
             start[:, :n] = np.asarray(Z0, dtype=np.float64).reshape(k, n)
         dr, dz = DeviceBuffer(k * ld).upload(staged.ravel()), DeviceBuffer(k * ld).upload(start.ravel())
         if active is None:
-            _check(self.lib.ehyb_bic_apply(self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(stream)), "ehyb_bic_apply")
+            self._call("apply", self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(stream))
         else:
             flags = np.zeros(k + (k & 1), dtype=np.int32)       # (a DeviceBuffer holds doubles: two int32 each)
             flags[:k] = np.asarray(active, dtype=np.int32)
             da = DeviceBuffer(len(flags) // 2).upload(flags.view(np.float64))
-            _check(self.lib.ehyb_bic_apply_step(self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(da.ptr), C.c_void_p(stream)),
-                   "ehyb_bic_apply_step")
+            self._call("apply_step", self.h, C.c_void_p(dr.ptr), ld, C.c_void_p(dz.ptr), ld, k, C.c_void_p(da.ptr), C.c_void_p(stream))
         _check(self.lib.ehyb_dev_sync(), "ehyb_dev_sync")
         Z = dz.download().reshape(k, ld)
         self.last_pad = Z[:, n:]          # what lies between the columns: untouched (NaN) if the kernel keeps to its rows
@@ -1309,7 +1332,7 @@ class Bic:
 
     def destroy(self):
         if self.h:
-            self.lib.ehyb_bic_destroy(self.h)
+            getattr(self.lib, f"{self._PREFIX}_destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -1317,6 +1340,45 @@ class Bic:
             self.destroy()
         except Exception:
             pass
+
+
+BILU_ARRAYS = {"block_ptr": (0, np.int32), "perm": (1, np.int32), "l_row_ptr": (2, np.int64), "l_cols": (3, np.int32), "l_vals": (4, np.float64),
+               "u_row_ptr": (5, np.int64), "u_cols": (6, np.int32), "u_vals": (7, np.float64), "u_dinv": (8, np.float64), "level_f": (9, np.int32),
+               "level_b": (10, np.int32), "shift": (11, np.float64), "counts": (12, np.int64)}
+
+
+class Bilu(Bic):
+    """ehyb_bilu: the block ILU(0) preconditioner of Plan.gmres_bilu and Plan.bicgstab_bilu for a reordered (unsymmetric) matrix --
+    the matrix the plan was built from.  L U ~ A_b on the pattern of every diagonal block (the blocks and orders of Bic), applied
+    by Bic's kernel: a unit-lower forward solve and an upper backward solve in one workgroup's LDS.  upload=False keeps it on the
+    host (no GPU needed).  array(name): "block_ptr", "perm", "l_row_ptr", "l_cols", "l_vals" (the strictly lower part of L),
+    "u_row_ptr", "u_cols", "u_vals" (the strictly upper part of U), "u_dinv" (1 / u_ii), "level_f", "level_b", "shift", "counts".
+    blocks, shifted_blocks, fallback_blocks, levels, max_k, stream_info, apply (Z = P^T (L U)^-1 P R) and destroy as Bic's."""
+    _PREFIX, _ARRAYS = "ehyb_bilu", BILU_ARRAYS
+
+    @classmethod
+    def raw(cls, block_ptr, l_row_ptr, l_cols, l_vals, u_row_ptr, u_cols, u_vals, u_dinv, upload=True):
+        """ehyb_bilu_create_raw: an object from a caller's strictly lower L and strictly upper U in CSR form (block-local columns)
+        and 1 / u_ii, with the identity order -- for tests of the kernels."""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.order = _lib.load(), C.c_void_p(), "stored"
+        bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
+        dv = np.ascontiguousarray(u_dinv, dtype=np.float64)
+        self.n = len(dv)
+        tri = []
+        for rp, cl, vl in ((l_row_ptr, l_cols, l_vals), (u_row_ptr, u_cols, u_vals)):
+            rp = np.ascontiguousarray(rp, dtype=np.int64)
+            cl = np.ascontiguousarray(cl, dtype=np.int32)
+            vl = np.ascontiguousarray(vl, dtype=np.float64)
+            assert rp.shape == (self.n + 1,) and len(cl) == len(vl) == rp[-1] and len(bp) >= 2
+            if len(cl) == 0:            # (an empty array has no address worth passing; one unread element)
+                cl, vl = np.zeros(1, dtype=np.int32), np.zeros(1)
+            tri += [rp, cl, vl]
+        self._call("create_raw", self.n, len(bp) - 1, _ptr(bp, C.c_int32), _ptr(tri[0], C.c_int64), _ptr(tri[1], C.c_int32), _ptr(tri[2], C.c_double),
+                   _ptr(tri[3], C.c_int64), _ptr(tri[4], C.c_int32), _ptr(tri[5], C.c_double), _ptr(dv, C.c_double), C.byref(self.h))
+        if upload:
+            self.upload()
+        return self
 
 
 def fsai_factor_step(indptr, indices, data, g_ptr, g_cols, stream=0):

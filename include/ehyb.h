@@ -1382,7 +1382,7 @@ int  ehyb_fsai_tt_step(int n, const double* t_dev, double* s_dev, int rz, void* 
  *   launches, on any stream and for any check_every, and column j of a k-column solve equals the one-vector solve.
  *   In this order: EHYB_ERR_ARG for what ehyb_pcg rejects, then for a null object or one with another number of rows;
  *   EHYB_ERR_STATE for a plan, then an object, that was never uploaded.  All before any device work.
- * Out of scope: fp32 storage of L, a numeric phase on the device, overlapping blocks, ILU for GMRES / BiCGSTAB, several GPUs.
+ * Out of scope: fp32 storage of L, a numeric phase on the device, overlapping blocks, several GPUs.  (ILU for GMRES / BiCGSTAB: ehyb_bilu below.)
  */
 #define EHYB_BIC_MAX_BLOCK 20480
 enum { EHYB_BIC_ORDER_STORED = 0, EHYB_BIC_ORDER_COLOUR = 1 };
@@ -1405,6 +1405,87 @@ int  ehyb_pcg_bic(ehyb_plan* plan, ehyb_bic* f, const double* b_dev, double* x_d
                   void* stream, int* iters_done, double* rel_residual);
 int  ehyb_pcg_bic_multi(ehyb_plan* plan, ehyb_bic* f, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k, int max_iter,
                         double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+
+/*
+ * BLOCK ILU(0) (BILU) FOR GMRES AND BICGSTAB: the unsymmetric counterpart of BIC.  M^-1 = P^T (L U)^-1 P, L unit lower and U upper,
+ * block diagonal, L U ~ A_b on the pattern of every diagonal block A_b.  The blocks and the local order are ehyb_bic's, by the same
+ * code (EHYB_BIC_MAX_BLOCK, EHYB_BIC_ORDER_*); the colouring counts every in-block off-diagonal entry (i, j) as an edge, both ways:
+ * the pattern of A_b + A_b^T.  The device side is ehyb_bic's too: the same two streams, the same apply kernel
+ * x = (x - sum v x[col]) * dinv -- forward with the strictly lower part of L and dinv = 1 (an exact multiply), backward with the
+ * strictly upper part of U and dinv = 1 / u_ii --, the same upload, release, max_k and stream_info.
+ *
+ * Definition.
+ *   A_b.  The entries of A with row and column inside the block, in local order (entry (i, j) lands in row pos i, column pos j);
+ *   what lies outside the block is dropped (block Jacobi).  A column stored more than once in a row is summed first, in stored order.
+ *   The diagonal is always part of the pattern: a row that stores none holds a zero there.  The pattern may be structurally
+ *   unsymmetric; a row may lack entries below or above the diagonal.
+ *   Factor.  Row-wise IKJ on the pattern, in place: for rows i rising, for the k < i of row i rising: l_ik = w_k / u_kk (a true
+ *   division), then for the j > k of row k rising that row i holds: w_j = w_j - l_ik u_kj; what is left of row i right of the
+ *   diagonal is U's, w_i = u_ii.  The host rounds every product and difference.  (L U)_ij = a_ij at every (i, j) of the pattern.
+ *   U_DINV[i] = 1 / u_ii is stored, and the backward solve multiplies by it.
+ *   Pivot rule.  s_i = sum_j |a_ij| over the block row (duplicates summed, columns rising).  u_ii is accepted if it is finite and
+ *   |u_ii| > 2^-26 s_i.  Otherwise the WHOLE block is refactored from A_b + alpha diag(s) (a_ii + alpha s_i, rounded twice), alpha =
+ *   2^-10, 2^-8, ..., 2^10 in turn -- s rather than a_ii, so a zero diagonal is cured too; SHIFT[b] is the alpha that worked, 0 where
+ *   none was needed.  If none works the block takes its Jacobi form: no entries, U_DINV = 1 / a_ii (1 where a_ii is 0 or not
+ *   finite), SHIFT[b] = -1.
+ *   Levels.  LEVEL_F[p] = 1 + max LEVEL_F[q] over the entries (p, q) of L's row p, 0 if it has none; LEVEL_B[p] = 1 + max
+ *   LEVEL_B[q] over the entries (p, q) of U's row p, 0 if it has none.  They differ where the pattern is unsymmetric.
+ *
+ * ehyb_bilu_create_host (no GPU needed; the same bits for any number of OpenMP threads: blocks are dealt to threads whole):
+ *   arguments and EHYB_ERR_ARG as ehyb_bic_create_host, but that no diagonal is refused.
+ * ehyb_bilu_create_raw (for tests of the kernels): both triangles in CSR form with block-local columns, rising, and 1 / u_ii; the
+ *   identity order.  EHYB_ERR_ARG as ehyb_bic_create_raw, for either triangle.
+ * ehyb_bilu_host_array: which = EHYB_BILU_BLOCK_PTR int32[nb + 1], _PERM int32[n], _L_ROW_PTR / _U_ROW_PTR int64[n + 1], _L_COLS /
+ *   _U_COLS int32 (block-local positions), _L_VALS / _U_VALS double (the strict triangles in CSR form in position order), _U_DINV
+ *   double[n], _LEVEL_F / _LEVEL_B int32[n], _SHIFT double[nb], _COUNTS int64[4] {blocks, shifted blocks, fallback blocks, most
+ *   levels of any block in either direction}.
+ * ehyb_bilu_max_k, _upload, _destroy, _stream_info, _apply (Z = P^T (L U)^-1 P R), _apply_step: as their ehyb_bic_* namesakes --
+ *   the same code on the same streams; the bits of a column do not depend on k.
+ *
+ * ehyb_gmres_bilu: ehyb_gmres right-preconditioned with M instead of diag(A) -- A M^-1 y = b, x = M^-1 y, so the residual tested
+ *   is the true one.  Every rule of ehyb_gmres holds as stated there (stop, breakdown, the counter, NULL outputs, the same bits
+ *   from run to run, for graphs and plain launches and on any stream with plain storage).  z = M^-1 v_j is one launch of the apply
+ *   kernel that reads column j of the basis where it lies (and returns at once after a stop); no second basis is kept (M is
+ *   fixed: this is not flexible GMRES).  At a cycle's end the back substitution writes sum y_i v_i into w, one apply -- whatever
+ *   the status -- makes z = M^-1 w, and gmres_add_kernel adds z to x (the pair walk of the other GMRES kernels; nothing if the
+ *   cycle counted no step).  A cycle stays one hipGraph.
+ * ehyb_bicgstab_bilu / ehyb_bicgstab_bilu_multi: ehyb_bicgstab / _multi in the textbook right-preconditioned form: p^ = M^-1 p,
+ *   v = A p^, s = r - alpha v, s^ = M^-1 s, t = A s^, x += alpha p^ + omega s^, r = s - omega t, p = r + beta (p - omega v) on the
+ *   unpreconditioned p (one vector more than ehyb_bicgstab).  Two applies per iteration, each ceil(k / ehyb_bilu_max_k) launches
+ *   that skip a stopped column as the vector kernels do; the vector kernels are ehyb_bicgstab's with inv_diag = NULL.  Stop, breakdown,
+ *   status words, check_every and outputs as ehyb_bicgstab(_multi); with plain storage column j equals the single solve of b_j bit
+ *   for bit.
+ *   In this order: EHYB_ERR_ARG for what the Jacobi solver rejects, then for a null factor or one with another number of rows;
+ *   EHYB_ERR_STATE for a plan, then a factor, that was never uploaded.  All before any device work.
+ * ehyb_bilu_gmres_combine_step / ehyb_bilu_gmres_add_step (building blocks, as the other ehyb_gmres_*_step): solve_x with the combination
+ *   sum y_i v_i written to comb_dev and no x; x += z if J > 0 (J as in solve_x).  comb_dev, z_dev, x_dev 16-byte aligned.
+ * Out of scope: a numeric phase on the device for new values on an unchanged pattern, ILU(k), ILUT, fp32 factors, overlapping
+ * blocks, ehyb_gmres_t (it needs M^-T), MINRES and LSQR, several GPUs.
+ */
+enum {
+    EHYB_BILU_BLOCK_PTR = 0, EHYB_BILU_PERM = 1, EHYB_BILU_L_ROW_PTR = 2, EHYB_BILU_L_COLS = 3, EHYB_BILU_L_VALS = 4,
+    EHYB_BILU_U_ROW_PTR = 5, EHYB_BILU_U_COLS = 6, EHYB_BILU_U_VALS = 7, EHYB_BILU_U_DINV = 8, EHYB_BILU_LEVEL_F = 9,
+    EHYB_BILU_LEVEL_B = 10, EHYB_BILU_SHIFT = 11, EHYB_BILU_COUNTS = 12
+};
+typedef struct ehyb_bilu ehyb_bilu;
+int  ehyb_bilu_create_host(const matrixCOO* m, int block_rows, int order, ehyb_bilu** out);
+int  ehyb_bilu_create_raw(int n, int nb, const int32_t* block_ptr, const int64_t* l_row_ptr, const int32_t* l_cols, const double* l_vals,
+                          const int64_t* u_row_ptr, const int32_t* u_cols, const double* u_vals, const double* u_dinv, ehyb_bilu** out);
+int  ehyb_bilu_host_array(const ehyb_bilu* f, int which, const void** ptr, int64_t* count);
+int  ehyb_bilu_max_k(const ehyb_bilu* f);
+int  ehyb_bilu_upload(ehyb_bilu* f);
+void ehyb_bilu_destroy(ehyb_bilu* f);
+int  ehyb_bilu_stream_info(const ehyb_bilu* f, int64_t* bytes, int64_t* entries, int* threads);
+int  ehyb_bilu_apply(ehyb_bilu* f, const double* R_dev, int64_t ldr, double* Z_dev, int64_t ldz, int k, void* stream);
+int  ehyb_bilu_apply_step(ehyb_bilu* f, const double* R_dev, int64_t ldr, double* Z_dev, int64_t ldz, int k, const int* active_dev, void* stream);
+int  ehyb_gmres_bilu(ehyb_plan* plan, ehyb_bilu* f, const double* b_dev, double* x_dev, int restart, int ortho_passes, int max_iter,
+                     double rtol, void* stream, int* iters_done, double* rel_residual);
+int  ehyb_bicgstab_bilu(ehyb_plan* plan, ehyb_bilu* f, const double* b_dev, double* x_dev, int max_iter, double rtol, int check_every,
+                        void* stream, int* iters_done, double* rel_residual);
+int  ehyb_bicgstab_bilu_multi(ehyb_plan* plan, ehyb_bilu* f, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int k, int max_iter,
+                              double rtol, int check_every, void* stream, int* iters_done, double* rel_residual);
+int  ehyb_bilu_gmres_combine_step(int n, int64_t ld, const double* V_dev, double* comb_dev, double* s_dev, void* stream);
+int  ehyb_bilu_gmres_add_step(int n, const double* z_dev, double* x_dev, double* s_dev, void* stream);
 
 /*
  * The vector kernels of ehyb_pcg as building blocks for a caller that owns the loop -- the multi-GPU CG of
